@@ -13,7 +13,12 @@ Launch:  python bench.py [--gpus N --steps K --warmup W]
             --master-port P bench.py --gpus N --steps K --warmup W      (one rank per GPU, RCCL)
          or plain `python bench.py --gpus N ...` from a bare shell: with no WORLD_SIZE in the environment the script
          re-launches itself as N ranks through torch.distributed.run (self_launch below) and relays rank 0's JSON line.
-Prints ONE JSON line on rank 0 (roofline + cpu_baseline objects: see DESIGN.md "Measurement").
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up (W steps, plus the launch-mode calibration of --graph auto), times
+exactly K steps once and prints the headline line.  --full adds everything else the line can carry: the K-step region repeated with
+the median reported, roofline + roofline_extra from per-kernel event timings, the exposed all-reduce, the one-rank RCCL probe, the
+EdgeConv-stack-only rate and the cpu_baseline object (see DESIGN.md "Measurement").
+--dump-outputs DIR writes what the last timed step returned (gradient bucket, accuracy, loss) and the parameters its Adam update
+left, as DIR/<name>.npy in float32; the inputs and initial weights are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -291,8 +296,16 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--kernel-table", action="store_true", help="print per-kernel event timings to stderr")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the timed region repeated (--repeats) with the median reported, "
+                         "the per-kernel table and roofline figures, the exposed all-reduce, the one-rank RCCL probe, the "
+                         "EdgeConv-stack-only rate and the CPU baseline.  Without it a run warms up, times exactly --steps "
+                         "steps once and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (gradient bucket, accuracy, loss) and the parameters it "
+                         "left as DIR/<name>.npy (float32, rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--kernel-table", action="store_true", help="--full: print per-kernel event timings to stderr")
     ap.add_argument("--backend", default="rccl", choices=["rccl", "nccl", "gloo"],
                     help="N > 1: rccl (default) = the library's own RCCL communicator (dgcnn/rccl.py over csrc/comm.cc, no "
                          "torch.distributed); nccl = RCCL through torch.distributed; gloo = only for the single-GPU-box sanity run "
@@ -301,10 +314,10 @@ def main():
     ap.add_argument("--deterministic", action="store_true", help="(the default since round 5; kept so that old command lines run)")
     ap.add_argument("--atomics", action="store_true", help="the atomics mode instead of the deterministic kernels (32 statistics slots, "
                     "several writers each, unsorted adjacency): 3-4 %% faster, reproducible to ~1e-7 per step only (DESIGN 2)")
-    ap.add_argument("--repeats", type=int, default=0, help="the K-step timed region is run this many times back to back and the MEDIAN "
-                    "region is reported (all of them in config.per_repeat_ms_per_step); 0 = as many as fill ~2 s, at least 5")
-    ap.add_argument("--no-edgeconv-stack", action="store_true", help="skip the EdgeConv-stack-only passes after the timed region "
-                    "(profiling runs)")
+    ap.add_argument("--repeats", type=int, default=0, help="--full: the K-step timed region is run this many times back to back and the "
+                    "MEDIAN region is reported (all of them in config.per_repeat_ms_per_step); 0 = as many as fill ~2 s, at least 5")
+    ap.add_argument("--no-edgeconv-stack", action="store_true", help="--full: skip the EdgeConv-stack-only passes after the timed "
+                    "region (profiling runs)")
     ap.add_argument("--graph", default="auto", choices=["0", "1", "plan", "auto"],
                     help="how the forward+backward tower is launched (the reference replays a static TF graph with sess.run): "
                          "plan = recorded launch plan re-issued from one C loop (csrc/plan.cc); 1 = captured HIP graph; 0 = eager "
@@ -318,6 +331,8 @@ def main():
                          "gather / JSON path of an N-rank run with a stand-in step and the communicator class named by "
                          "$DGCNN_BENCH_GROUP (module:Class); the line says dry_run and measures nothing")
     args = ap.parse_args()
+    if not args.full and (args.repeats or args.kernel_table):
+        ap.error("--repeats and --kernel-table need --full")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -398,22 +413,24 @@ def main():
         step()
         fence()
     tv.use_graph(first_mode)
-    # kernel table from a step with the side stream switched off (launches serialised): per-kernel event times are
-    # then those of each kernel ALONE; in the timed region weight-gradient GEMMs overlap the backward chain
-    from dgcnn import _engine as E
-    side = E.WGRAD_SIDE_STREAM
-    E.WGRAD_SIDE_STREAM = False
-    H.TIMER = H.Timer()
-    step()
-    table = H.TIMER.summary()
-    H.TIMER = None
-    E.WGRAD_SIDE_STREAM = side
-    # the kernel with the largest time in that step.  The three operand layouts of the head GEMM (forward / data gradient / weight
-    # gradient: the same flops each) are within a few per cent of each other, so "largest" flipped from run to run; among tags within
-    # 5 % of the largest the choice is fixed (first in name order) so that successive bench lines report the same kernel
-    tmax = max(v[1] for v in table.values())
-    dominant = sorted(t for t in table if table[t][1] >= 0.95 * tmax)[0]
-    for _ in range(max(args.warmup - 2, 0)):
+    side = table = dominant = None
+    if args.full:
+        # kernel table from a step with the side stream switched off (launches serialised): per-kernel event times are
+        # then those of each kernel ALONE; in the timed region weight-gradient GEMMs overlap the backward chain
+        from dgcnn import _engine as E
+        side = E.WGRAD_SIDE_STREAM
+        E.WGRAD_SIDE_STREAM = False
+        H.TIMER = H.Timer()
+        step()
+        table = H.TIMER.summary()
+        H.TIMER = None
+        E.WGRAD_SIDE_STREAM = side
+        # the kernel with the largest time in that step.  The three operand layouts of the head GEMM (forward / data gradient / weight
+        # gradient: the same flops each) are within a few per cent of each other, so "largest" flipped from run to run; among tags within
+        # 5 % of the largest the choice is fixed (first in name order) so that successive bench lines report the same kernel
+        tmax = max(v[1] for v in table.values())
+        dominant = sorted(t for t in table if table[t][1] >= 0.95 * tmax)[0]
+    for _ in range(max(args.warmup - (2 if args.full else 1), 0)):
         step()
     calib = None
     if args.graph == "auto":                    # untimed calibration: which launch mode is faster on THIS host + GPU
@@ -454,21 +471,24 @@ def main():
 
     # ---- timed regions: R times EXACTLY K steps, each bracketed by fence() on both sides, no instrumentation (an event pair
     # around every launch of the dominant kernel perturbs what it measures: with the plane GEMMs +0.1 .. +1.9 ms per step,
-    # profiles/r03/bench_events.txt).  The MEDIAN region is the reported one; all R are in the line. ----
+    # profiles/r03/bench_events.txt).  A plain run times one region (R = 1); with --full the MEDIAN of R regions is the reported
+    # one and all R are in the line. ----
     H.TIMER = None
-    step()
-    fence()
-    t0 = time.perf_counter()
-    step()
-    fence()
-    t_probe = time.perf_counter() - t0
-    R = args.repeats if args.repeats > 0 else max(5, min(25, int(2.0 / max(args.steps * t_probe, 1e-4)) + 1))
-    if group is not None:                       # (one R for every rank)
-        R = int(group.gather_scalars([float(R)]).max(0).values[0])
-    elif dist is not None:
-        vt = torch.tensor([float(R)], dtype=torch.float64, device="cuda")
-        dist.all_reduce(vt, op=dist.ReduceOp.MAX)
-        R = int(vt[0])
+    R = 1
+    if args.full:
+        step()
+        fence()
+        t0 = time.perf_counter()
+        step()
+        fence()
+        t_probe = time.perf_counter() - t0
+        R = args.repeats if args.repeats > 0 else max(5, min(25, int(2.0 / max(args.steps * t_probe, 1e-4)) + 1))
+        if group is not None:                       # (one R for every rank)
+            R = int(group.gather_scalars([float(R)]).max(0).values[0])
+        elif dist is not None:
+            vt = torch.tensor([float(R)], dtype=torch.float64, device="cuda")
+            dist.all_reduce(vt, op=dist.ReduceOp.MAX)
+            R = int(vt[0])
     regions, issues = [], []
     for _ in range(R):
         with guard("timed region of %d steps" % args.steps):
@@ -479,30 +499,38 @@ def main():
             issues.append(time.perf_counter() - t0)  # host time to enqueue K steps (launch-bound check)
             fence()
             regions.append(time.perf_counter() - t0)
+    # what the last timed step handed its caller ([gradient bucket, accuracy, loss]) and the parameters its Adam update left
+    outputs = None
+    if args.dump_outputs and rank == 0:
+        outputs = {"grad": res[0], "accuracy": res[1], "loss": res[2], "params": dgcnn.ctx().flat_param}
+        outputs = {n: v.detach().float().cpu().numpy() for n, v in outputs.items()}
+    loss = float(res[2])
     tail_guard = guard("post-region measurements (event-timed eager steps, exposed all-reduce, gathers over the ranks)", 2.0)
     tail_guard.__enter__()
-    # ---- the dominant kernel, live: HIP events (on the launch stream) around its launches in eager steps that follow the
-    # timed regions immediately (same process, same buffers, same two-stream schedule) ----
-    tv.use_graph(False)
-    H.TIMER = H.Timer(watch={dominant})
-    for _ in range(max(args.steps // 4, 3)):
-        step()
-    dom = H.TIMER.summary()[dominant]
-    H.TIMER = None
-    # ---- the collective, live: event pairs around the part of the all-reduce the step's stream has to WAIT for (the head bucket
-    # travels under the EdgeConv backward; what is left is the exposed cost) -- in the launch mode of the timed regions ----
-    tv.use_graph(launch_mode)
-    tv._ar_events = []
-    for _ in range(max(args.steps // 4, 3)):
-        step()
-    torch.cuda.synchronize()
-    exposed_ms = sorted(a.elapsed_time(b) for a, b in tv._ar_events)
-    tv._ar_events = None
-    loss = float(res[2])
+    dom, exposed_ms = None, []
+    if args.full:
+        # ---- the dominant kernel, live: HIP events (on the launch stream) around its launches in eager steps that follow the
+        # timed regions immediately (same process, same buffers, same two-stream schedule) ----
+        tv.use_graph(False)
+        H.TIMER = H.Timer(watch={dominant})
+        for _ in range(max(args.steps // 4, 3)):
+            step()
+        dom = H.TIMER.summary()[dominant]
+        H.TIMER = None
+        # ---- the collective, live: event pairs around the part of the all-reduce the step's stream has to WAIT for (the head bucket
+        # travels under the EdgeConv backward; what is left is the exposed cost) -- in the launch mode of the timed regions ----
+        tv.use_graph(launch_mode)
+        tv._ar_events = []
+        for _ in range(max(args.steps // 4, 3)):
+            step()
+        torch.cuda.synchronize()
+        exposed_ms = sorted(a.elapsed_time(b) for a, b in tv._ar_events)
+        tv._ar_events = None
     plan_info = tv.launch_plan_info()
 
     # replicas must hold identical parameters after identical Adam steps on the all-reduced gradient
-    chk = torch.stack([dgcnn.ctx().flat_param.double().sum(), dgcnn.ctx().flat_param.double().abs().sum()])
+    if world > 1:
+        chk = torch.stack([dgcnn.ctx().flat_param.double().sum(), dgcnn.ctx().flat_param.double().abs().sum()])
     per_rank_regions = [regions]
     if group is not None:
         allv = group.gather_scalars(regions + [float(x) for x in chk.float()])      # (world, R + 2)
@@ -531,115 +559,117 @@ def main():
     arith_name = {0: "native fp32 MFMA", 6: "exact 3-way bf16 split, 6 partial products on the bf16 MFMA pipe",
                   9: "exact 3-way bf16 split, 9 partial products on the bf16 MFMA pipe"}[H.gemm_arith()]
     if rank == 0:
-        is_gemm = dominant.startswith("gemm") or dominant.startswith("knn")
-        launches, secs, work = dom[:3]
-        if is_gemm:
-            achieved = work / secs / 1e12          # algorithmic fp32 flops (2 M N K per GEMM)
-            peak, note = PEAK_F32_MFMA_TFLOPS, "fp32 MFMA dense peak"
-            if dominant.startswith("gemm_x3"):      # gemm_x3_kernel / gemm_x3w2_kernel
-                # fp32 GEMM computed as NP exact bf16 partial products on the bf16 matrix pipe (gemm_x3.hip):
-                # the ceiling for ALGORITHMIC fp32 flops is the bf16 dense peak / NP
-                nprod = int(dominant.rstrip(">").split("bf16x")[1])
-                peak = round(PEAK_BF16_MFMA_TFLOPS / nprod, 1)
-                note = "bf16 MFMA dense peak %.0f / %d partial products per fp32 product" % (PEAK_BF16_MFMA_TFLOPS, nprod)
-            elif dominant.startswith("gemm_pl"):    # plane GEMM (gemm_pl.hip): 3 bf16 planes -> 6 products, 2 fp16 planes -> 3
-                nprod = 3 if "f16x2" in dominant else 6
-                peak = round(PEAK_BF16_MFMA_TFLOPS / nprod, 1)
-                note = ("16-bit MFMA dense peak %.0f (bf16 = fp16 rate) / %d partial products per fp32 product"
-                        % (PEAK_BF16_MFMA_TFLOPS, nprod))
-            roof = {"kernel": dominant, "bound": "mfma" if dominant.startswith("gemm") else "valu",
-                    "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
-                    "frac": round(achieved / peak, 4), "traffic": None,
-                    "launches": launches, "avg_us": round(secs / launches * 1e6, 1), "peak_note": note}
-        else:
-            achieved = work / secs / 1e9
-            roof = {"kernel": dominant, "bound": "hbm", "achieved": round(achieved, 1), "peak": PEAK_HBM_GBS,
-                    "unit": "GB/s", "frac": round(achieved / PEAK_HBM_GBS, 4), "traffic": None,
-                    "launches": launches, "avg_us": round(secs / launches * 1e6, 1)}
-        if side and is_gemm:
-            n1, s1, w1 = table[dominant][:3]
-            roof["achieved_serialized"] = round(w1 / s1 / 1e12, 2)
-            roof["frac_serialized"] = round(w1 / s1 / 1e12 / roof["peak"], 4)
-            roof["note"] = ("achieved/frac: HIP events around every launch of this kernel in eager steps right after the timed "
-                            "region, where weight-gradient GEMMs run concurrently on a second stream and stretch it; "
-                            "*_serialized: the same kernel timed in a warm-up step with the side stream off")
-        pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(pmc):
-            try:
-                roof["traffic"] = json.load(open(pmc)).get(dominant)
-            except Exception:
-                pass
-        # north_star: "rocprof HBM GB/s on the distance/gather kernels and MFMA utilisation on the edge MLP": the other kernel
-        # families of the step, each timed ALONE (the serialised warm-up step above), against the ceiling that bounds it
-        extra = []
-        for t, (n, sec, work, nbytes) in sorted(table.items(), key=lambda kv: -kv[1][1]):
-            if t == dominant or sec <= 0:
-                continue
-            if t.startswith("knn"):
-                # a k-NN CALL (dgcnn_knn_f32 / dgcnn_knn_seeded_f32) is several kernels; the tag lists them and names the pipe the
-                # 2 B N^2 C distance flops run on: the raw-coordinate kernel forms them on the fp32 VALU, the list-keeping feature kernel
-                # on the fp32 MFMA, the append-form scan as a conservative bf16-MFMA filter with an exact fp32 re-check of the survivors
-                c_in = int(t.split("<C")[1].split(",")[0])
-                if "knn_bf16a_kernel" in t:
-                    pipe, pk = "bf16 MFMA filter (+ exact fp32 VALU re-check of the survivors); staging / barrier bound", PEAK_BF16_MFMA_TFLOPS
-                elif c_in <= 4:
-                    pipe, pk = "fp32 VALU (distances and sorted inserts share the vector pipe)", PEAK_F32_MFMA_TFLOPS
-                else:
-                    pipe, pk = "fp32 MFMA (blocks VALU issue: shares the vector pipe with the selection)", PEAK_F32_MFMA_TFLOPS
-                extra.append({"kernel": t, "bound": pipe,
-                              "achieved": round(work / sec / 1e12, 2), "peak": pk, "unit": "TFLOP/s",
-                              "frac": round(work / sec / 1e12 / pk, 4), "launches": n,
-                              "avg_us": round(sec / n * 1e6, 1),
-                              "materialised_equiv_GBs": round(n * 2.0 * B * N * N * 4 / sec / 1e9, 1),
-                              "note": "one CALL = the kernels in the tag; flops = 2 B N^2 C (C = %d padded); materialised_equiv = the "
-                                      "2 B N^2 4-byte write+read of the reference's (B,N,N) distance tensor that never touches HBM here" % c_in})
-            elif t.startswith("gemm"):
-                pk = PEAK_F32_MFMA_TFLOPS
-                if "bf16x" in t:
-                    pk = PEAK_BF16_MFMA_TFLOPS / int(t.rstrip(">").split("bf16x")[1])
-                if t.startswith("gemm_pl"):
-                    pk = PEAK_BF16_MFMA_TFLOPS / (3 if "f16x2" in t else 6)
-                # which roof: flops per compulsory byte against the ridge of this arithmetic (peak flops / HBM peak)
-                if nbytes > 0 and work / nbytes < pk * 1e12 / (PEAK_HBM_GBS * 1e9):
-                    extra.append({"kernel": t, "bound": "hbm", "achieved": round(nbytes / sec / 1e9, 1), "peak": PEAK_HBM_GBS,
-                                  "unit": "GB/s", "frac": round(nbytes / sec / 1e9 / PEAK_HBM_GBS, 4), "launches": n,
-                                  "avg_us": round(sec / n * 1e6, 1), "mfma_frac": round(work / sec / 1e12 / pk, 4),
-                                  "note": "short reduction: %.0f flops per operand/result byte, below the ridge of %.0f" % (
-                                      work / nbytes, pk * 1e12 / (PEAK_HBM_GBS * 1e9))})
-                else:
-                    extra.append({"kernel": t, "bound": "mfma", "achieved": round(work / sec / 1e12, 2), "peak": round(pk, 1),
-                                  "unit": "TFLOP/s", "frac": round(work / sec / 1e12 / pk, 4), "launches": n,
+        roof = extra = None
+        if args.full:
+            is_gemm = dominant.startswith("gemm") or dominant.startswith("knn")
+            launches, secs, work = dom[:3]
+            if is_gemm:
+                achieved = work / secs / 1e12          # algorithmic fp32 flops (2 M N K per GEMM)
+                peak, note = PEAK_F32_MFMA_TFLOPS, "fp32 MFMA dense peak"
+                if dominant.startswith("gemm_x3"):      # gemm_x3_kernel / gemm_x3w2_kernel
+                    # fp32 GEMM computed as NP exact bf16 partial products on the bf16 matrix pipe (gemm_x3.hip):
+                    # the ceiling for ALGORITHMIC fp32 flops is the bf16 dense peak / NP
+                    nprod = int(dominant.rstrip(">").split("bf16x")[1])
+                    peak = round(PEAK_BF16_MFMA_TFLOPS / nprod, 1)
+                    note = "bf16 MFMA dense peak %.0f / %d partial products per fp32 product" % (PEAK_BF16_MFMA_TFLOPS, nprod)
+                elif dominant.startswith("gemm_pl"):    # plane GEMM (gemm_pl.hip): 3 bf16 planes -> 6 products, 2 fp16 planes -> 3
+                    nprod = 3 if "f16x2" in dominant else 6
+                    peak = round(PEAK_BF16_MFMA_TFLOPS / nprod, 1)
+                    note = ("16-bit MFMA dense peak %.0f (bf16 = fp16 rate) / %d partial products per fp32 product"
+                            % (PEAK_BF16_MFMA_TFLOPS, nprod))
+                roof = {"kernel": dominant, "bound": "mfma" if dominant.startswith("gemm") else "valu",
+                        "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
+                        "frac": round(achieved / peak, 4), "traffic": None,
+                        "launches": launches, "avg_us": round(secs / launches * 1e6, 1), "peak_note": note}
+            else:
+                achieved = work / secs / 1e9
+                roof = {"kernel": dominant, "bound": "hbm", "achieved": round(achieved, 1), "peak": PEAK_HBM_GBS,
+                        "unit": "GB/s", "frac": round(achieved / PEAK_HBM_GBS, 4), "traffic": None,
+                        "launches": launches, "avg_us": round(secs / launches * 1e6, 1)}
+            if side and is_gemm:
+                n1, s1, w1 = table[dominant][:3]
+                roof["achieved_serialized"] = round(w1 / s1 / 1e12, 2)
+                roof["frac_serialized"] = round(w1 / s1 / 1e12 / roof["peak"], 4)
+                roof["note"] = ("achieved/frac: HIP events around every launch of this kernel in eager steps right after the timed "
+                                "region, where weight-gradient GEMMs run concurrently on a second stream and stretch it; "
+                                "*_serialized: the same kernel timed in a warm-up step with the side stream off")
+            pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+            if os.path.exists(pmc):
+                try:
+                    roof["traffic"] = json.load(open(pmc)).get(dominant)
+                except Exception:
+                    pass
+            # north_star: "rocprof HBM GB/s on the distance/gather kernels and MFMA utilisation on the edge MLP": the other kernel
+            # families of the step, each timed ALONE (the serialised warm-up step above), against the ceiling that bounds it
+            extra = []
+            for t, (n, sec, work, nbytes) in sorted(table.items(), key=lambda kv: -kv[1][1]):
+                if t == dominant or sec <= 0:
+                    continue
+                if t.startswith("knn"):
+                    # a k-NN CALL (dgcnn_knn_f32 / dgcnn_knn_seeded_f32) is several kernels; the tag lists them and names the pipe the
+                    # 2 B N^2 C distance flops run on: the raw-coordinate kernel forms them on the fp32 VALU, the list-keeping feature kernel
+                    # on the fp32 MFMA, the append-form scan as a conservative bf16-MFMA filter with an exact fp32 re-check of the survivors
+                    c_in = int(t.split("<C")[1].split(",")[0])
+                    if "knn_bf16a_kernel" in t:
+                        pipe, pk = "bf16 MFMA filter (+ exact fp32 VALU re-check of the survivors); staging / barrier bound", PEAK_BF16_MFMA_TFLOPS
+                    elif c_in <= 4:
+                        pipe, pk = "fp32 VALU (distances and sorted inserts share the vector pipe)", PEAK_F32_MFMA_TFLOPS
+                    else:
+                        pipe, pk = "fp32 MFMA (blocks VALU issue: shares the vector pipe with the selection)", PEAK_F32_MFMA_TFLOPS
+                    extra.append({"kernel": t, "bound": pipe,
+                                  "achieved": round(work / sec / 1e12, 2), "peak": pk, "unit": "TFLOP/s",
+                                  "frac": round(work / sec / 1e12 / pk, 4), "launches": n,
+                                  "avg_us": round(sec / n * 1e6, 1),
+                                  "materialised_equiv_GBs": round(n * 2.0 * B * N * N * 4 / sec / 1e9, 1),
+                                  "note": "one CALL = the kernels in the tag; flops = 2 B N^2 C (C = %d padded); materialised_equiv = the "
+                                          "2 B N^2 4-byte write+read of the reference's (B,N,N) distance tensor that never touches HBM here" % c_in})
+                elif t.startswith("gemm"):
+                    pk = PEAK_F32_MFMA_TFLOPS
+                    if "bf16x" in t:
+                        pk = PEAK_BF16_MFMA_TFLOPS / int(t.rstrip(">").split("bf16x")[1])
+                    if t.startswith("gemm_pl"):
+                        pk = PEAK_BF16_MFMA_TFLOPS / (3 if "f16x2" in t else 6)
+                    # which roof: flops per compulsory byte against the ridge of this arithmetic (peak flops / HBM peak)
+                    if nbytes > 0 and work / nbytes < pk * 1e12 / (PEAK_HBM_GBS * 1e9):
+                        extra.append({"kernel": t, "bound": "hbm", "achieved": round(nbytes / sec / 1e9, 1), "peak": PEAK_HBM_GBS,
+                                      "unit": "GB/s", "frac": round(nbytes / sec / 1e9 / PEAK_HBM_GBS, 4), "launches": n,
+                                      "avg_us": round(sec / n * 1e6, 1), "mfma_frac": round(work / sec / 1e12 / pk, 4),
+                                      "note": "short reduction: %.0f flops per operand/result byte, below the ridge of %.0f" % (
+                                          work / nbytes, pk * 1e12 / (PEAK_HBM_GBS * 1e9))})
+                    else:
+                        extra.append({"kernel": t, "bound": "mfma", "achieved": round(work / sec / 1e12, 2), "peak": round(pk, 1),
+                                      "unit": "TFLOP/s", "frac": round(work / sec / 1e12 / pk, 4), "launches": n,
+                                      "avg_us": round(sec / n * 1e6, 1)})
+                elif nbytes > 0:
+                    # passes that re-form y = V[neighbour] + U[point] per edge instead of streaming a materialised (B N k, F) tensor: the
+                    # bytes that move are rows GATHERED from the point-level [U | V] buffer (25-50 MB: resident in the XCDs' L2s), so the
+                    # roof is the L2 -> CU bandwidth, not HBM; `hbm_GBs` is what the pass moves through HBM (outputs, indices)
+                    extra.append({"kernel": t, "bound": "l2-gather", "achieved": round(nbytes / sec / 1e9, 1), "peak": PEAK_L2_GBS,
+                                  "unit": "GB/s", "frac": round(nbytes / sec / 1e9 / PEAK_L2_GBS, 4), "launches": n,
+                                  "avg_us": round(sec / n * 1e6, 1), "hbm_GBs": round(work / sec / 1e9, 1),
+                                  "note": "gathered bytes = 4 (R k F + R F) per launch (one F-float row of V per edge + U once per point)"})
+                elif work > 0:
+                    extra.append({"kernel": t, "bound": "hbm", "achieved": round(work / sec / 1e9, 1), "peak": PEAK_HBM_GBS,
+                                  "unit": "GB/s", "frac": round(work / sec / 1e9 / PEAK_HBM_GBS, 4), "launches": n,
                                   "avg_us": round(sec / n * 1e6, 1)})
-            elif nbytes > 0:
-                # passes that re-form y = V[neighbour] + U[point] per edge instead of streaming a materialised (B N k, F) tensor: the
-                # bytes that move are rows GATHERED from the point-level [U | V] buffer (25-50 MB: resident in the XCDs' L2s), so the
-                # roof is the L2 -> CU bandwidth, not HBM; `hbm_GBs` is what the pass moves through HBM (outputs, indices)
-                extra.append({"kernel": t, "bound": "l2-gather", "achieved": round(nbytes / sec / 1e9, 1), "peak": PEAK_L2_GBS,
-                              "unit": "GB/s", "frac": round(nbytes / sec / 1e9 / PEAK_L2_GBS, 4), "launches": n,
-                              "avg_us": round(sec / n * 1e6, 1), "hbm_GBs": round(work / sec / 1e9, 1),
-                              "note": "gathered bytes = 4 (R k F + R F) per launch (one F-float row of V per edge + U once per point)"})
-            elif work > 0:
-                extra.append({"kernel": t, "bound": "hbm", "achieved": round(work / sec / 1e9, 1), "peak": PEAK_HBM_GBS,
-                              "unit": "GB/s", "frac": round(work / sec / 1e9 / PEAK_HBM_GBS, 4), "launches": n,
-                              "avg_us": round(sec / n * 1e6, 1)})
-        # the step as a whole: executed fp32-equivalent flops (GEMMs 2 M N K as launched -- the fold and the FC0 global-feature split
-        # already taken out -- plus the k-NN distance products) and algorithmic HBM bytes (every tagged launch's compulsory operand +
-        # result bytes) per step, over the MEDIAN region's ms_per_step, against both peaks
-        st_flops = sum(v[2] for t, v in table.items() if t.startswith("gemm") or t.startswith("knn"))
-        st_bytes = sum((v[3] if t.startswith("gemm") else (v[2] if not t.startswith("knn") else 0.0)) for t, v in table.items())
-        st_ms = elapsed / args.steps * 1e3
-        roof["step"] = {"executed_GFLOP": round(st_flops / 1e9, 1), "TFLOP/s": round(st_flops / st_ms / 1e9, 1),
-                        "frac_of_mfma_peak": round(st_flops / st_ms / 1e9 / (PEAK_BF16_MFMA_TFLOPS / 6), 4),
-                        "mfma_peak": round(PEAK_BF16_MFMA_TFLOPS / 6, 1),
-                        "hbm_GB": round(st_bytes / 1e9, 2), "GB/s": round(st_bytes / st_ms / 1e6, 1),
-                        "frac_of_hbm_peak": round(st_bytes / st_ms / 1e6 / PEAK_HBM_GBS, 4),
-                        "kernel_ms_serialised": round(sum(v[1] for v in table.values()) * 1e3, 3), "ms_per_step": round(st_ms, 3),
-                        "note": "sums over the tagged launches of one step (event-timed with the side stream off): fp32-equivalent "
-                                "flops of the GEMMs and k-NN products as executed, compulsory operand/result bytes of every launch"}
-        if args.kernel_table:
-            tot = sum(v[1] for v in table.values())
-            for t, (n, s, w, _b) in sorted(table.items(), key=lambda kv: -kv[1][1]):
-                sys.stderr.write("%-46s launches %3d  %8.3f ms  %5.1f%%  work/s %.3e\n" % (t, n, s * 1e3, 100 * s / tot, w / s))
+            # the step as a whole: executed fp32-equivalent flops (GEMMs 2 M N K as launched -- the fold and the FC0 global-feature split
+            # already taken out -- plus the k-NN distance products) and algorithmic HBM bytes (every tagged launch's compulsory operand +
+            # result bytes) per step, over the MEDIAN region's ms_per_step, against both peaks
+            st_flops = sum(v[2] for t, v in table.items() if t.startswith("gemm") or t.startswith("knn"))
+            st_bytes = sum((v[3] if t.startswith("gemm") else (v[2] if not t.startswith("knn") else 0.0)) for t, v in table.items())
+            st_ms = elapsed / args.steps * 1e3
+            roof["step"] = {"executed_GFLOP": round(st_flops / 1e9, 1), "TFLOP/s": round(st_flops / st_ms / 1e9, 1),
+                            "frac_of_mfma_peak": round(st_flops / st_ms / 1e9 / (PEAK_BF16_MFMA_TFLOPS / 6), 4),
+                            "mfma_peak": round(PEAK_BF16_MFMA_TFLOPS / 6, 1),
+                            "hbm_GB": round(st_bytes / 1e9, 2), "GB/s": round(st_bytes / st_ms / 1e6, 1),
+                            "frac_of_hbm_peak": round(st_bytes / st_ms / 1e6 / PEAK_HBM_GBS, 4),
+                            "kernel_ms_serialised": round(sum(v[1] for v in table.values()) * 1e3, 3), "ms_per_step": round(st_ms, 3),
+                            "note": "sums over the tagged launches of one step (event-timed with the side stream off): fp32-equivalent "
+                                    "flops of the GEMMs and k-NN products as executed, compulsory operand/result bytes of every launch"}
+            if args.kernel_table:
+                tot = sum(v[1] for v in table.values())
+                for t, (n, s, w, _b) in sorted(table.items(), key=lambda kv: -kv[1][1]):
+                    sys.stderr.write("%-46s launches %3d  %8.3f ms  %5.1f%%  work/s %.3e\n" % (t, n, s * 1e3, 100 * s / tot, w / s))
         out = {
             "metric": METRIC,
             "value": round(world * B * args.steps / elapsed, 2),
@@ -665,23 +695,30 @@ def main():
                        "deterministic": not args.atomics,
                        "repeats": R, "per_repeat_ms_per_step": [round(t / args.steps * 1e3, 3) for t in region_max],
                        "repeat_spread": round((max(region_max) - min(region_max)) / elapsed, 4),
-                       "timing": "the K-step region (fence = device synchronize + barrier on both sides) is run `repeats` times "
-                                 "back to back; ms_per_step / value are those of the MEDIAN region (max over ranks per region)",
+                       "timing": ("the K-step region (fence = device synchronize + barrier on both sides) is run `repeats` times "
+                                  "back to back; ms_per_step / value are those of the MEDIAN region (max over ranks per region)"
+                                  if args.full else "one K-step region, fence = device synchronize + barrier on both sides; "
+                                  "ms_per_step / value are those of the slowest rank"),
                        "launches_per_step": (dict(plan_info[0], outside_plan="zero-gradient memset, dropout-seed fill, softmax / "
                                                   "[loss, accuracy] copies, (all-reduce rest piece + scale), Adam")
                                              if plan_info else None)},
-            "roofline": roof,
-            "roofline_extra": extra[:14],
         }
-        if world == 1:
+        if args.full:
+            out["roofline"] = roof
+            out["roofline_extra"] = extra[:14]
+        if args.full and world == 1:
             probe = one_rank_rccl_probe(dgcnn.ctx().flat_grad.numel())
             out["config"]["rccl_probe"] = probe
             if probe and "nranks" in probe:
                 out["config"].update(rccl_ranks=probe["nranks"], rccl_rank=probe["rank"], rccl_ranks_source=probe["source"])
-        if world == 1 and not args.no_edgeconv_stack:
+        if args.full and world == 1 and not args.no_edgeconv_stack:
             out["edgeconv_stack"] = edgeconv_stack_rate(dgcnn, pts)     # after the timed region; resets the engine context
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
+        if outputs is not None:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in outputs.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
         print(json.dumps(out))
     if group is not None:
         parallel.shutdown_rccl()

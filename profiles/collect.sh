@@ -7,9 +7,10 @@ TAG=${1:-r05}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
+R=$PWD
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 cd /tmp && export TMPDIR=/tmp
-B="python $GRAFT_REPO_ROOT/bench.py --repeats 1 --no-cpu-baseline"
+B="python $R/bench.py --full --repeats 1 --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $B --steps 8 --warmup 2 > $OUT/trace.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_eager -- $B --steps 8 --warmup 2 --graph 0 > $OUT/trace_eager.log 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- $B --steps 2 --warmup 2 --graph 0 > $OUT/pmc_fetch.log 2>&1

@@ -10,7 +10,7 @@ OUT=gpurun_out/side_stream_ab.txt
 : > $OUT
 run() {  # name, env...
   local name=$1; shift
-  local ms=$(env "$@" python bench.py --no-cpu-baseline --no-edgeconv-stack --graph plan --repeats 9 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], min(d['config']['per_repeat_ms_per_step']))")
+  local ms=$(env "$@" python bench.py --full --no-cpu-baseline --no-edgeconv-stack --graph plan --repeats 9 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], min(d['config']['per_repeat_ms_per_step']))")
   echo "$name $ms" | tee -a $OUT
 }
 for rep in 1 2; do

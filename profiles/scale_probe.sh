@@ -24,7 +24,7 @@ BASE=""
 for N in 1 $LIST; do
   if [ "$N" -gt "$NGPU" ] && [ -z "${SCALE_PROBE_NGPU:-}" ]; then echo "N=$N: skipped (only $NGPU GPU(s) here)"; continue; fi
   J=$OUT/n$N.json; E=$OUT/n$N.err
-  timeout ${SCALE_PROBE_TIMEOUT:-900} $PY bench.py --gpus $N --steps ${SCALE_PROBE_STEPS:-20} --warmup 5 --no-cpu-baseline --no-edgeconv-stack ${SCALE_PROBE_BENCH_ARGS:-} > $J 2> $E
+  timeout ${SCALE_PROBE_TIMEOUT:-900} $PY bench.py --gpus $N --steps ${SCALE_PROBE_STEPS:-20} --warmup 5 --full --no-cpu-baseline --no-edgeconv-stack ${SCALE_PROBE_BENCH_ARGS:-} > $J 2> $E
   RC=$?
   $PY - "$N" "$J" "$E" "$RC" "$BASE" <<'PY'
 import json, re, sys

@@ -12,7 +12,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_prints_one_json_line_with_the_contract_keys():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--no-cpu-baseline"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--no-cpu-baseline",
+                        "--full"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-2000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.strip()]
@@ -50,7 +51,7 @@ def test_bench_gpus_2_from_a_bare_shell_launches_two_ranks_itself():
     contract of the N > 1 line and that the replica-checksum guard ran (the run would exit non-zero on diverged replicas)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--same-device", "--backend", "gloo",
-                        "--steps", "3", "--warmup", "2", "--no-cpu-baseline"],
+                        "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--full"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.strip().startswith("{")]
@@ -71,7 +72,7 @@ def test_bench_default_mode_gives_a_reproducible_line(graph):
     outs = []
     for _ in range(2):
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--no-cpu-baseline",
-                            "--no-edgeconv-stack", "--graph", graph, "--repeats", "5"],
+                            "--no-edgeconv-stack", "--graph", graph, "--repeats", "5", "--full"],
                            stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, cwd=ROOT)
         assert p.returncode == 0, p.stderr.decode(errors="replace")[-2000:]
         d = json.loads([l for l in p.stdout.decode().splitlines() if l.strip().startswith("{")][0])
@@ -84,8 +85,45 @@ def test_bench_default_mode_gives_a_reproducible_line(graph):
 
 def test_bench_atomics_mode_is_reachable():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--no-cpu-baseline",
-                        "--no-edgeconv-stack", "--atomics", "--repeats", "5"],
+                        "--no-edgeconv-stack", "--atomics", "--repeats", "5", "--full"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-2000:]
     d = json.loads([l for l in p.stdout.decode().splitlines() if l.strip().startswith("{")][0])
     assert d["config"]["deterministic"] is False
+
+
+def test_a_plain_run_times_exactly_k_steps_and_dumps_reproducible_outputs(tmp_path):
+    """Without --full the line is the headline alone: ONE region of exactly --steps steps, none of the --full objects.
+    --dump-outputs writes what the last timed step returned plus the parameters it left, float32; two runs of the same
+    command (seeded inputs and weights, deterministic mode) write the same gradient and parameters bit for bit, and the same
+    loss and accuracy to rounding."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        out = tmp_path / ("run%d" % i)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
+                            "--graph", "plan", "--dump-outputs", str(out)],
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, cwd=ROOT)
+        assert p.returncode == 0, p.stderr.decode(errors="replace")[-2000:]
+        lines = [l for l in p.stdout.decode().splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        d = json.loads(lines[0])
+        for key, typ in (("metric", str), ("value", float), ("unit", str), ("ms_per_step", float), ("higher_is_better", bool),
+                         ("dtype", str)):
+            assert isinstance(d[key], typ), (key, d[key])
+        assert d["steps"] == 4 and d["unit"] == "clouds/s" and d["dtype"] == "f32" and d["higher_is_better"] is True
+        assert d["config"]["repeats"] == 1 and len(d["config"]["per_repeat_ms_per_step"]) == 1
+        assert abs(d["value"] - 24 * 1e3 / d["ms_per_step"]) / d["value"] < 1e-3
+        for key in ("roofline", "roofline_extra", "edgeconv_stack", "cpu_baseline"):
+            assert key not in d, key
+        arrs = {f.name[:-4]: np.load(f) for f in sorted(out.glob("*.npy"))}
+        assert sorted(arrs) == ["accuracy", "grad", "loss", "params"], sorted(arrs)
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+        assert arrs["grad"].shape == arrs["params"].shape
+        assert abs(float(arrs["loss"]) - d["config"]["final_loss"]) <= 1e-5            # final_loss: the same step, 5 decimals
+        assert sum(a.nbytes for a in arrs.values()) < 64 << 20
+        dumps.append(arrs)
+    for name in ("grad", "params"):                                   # the deterministic kernels: bit for bit
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
+    for name in ("loss", "accuracy"):                                 # block partials atomically added in any order
+        assert np.allclose(dumps[0][name], dumps[1][name], rtol=1e-5, atol=0), name
