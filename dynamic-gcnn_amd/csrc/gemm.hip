@@ -688,6 +688,10 @@ int launch(GemmP& p, hipStream_t st, const char* what) {
   if (plain && vec && dg::gemm_arith() != 0) {          // bf16-split kernel (gemm_x3.hip)
     p.bm = dg::x3_tile_m(p.M, p.N, p.K);
     if (dg::x3_tile_n(p.M, p.N, p.K) == 256) bn = 256;
+    // the column-maximum epilogue keys a whole tile by the group of its first row, and a group is a multiple of 256 rows, not
+    // of 192: a 192-row tile can straddle two groups, so such a product takes the 256 x 256 tile instead (same per-element
+    // k order: bit-identical C)
+    if (p.colmax && p.colmax_rpg % p.bm != 0) p.bm = 256;
     p.mtiles = (int)dg::cdiv(p.M, p.bm);
     p.ntiles = (int)dg::cdiv(p.N, bn);
     p.xcd_group = (p.ntiles > 1 && p.mtiles >= 16 && p.splits == 1) ? 1 : 0;
@@ -814,7 +818,8 @@ extern "C" int dgcnn_gemm_f32(int transA, int transB, int M, int N, int K,
   p.stats = stats;
   p.splits = 1; p.kchunk = K;
   DG_REQUIRE(!colmax_keys || (colmax_rows_per_group > 0 && colmax_rows_per_group % 256 == 0 && !transA && N > 4), DGCNN_EUNSUP,
-             "dgcnn_gemm_f32: the column-maximum epilogue needs rows_per_group %% 256 == 0 (a tile inside one group), no transA, N > 4");
+             "dgcnn_gemm_f32: the column-maximum epilogue needs rows_per_group %% 256 == 0 (every row tile inside one group: "
+             "64, 128 or 256 rows; launch<> does not take the 192-row tile then), no transA, N > 4");
   p.colmax = reinterpret_cast<unsigned long long*>(colmax_keys); p.colmax_rpg = colmax_rows_per_group;
   p.gbvec = gbias && (ldgbias % 4 == 0) && aligned16(gbias);
   p.avec = (lda % 4 == 0) && aligned16(A);

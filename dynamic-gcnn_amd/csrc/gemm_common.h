@@ -36,7 +36,8 @@ struct GemmP {
   int zmajor;     // split-K launches of the bf16-split kernels: 1-D grid, XCD x (= block id % 8) owns the k-chunks z = x (mod 8)
   // per-group column maximum of the output (model.py:76-77 max-pool over the points of a cloud, taken in the epilogue of the GEMM
   // that produces the tensor): keys[group][N] <- atomicMax(order-preserving bits of the value << 32 | ~row-in-group), i.e. the
-  // largest value and, among ties, the FIRST row.  Needs rows_per_group % tile rows == 0 (checked by the host).
+  // largest value and, among ties, the FIRST row.  Needs rows_per_group % tile rows == 0: the host requires a multiple of 256 and
+  // gemm.hip:launch<> replaces the 192-row tile by the 256-row one when colmax is set.
   unsigned long long* colmax; int colmax_rpg;
   int stat_slots; // slots of p.stats (dg::stat_slots() at launch)
 };
@@ -240,7 +241,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, f32x16 (&acc)[TM][
           atomicAdd(p.stats + ((int64_t)slot * 2 + 1) * p.N + c, (double)s1);
         }
         if (want_max && mr != 0x7fffffff) {
-          const int grp = m0 / p.colmax_rpg;                  // the tile lies inside one group (host check)
+          const int grp = m0 / p.colmax_rpg;                  // the tile lies inside one group (host check + launch<>: no 192-row tile)
           const unsigned long long key = ((unsigned long long)f32_ordered(mx) << 32) |
                                          (unsigned long long)(0xffffffffu - (unsigned)(mr - grp * p.colmax_rpg));
           atomicMax(p.colmax + (int64_t)grp * p.N + c, key);

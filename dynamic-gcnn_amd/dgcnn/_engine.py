@@ -540,7 +540,7 @@ def _tile_m(M, N):
     return 128
 
 
-def _gemm_tag(M, N, K, transA, transB, A, Bm):
+def _gemm_tag(M, N, K, transA, transB, A, Bm, colmax_rpg=0):
     """Kernel identity of a dgcnn_gemm_f32 launch for bench.py's table (mirrors the C dispatch); None when nobody is timing."""
     if H.TIMER is None:
         return None
@@ -554,6 +554,8 @@ def _gemm_tag(M, N, K, transA, transB, A, Bm):
     if vec and arith:
         kinds = ("KSTRIDED" if transA else "KCONTIG", "KCONTIG" if transB else "KSTRIDED")
         rows = H.load().dgcnn_gemm_x3_tile_rows(M, N, K)
+        if colmax_rpg and colmax_rpg % rows:                      # gemm.hip:launch<>: no tile may straddle two groups
+            rows = 256
         if H.load().dgcnn_gemm_x3_tile_cols(M, N, K) == 256:     # dg::x3_tile_n: the 256-column unspecialised kernels
             return "gemm_x3q_kernel<%s,%s,%d,bf16x%d>" % (kinds + (rows, arith))
         if rows == 256:                                           # dg::x3_tile_m: the 256 x 128 wave-specialised kernel
@@ -578,7 +580,7 @@ def gemm(A, Bm, C, transA=False, transB=False, beta=0.0, gbias=None, rpg=0, stat
     Kb = Bm.shape[1] if transB else Bm.shape[0]
     assert K == Kb and tuple(C.shape) == (M, N), (A.shape, Bm.shape, C.shape, transA, transB)
     ws = ctx().workspace()
-    tag = _gemm_tag(M, N, K, transA, transB, A, Bm)
+    tag = _gemm_tag(M, N, K, transA, transB, A, Bm, colmax_rpg if colmax is not None else 0)
     H.call("dgcnn_gemm_f32", int(transA), int(transB), M, N, K, A.data_ptr(), H.ld2(A), Bm.data_ptr(), H.ld2(Bm),
            C.data_ptr(), H.ld2(C), float(beta), H._p(gbias), 0 if gbias is None else H.ld2(gbias), int(rpg),
            H._p(stats), H._p(colmax), int(colmax_rpg), ws.data_ptr(), ws.numel(), tag=tag, work=2.0 * M * N * K,
@@ -655,7 +657,8 @@ def conv_bn_act(x, leaf_scope, num_outputs, relu=True, out=None, out2=None, gbia
     use_pl = arith is None and planes_ok(R, Cin, F)
     xp = None
     # the per-cloud column maximum (model.py:76-77), when asked for, comes out of the GEMM's epilogue as packed (value, first row)
-    # keys -- a tile of 256 rows must lie inside one cloud; otherwise a separate pass over T below
+    # keys -- every row tile must lie inside one cloud: clouds of a multiple of 256 points (the library then runs no 192-row tile,
+    # gemm.hip:launch<>); otherwise a separate pass over T below
     keys = None
     if gmax is not None and gmax[1] % 256 == 0 and gmax[0] * gmax[1] == R and F > 4:
         keys = c.stats_raw(gmax[0] * F)                                    # zeroed uint64[B][F]

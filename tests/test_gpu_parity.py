@@ -1044,7 +1044,8 @@ def test_dropout_fused_into_the_last_fc_layer_equals_the_separate_passes(dg):
     assert 0.3 <= seen["frac0"] <= 0.9, seen          # 30 % dropped + the ReLU's own zeros
 
 
-@pytest.mark.parametrize("B,N,Cin,F", [(3, 512, 64, 128), (2, 1024, 192, 1024), (5, 256, 32, 96)])
+@pytest.mark.parametrize("B,N,Cin,F", [(3, 512, 64, 128), (2, 1024, 192, 1024), (5, 256, 32, 96),
+                                     (20, 512, 192, 1024)])       # (the cost rule picks the 192 x 256 tile there)
 def test_column_maximum_from_the_gemm_epilogue(dg, B, N, Cin, F):
     """model.py:76-77 (max_pool_v2 over the points of a cloud): the per-cloud column maximum and its FIRST row come out of the
     epilogue of the GEMM that produces the tensor (packed keys + dgcnn_colmax_decode_f32) -- against numpy, ties included."""
