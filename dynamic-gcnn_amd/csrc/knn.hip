@@ -24,6 +24,32 @@ constexpr int WAVES = 4;
 constexpr int TJ = 128;
 constexpr int PERW = TJ / WAVES;
 
+// Which rows of x a grid row (blockIdx.y = b) searches.  Dense: cloud b = rows [b N, b N + N), indices cloud-local.  Packed tower:
+// cloud b = rows [off[b], off[b + 1]), indices tower rows (off[b] + j), grid cdiv(max_n, 64) x nseg -- a block past its cloud's rows
+// leaves before its first barrier.  Within a cloud the arithmetic is the same: per cloud the packed result is the dense one.
+struct DenseClouds {
+  int N;
+  __host__ __device__ constexpr DenseClouds(int n) : N(n) {}
+  static constexpr bool kPacked = false;
+  __device__ int64_t base(int b) const { return (int64_t)b * N; }
+  __device__ int size(int) const { return N; }
+};
+struct PackedClouds {
+  const int* __restrict__ off;               // nseg + 1 increasing tower rows, off[0] = 0
+  int nseg;
+  static constexpr bool kPacked = true;
+  __device__ int64_t base(int b) const { return off[b]; }
+  __device__ int size(int b) const { return off[b + 1] - off[b]; }
+  __device__ int cloud_of(int64_t row) const {                 // last b with off[b] <= row (row wave-uniform: a scalar loop)
+    int lo = 0, hi = nseg;
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (off[mid] <= row) lo = mid; else hi = mid;
+    }
+    return lo;
+  }
+};
+
 // s_i = sequential sum of fl(x^2) over c ascending (the oracle's order: no FMA, no reassociation), one thread per row.
 // 64 rows per block (B*N/64 blocks: 768 at the headline shape -- the round-1 kernel ran 192 blocks of 256 rows, under one
 // block per CU, 24 us at C = 64): the block's rows are staged through LDS with coalesced loads (a thread walking its own
@@ -63,8 +89,8 @@ __global__ __launch_bounds__(256) void sqnorm_kernel(const float* __restrict__ x
 // a coarse bin (many equal distances) only makes the bound looser.  Per candidate: one LDS broadcast read, the 6-operation distance,
 // clamp, shift, one ds_add_u32 into the thread's own column of the histogram ([bin][thread]: bank = thread, conflict free).
 constexpr int HB_NB = 48;
-template <int STRIDE>
-__global__ __launch_bounds__(256) void knn_hist_bound_kernel(const float* __restrict__ x, const float* __restrict__ sq, int N, int C,
+template <int STRIDE, class Clouds = DenseClouds>
+__global__ __launch_bounds__(256) void knn_hist_bound_kernel(const float* __restrict__ x, const float* __restrict__ sq, Clouds cl, int C,
                                                              int64_t ldx, int k, float* __restrict__ tau0) {
   // 64 query rows per workgroup (lane = row); wave w counts quarter w of every 256-candidate tile into its own histogram
   // ([wave][bin][lane]: bank = lane), the four are added at the end -- 3072 waves at (24,2048) instead of 768: the per-candidate chain
@@ -78,9 +104,12 @@ __global__ __launch_bounds__(256) void knn_hist_bound_kernel(const float* __rest
   const int lane = tid & 63;
   const int w = tid >> 6;
   const int b = blockIdx.y;
+  const int N = cl.size(b);
+  if (Clouds::kPacked && (int)blockIdx.x * 64 >= N) return;
+  const int64_t cb = cl.base(b);
   const int row = blockIdx.x * 64 + lane;
-  const float* xb = x + (int64_t)b * N * ldx;
-  const float* sqb = sq + (int64_t)b * N;
+  const float* xb = x + cb * ldx;
+  const float* sqb = sq + cb;
   const int rowc = row < N ? row : N - 1;
   float xi[4];
 #pragma unroll
@@ -154,7 +183,7 @@ __global__ __launch_bounds__(256) void knn_hist_bound_kernel(const float* __rest
   float tau = INFINITY;
   const int eraw = bin0 + bsel + 1;
   if (bsel < HB_NB - 1 && eraw > 0 && eraw < 0x1FE) tau = __uint_as_float((unsigned)eraw << 22);
-  if (row < N) tau0[(int64_t)b * N + row] = tau;
+  if (row < N) tau0[cb + row] = tau;
 }
 
 // Shared selection bound.  The candidates of a query row are split over FOUR sorted lists (KC entries each, KC % 4 == 0).
@@ -170,9 +199,9 @@ constexpr int knn_min_waves() {
   return (CP + 2 * KC + 70 <= 128) ? 4 : ((CP + 2 * KC + 70 <= 168) ? 3 : ((CP + 2 * KC + 70 <= 256) ? 2 : 1));
 }
 
-template <int CP, int KC>
+template <int CP, int KC, class Clouds = DenseClouds>
 __global__ __launch_bounds__(256, (knn_min_waves<CP, KC>())) void knn_kernel(const float* __restrict__ x,
-                                                                            const float* __restrict__ sq, int N, int C,
+                                                                            const float* __restrict__ sq, Clouds cl, int C,
                                                                             int64_t ldx, int k, int vec_ok,
                                                                             int32_t* __restrict__ idx, const float* __restrict__ tau0) {
   constexpr int TILE_F = TJ * CP;
@@ -189,9 +218,12 @@ __global__ __launch_bounds__(256, (knn_min_waves<CP, KC>())) void knn_kernel(con
   const int lane = tid & 63;
   const int w = tid >> 6;
   const int b = blockIdx.y;
+  const int N = cl.size(b);
+  if (Clouds::kPacked && (int)blockIdx.x * ROWS >= N) return;
+  const int64_t cb = cl.base(b);
   const int row = blockIdx.x * ROWS + lane;
-  const float* xb = x + (int64_t)b * N * ldx;
-  const float* sqb = sq + (int64_t)b * N;
+  const float* xb = x + cb * ldx;
+  const float* sqb = sq + cb;
 
   const int rowc = row < N ? row : N - 1;
   float xi[CP];
@@ -199,7 +231,7 @@ __global__ __launch_bounds__(256, (knn_min_waves<CP, KC>())) void knn_kernel(con
   for (int c = 0; c < CP; ++c) xi[c] = (c < C) ? xb[(int64_t)rowc * ldx + c] : 0.0f;
   const float si = sqb[rowc];
   // a bound known in advance (knn_hist_bound_kernel: the row's k-th distance is < tau_row): candidates at or above it never enter
-  const float tau_row = tau0 ? tau0[(int64_t)b * N + rowc] : INFINITY;
+  const float tau_row = tau0 ? tau0[cb + rowc] : INFINITY;
 
   float dl[KC];
   int jl[KC];
@@ -307,10 +339,10 @@ __global__ __launch_bounds__(256, (knn_min_waves<CP, KC>())) void knn_kernel(con
     }
   }
   if (w == 0 && row < N) {
-    int32_t* out = idx + ((int64_t)b * N + row) * k;
+    int32_t* out = idx + (cb + row) * k;
 #pragma unroll
     for (int t = 0; t < KC; ++t)
-      if (t < k) out[t] = jl[t];
+      if (t < k) out[t] = Clouds::kPacked ? (int)cb + jl[t] : jl[t];
   }
 }
 
@@ -920,10 +952,10 @@ __device__ __forceinline__ unsigned long long wave_lowest64(const unsigned long 
 // exact products on top: |d' - d| <= 2^-7 t (1 + 2^-8); tested with 2^-6 t): a third of the MFMAs, a quarter of the staging
 // arithmetic, one plane in LDS -- for a wider margin, i.e. more pairs re-checked exactly.  The result is the same bit for bit (the
 // re-check decides).
-template <bool LX, int NPR = 3>
+template <bool LX, int NPR = 3, class Clouds = DenseClouds>
 // N >= 8192 with the one-product filter: 4 workgroups per CU (128 VGPRs; the re-check's candidate ring 8 -> 4 deep keeps it out of
 // scratch): (8,16384,64,40) 2048 workgroups = 2 rounds of 1024 instead of 2.67 of 768, 1.71 -> 1.54 ms (profiles/r06/knn_occ.txt)
-__global__ __launch_bounds__(256, ((LX || NPR != 1) ? 3 : 4)) void knn_bf16a_kernel(const float* __restrict__ x, const float* __restrict__ sq, int N, int C,
+__global__ __launch_bounds__(256, ((LX || NPR != 1) ? 3 : 4)) void knn_bf16a_kernel(const float* __restrict__ x, const float* __restrict__ sq, Clouds cl, int C,
                                                            int64_t ldx, int k, const float* __restrict__ tau0, int cap,
                                                            unsigned long long* __restrict__ ent, int* __restrict__ cnt,
                                                            int ka_tight_mask) {
@@ -960,16 +992,18 @@ __global__ __launch_bounds__(256, ((LX || NPR != 1) ? 3 : 4)) void knn_bf16a_ker
   const int qg = w & 1;
   const int cs = w >> 1;
   const int b = blockIdx.y;
+  const int N = cl.size(b);
+  if (Clouds::kPacked && (int)blockIdx.x * ROWS >= N) return;
   const int row0 = blockIdx.x * ROWS;
   const int row = row0 + qg * 32 + l31;
-  const float* xb = x + (int64_t)b * N * ldx;
-  const float* sqb = sq + (int64_t)b * N;
+  const float* xb = x + cl.base(b) * ldx;
+  const float* sqb = sq + cl.base(b);
   const int rowc = row < N ? row : N - 1;
   const int cbase = cs * 32;
   const int rslot = qg * 32 + l31;
   const float si = sqb[rowc];
   const float* xi_row = xb + (int64_t)rowc * ldx;
-  const int64_t grow0 = (int64_t)b * N + row0;                     // global row of the block's first query row
+  const int64_t grow0 = cl.base(b) + row0;                         // global row of the block's first query row
   const int trig = cap - (LX ? KA_SLACK_LX : KA_SLACK);
   volatile qent_t* myq = queue + w * QN;
   constexpr float C1 = (NPR == 3) ? KA_C1 : 0.5f * (1.0f - 1.0f / 64.0f);       // the filter's (1 - E') / 2
@@ -1002,7 +1036,7 @@ __global__ __launch_bounds__(256, ((LX || NPR != 1) ? 3 : 4)) void knn_bf16a_ker
   }
   if (tid < ROWS) {
     const int rr = (row0 + tid < N) ? row0 + tid : N - 1;
-    const float t0 = tau0[(int64_t)b * N + rr];
+    const float t0 = tau0[cl.base(b) + rr];
     thr_s[tid] = next_up(t0);
     cnt_s[tid] = 0;
     // levels T c_m, T = t0 truncated to its upper 16 bits (any positive T <= t0 serves; 16 bits fit beside a counter).  Rows
@@ -1098,7 +1132,7 @@ __global__ __launch_bounds__(256, ((LX || NPR != 1) ? 3 : 4)) void knn_bf16a_ker
     const float d = tt - tp;
     if (on && d < thr_s[rs]) {
       const int pos = atomicAdd(&cnt_s[rs], 1);                      // < cap by the invariant
-      ent[(grow0 + rs) * cap + pos] = knn_key(d, j);
+      ent[(grow0 + rs) * cap + pos] = knn_key(d, Clouds::kPacked ? (int)cl.base(b) + j : j);     // (one offset per row: same order)
       if (pos >= trig) flags[par] = 1;
       // level histogram: the finest level T c_m the candidate lies under (the row itself is left out: one count less can
       // never overflow a 16-bit counter at N <= 65536)
@@ -1276,8 +1310,10 @@ bool knn_force_valu() { return g_knn_valu == 1; }
 //     tau0 = max_m [ (s_i + s_j) - 2 p~ + 2^-16 (s_i + s_j) ]
 // an upper bound of the normative distances -- all the proof needs (k distinct candidates at distance <= tau0).
 // Seeds that are not k DISTINCT in-range indices give +inf (no bound).
-template <int LP, int MAXSTEPS>
-__global__ __launch_bounds__(256) void knn_seed_bound_kernel(const float* __restrict__ x, const float* __restrict__ sq, int N,
+// Packed towers: seeds are tower rows, and only rows of the query row's own cloud count (a row of a neighbouring cloud can be nearer
+// than every true candidate: its distance would be no bound).
+template <int LP, int MAXSTEPS, class Clouds = DenseClouds>
+__global__ __launch_bounds__(256) void knn_seed_bound_kernel(const float* __restrict__ x, const float* __restrict__ sq, Clouds cl,
                                                              int64_t ldx, const int32_t* __restrict__ seed, int64_t ldseed, int k,
                                                              int64_t rows, float* __restrict__ tau0) {
   constexpr int PPS = 64 / LP;                            // pairs per step
@@ -1290,7 +1326,7 @@ __global__ __launch_bounds__(256) void knn_seed_bound_kernel(const float* __rest
   if (g0 >= rows || ((int64_t)(blockIdx.x >> 3) * 4 + (threadIdx.x >> 6)) * RW >= per) return;       // (wave-uniform)
   const int slot = lane / LP, cq = lane % LP;
   const int steps = (k + PPS - 1) / PPS;
-  int jj[RW];
+  int jj[RW], nn[RW];
   int64_t gr[RW];
   const float* xc[RW];                                    // the row's cloud: x and s_i of its first point (wave-uniform)
   const float* sc[RW];
@@ -1298,9 +1334,19 @@ __global__ __launch_bounds__(256) void knn_seed_bound_kernel(const float* __rest
   for (int w = 0; w < RW; ++w) {
     gr[w] = (g0 + w < rows) ? g0 + w : rows - 1;
     jj[w] = (lane < k) ? seed[gr[w] * ldseed + lane] : -1 - lane;      // the row's seeds, one per lane
-    const int64_t cloud = (rows < 0x7fffffffll) ? (int64_t)((unsigned)gr[w] / (unsigned)N) : gr[w] / N;
-    xc[w] = x + cloud * N * ldx;
-    sc[w] = sq + cloud * N;
+    if constexpr (Clouds::kPacked) {
+      const int cloud = cl.cloud_of(gr[w]);
+      const int64_t cb = cl.base(cloud);
+      nn[w] = cl.size(cloud);
+      jj[w] -= (int)cb;                                                 // tower rows -> rows of the cloud (others: out of range)
+      xc[w] = x + cb * ldx;
+      sc[w] = sq + cb;
+    } else {
+      const int N = cl.N;
+      const int64_t cloud = (rows < 0x7fffffffll) ? (int64_t)((unsigned)gr[w] / (unsigned)N) : gr[w] / N;
+      xc[w] = x + cloud * N * ldx;
+      sc[w] = sq + cloud * N;
+    }
   }
   const unsigned uld = (unsigned)ldx;                     // (N * ldx < 2^31: checked by the host)
   float4 a[RW], v[RW][MAXSTEPS];
@@ -1314,7 +1360,9 @@ __global__ __launch_bounds__(256) void knn_seed_bound_kernel(const float* __rest
       if (s < steps) {                                    // (wave-uniform)
         const int m = s * PPS + slot;
         int jm = __shfl(jj[w], m < 64 ? m : 63, 64);
-        jm = (m < k && (unsigned)jm < (unsigned)N) ? jm : 0;
+        int lim;
+        if constexpr (Clouds::kPacked) lim = nn[w]; else lim = cl.N;
+        jm = (m < k && (unsigned)jm < (unsigned)lim) ? jm : 0;
         v[w][s] = *reinterpret_cast<const float4*>(xc[w] + ((unsigned)jm * uld + 4u * (unsigned)cq));
         sj[w][s] = sc[w][jm];
       }
@@ -1330,7 +1378,9 @@ __global__ __launch_bounds__(256) void knn_seed_bound_kernel(const float* __rest
     for (int t = 0; t < k; ++t) {
       const int st = __builtin_amdgcn_readlane(jj[w], t);
       const unsigned long long eq = __ballot(jj[w] == st) & kmask;
-      b = b || (__popcll(eq) != 1) || ((unsigned)st >= (unsigned)N);
+      int lim;
+      if constexpr (Clouds::kPacked) lim = nn[w]; else lim = cl.N;
+      b = b || (__popcll(eq) != 1) || ((unsigned)st >= (unsigned)lim);
     }
     anybad[w] = b;
   }
@@ -1356,12 +1406,12 @@ __global__ __launch_bounds__(256) void knn_seed_bound_kernel(const float* __rest
 }
 
 // C in {16, 32, 64} (LP = 4, 8, 16 lanes per pair), rows 16-byte aligned; k <= 64.  Returns false when the shape is not taken.
-bool launch_seed_bound(const float* x, const float* sq, int B, int N, int C, int64_t ldx, const int32_t* seed, int64_t ldseed,
-                       int k, float* tau0, hipStream_t st) {
-  const int64_t rows = (int64_t)B * N;
+template <class Clouds>
+bool launch_seed_bound(const float* x, const float* sq, int64_t rows, Clouds cl, int C, int64_t ldx, const int32_t* seed,
+                       int64_t ldseed, int k, float* tau0, hipStream_t st) {
   const int64_t per = dg::cdiv(dg::cdiv(rows, 8), 8) * 8;  // rows per XCD (blocks of 4 waves x 2 rows)
   const dim3 grid((unsigned)(per / 8 * 8));                // block id = 8 * (block within the XCD's share) + XCD
-#define DG_SB(LPV, MS) dg::launch((knn_seed_bound_kernel<LPV, MS>), grid, dim3(256), 0, st, x, sq, N, ldx, seed, ldseed, k, rows, tau0)
+#define DG_SB(LPV, MS) dg::launch((knn_seed_bound_kernel<LPV, MS, Clouds>), grid, dim3(256), 0, st, x, sq, cl, ldx, seed, ldseed, k, rows, tau0)
   if (C == 64) { if (k <= 20) DG_SB(16, 5); else if (k <= 40) DG_SB(16, 10); else DG_SB(16, 16); }
   else if (C == 32) { if (k <= 24) DG_SB(8, 3); else DG_SB(8, 8); }
   else if (C == 16) { if (k <= 32) DG_SB(4, 2); else DG_SB(4, 4); }
@@ -1389,6 +1439,21 @@ void launch_knn(const float* x, const float* sq, int B, int N, int C, int64_t ld
     }
   }
   dg::launch((knn_kernel<CP, KC>), grid, dim3(256), 0, st, x, sq, N, C, ldx, k, vec_ok, idx, (CP <= 4) ? tau0 : (const float*)nullptr);
+}
+
+// packed tower: the list-keeping VALU scan for every C (the bound tau0 only for C <= 4: knn_hist_bound_kernel)
+template <int CP>
+int dispatch_k_packed(const float* x, const float* sq, PackedClouds cl, int max_n, int C, int64_t ldx, int k, int vec_ok,
+                      int32_t* idx, const float* tau0, hipStream_t st) {
+  const dim3 grid((unsigned)dg::cdiv(max_n, ROWS), (unsigned)cl.nseg);
+  const float* t0 = (CP <= 4) ? tau0 : (const float*)nullptr;
+#define DG_KP(KCV) dg::launch((knn_kernel<CP, KCV, PackedClouds>), grid, dim3(256), 0, st, x, sq, cl, C, ldx, k, vec_ok, idx, t0)
+  if (k <= 8) DG_KP(8);
+  else if (k <= 20) DG_KP(20);
+  else if (k <= 40) DG_KP(40);
+  else DG_KP(64);
+#undef DG_KP
+  return dg::check_launch("dgcnn_knn_seg_f32");
 }
 
 template <int CP>
@@ -1431,9 +1496,15 @@ static int knn_append_cap(int k, int N) {    // entries per row buffer: >= k + s
   return k <= 20 ? 320 : (k <= 40 ? 448 : 512);
 }
 static bool knn_append_shape(int C, int k) { return C > 16 && C <= 64 && C % 4 == 0 && k <= 64; }
-static size_t knn_append_bytes(int B, int N, int k) {
-  const size_t rows = (size_t)B * (size_t)N;
-  return ((rows * sizeof(int) + 255) & ~(size_t)255) + rows * (size_t)knn_append_cap(k, N) * sizeof(unsigned long long);
+static size_t knn_append_rows_bytes(size_t rows, int cap) {
+  return ((rows * sizeof(int) + 255) & ~(size_t)255) + rows * (size_t)cap * sizeof(unsigned long long);
+}
+static size_t knn_append_bytes(int B, int N, int k) { return knn_append_rows_bytes((size_t)B * (size_t)N, knn_append_cap(k, N)); }
+static int knn_append_tighten_mask(bool lx) {
+  static int tight = -1;                     // DGCNN_KNN_TIGHTEN_EVERY (power of two; A/B switch): bound tightening every n-th tile
+  if (tight < 0) { const char* e = getenv("DGCNN_KNN_TIGHTEN_EVERY"); tight = e ? atoi(e) : 0; if (tight < 0 || (tight & (tight - 1))) tight = 1; }
+  // default: every 4th tile below N = 8192, every 8th above (profiles/r06/knn_tight.txt: 175 -> 168 us, 1.83 -> 1.70 ms, 19.2 -> 17.6 ms per call)
+  return (tight ? tight : (lx ? 4 : 8)) - 1;
 }
 
 extern "C" int64_t dgcnn_knn_workspace_bytes(int B, int N, int C, int k) {
@@ -1540,7 +1611,7 @@ static int knn_impl(const char* what, const float* x, int B, int N, int C, int64
   float* tau0 = nullptr;
   if (seeded) {
     tau0 = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + knn_sq_bytes(B, N));
-    if (!launch_seed_bound(x, sq_ws, B, N, C, ldx, seed, ldseed, k, tau0, st)) tau0 = nullptr;      // (the first k seeds of every row)
+    if (!launch_seed_bound(x, sq_ws, rows, DenseClouds(N), C, ldx, seed, ldseed, k, tau0, st)) tau0 = nullptr;      // (the first k seeds of every row)
   }
   if (tau0 && append) {                          // bound known in advance: append-form scan + one selection per row
     char* base = reinterpret_cast<char*>(ws) + grid_off;
@@ -1549,10 +1620,7 @@ static int knn_impl(const char* what, const float* x, int B, int N, int C, int64
     const int cap = knn_append_cap(k, N);
     const dim3 grid((unsigned)dg::cdiv(N, ROWS), (unsigned)B);
     const int npr = knn_append_products(knn_append_lx(N));
-    static int tight = -1;                     // DGCNN_KNN_TIGHTEN_EVERY (power of two; A/B switch): bound tightening every n-th tile
-    if (tight < 0) { const char* e = getenv("DGCNN_KNN_TIGHTEN_EVERY"); tight = e ? atoi(e) : 0; if (tight < 0 || (tight & (tight - 1))) tight = 1; }
-    // default: every 4th tile below N = 8192, every 8th above (profiles/r06/knn_tight.txt: 175 -> 168 us, 1.83 -> 1.70 ms, 19.2 -> 17.6 ms per call)
-    const int tmask = (tight ? tight : (knn_append_lx(N) ? 4 : 8)) - 1;
+    const int tmask = knn_append_tighten_mask(knn_append_lx(N));
 #define DG_KA(LXV, NPRV) dg::launch((knn_bf16a_kernel<LXV, NPRV>), grid, dim3(256), 0, st, x, (const float*)sq_ws, N, C, ldx, k, (const float*)tau0, cap, ent, cnt, tmask)
     if (knn_append_lx(N)) { if (npr == 1) DG_KA(true, 1); else DG_KA(true, 3); }
     else { if (npr == 1) DG_KA(false, 1); else DG_KA(false, 3); }
@@ -1593,4 +1661,79 @@ extern "C" int dgcnn_knn_seeded_f32(const float* x, int B, int N, int C, int64_t
                                     int kseed, int32_t* idx, void* ws, size_t ws_bytes, void* stream) {
   DG_REQUIRE(!seed || (ldseed >= kseed && kseed > 0), DGCNN_EINVAL, "dgcnn_knn_seeded_f32: bad seed shape");
   return knn_impl("dgcnn_knn_seeded_f32", x, B, N, C, ldx, k, seed, ldseed, kseed, idx, ws, ws_bytes, stream);
+}
+
+// ---- packed towers: clouds of different sizes concatenated row-wise, cloud b = rows [seg_off[b], seg_off[b + 1]) -----------------
+// Every form below is the dense kernel instantiated with PackedClouds (a block maps to its cloud's base and size instead of b N and
+// N); the host-known smallest / largest cloud (min_n, max_n) takes every decision the dense search takes from N.
+extern "C" int64_t dgcnn_knn_seg_workspace_bytes(int rows, int max_n, int C, int k) {
+  if (rows <= 0 || max_n <= 0) return 0;
+  size_t n = 2 * knn_sq_bytes(1, rows);              // s_i, and the seed bounds (or the histogram bounds of C <= 4)
+  if (knn_append_shape(C, k)) n += knn_append_rows_bytes((size_t)rows, knn_append_cap(k, max_n));
+  return (int64_t)n;
+}
+
+extern "C" int dgcnn_knn_seg_f32(const float* x, int64_t ldx, int C, int k, int nseg, const int32_t* seg_off, int rows, int min_n,
+                                 int max_n, const int32_t* seed, int64_t ldseed, int kseed, int32_t* idx, void* ws, size_t ws_bytes,
+                                 void* stream) {
+  const char* what = "dgcnn_knn_seg_f32";
+  DG_REQUIRE(x && idx && ws && seg_off, DGCNN_EINVAL, "%s: null pointer", what);
+  DG_REQUIRE(nseg > 0 && nseg <= 65535 && rows > 0 && C > 0 && ldx >= C, DGCNN_EINVAL, "%s: bad shape nseg=%d rows=%d C=%d", what,
+             nseg, rows, C);
+  DG_REQUIRE(min_n > 0 && min_n <= max_n && max_n <= rows && (int64_t)min_n * nseg <= rows && (int64_t)max_n * nseg >= rows,
+             DGCNN_EINVAL, "%s: cloud sizes min_n=%d max_n=%d do not fit %d rows in %d clouds", what, min_n, max_n, rows, nseg);
+  DG_REQUIRE(k > 0 && k <= min_n, DGCNN_EINVAL, "%s: k=%d must be in [1, smallest cloud=%d] (tf.nn.top_k raises otherwise)", what, k,
+             min_n);
+  DG_REQUIRE(k <= 64, DGCNN_EUNSUP, "%s: k=%d > 64 unsupported", what, k);
+  DG_REQUIRE(C <= 128, DGCNN_EUNSUP, "%s: C=%d > 128 unsupported", what, C);
+  DG_REQUIRE(!seed || (ldseed >= kseed && kseed > 0), DGCNN_EINVAL, "%s: bad seed shape", what);
+  DG_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0 && ws_bytes >= knn_sq_bytes(1, rows), DGCNN_EINVAL,
+             "%s: workspace must be 16-byte aligned and hold dgcnn_knn_seg_workspace_bytes(rows, max_n, C, k) bytes (got %zu)", what,
+             ws_bytes);
+  hipStream_t st = (hipStream_t)stream;
+  float* sq_ws = reinterpret_cast<float*>(ws);
+  float* tb = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + knn_sq_bytes(1, rows));
+  const bool tb_ok = ws_bytes >= 2 * knn_sq_bytes(1, rows);
+  const PackedClouds cl{seg_off, nseg};
+  const int vec_ok = (ldx % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
+  const size_t aux = 2 * knn_sq_bytes(1, rows);
+  const bool lx = knn_append_lx(max_n);
+  const int cap = knn_append_cap(k, max_n);
+  const bool append = knn_append_on() && knn_append_shape(C, k) && vec_ok && !knn_force_valu() && knn_bf16f_mode() != 0 &&
+                      ws_bytes >= aux + knn_append_rows_bytes((size_t)rows, cap);
+  const int seed_min = knn_seed_min_n() >= 0 ? knn_seed_min_n() : 0;
+  const bool seeded = append && seed && kseed >= k && kseed <= 64 && min_n >= seed_min && (int64_t)max_n * ldx < ((int64_t)1 << 31);
+  dg::launch(sqnorm_kernel, dim3((unsigned)dg::cdiv(rows, SQ_ROWS)), dim3(256), sizeof(float) * SQ_ROWS * (C + 1), st, x, ldx,
+             (int64_t)rows, C, sq_ws);
+  if (seeded && launch_seed_bound(x, sq_ws, (int64_t)rows, cl, C, ldx, seed, ldseed, k, tb, st)) {
+    char* base = reinterpret_cast<char*>(ws) + aux;
+    int* cnt = reinterpret_cast<int*>(base);
+    unsigned long long* ent = reinterpret_cast<unsigned long long*>(base + (((size_t)rows * sizeof(int) + 255) & ~(size_t)255));
+    const dim3 grid((unsigned)dg::cdiv(max_n, ROWS), (unsigned)nseg);
+    const int npr = knn_append_products(lx);
+    const int tmask = knn_append_tighten_mask(lx);
+#define DG_KA(LXV, NPRV) dg::launch((knn_bf16a_kernel<LXV, NPRV, PackedClouds>), grid, dim3(256), 0, st, x, (const float*)sq_ws, cl, C, ldx, k, (const float*)tb, cap, ent, cnt, tmask)
+    if (lx) { if (npr == 1) DG_KA(true, 1); else DG_KA(true, 3); }
+    else { if (npr == 1) DG_KA(false, 1); else DG_KA(false, 3); }
+#undef DG_KA
+    dg::launch(knn_select_kernel, dim3((unsigned)dg::cdiv(rows, 4)), dim3(256), 0, st, (const unsigned long long*)ent, (const int*)cnt,
+               (int64_t)rows, cap, k, idx);
+    return dg::check_launch(what);
+  }
+  if (C <= 4) {
+    // the histogram bound's precondition N >= 4 k stride must hold for the smallest cloud
+    const int hs = knn_hist_stride(min_n);
+    const float* tau0 = nullptr;
+    if (hs > 0 && !knn_force_valu() && min_n >= 4 * k * hs && tb_ok) {
+      const dim3 hg((unsigned)dg::cdiv(max_n, 64), (unsigned)nseg);
+      if (hs == 1) dg::launch(knn_hist_bound_kernel<1, PackedClouds>, hg, dim3(256), 0, st, x, (const float*)sq_ws, cl, C, ldx, k, tb);
+      else if (hs == 2) dg::launch(knn_hist_bound_kernel<2, PackedClouds>, hg, dim3(256), 0, st, x, (const float*)sq_ws, cl, C, ldx, k, tb);
+      else dg::launch(knn_hist_bound_kernel<4, PackedClouds>, hg, dim3(256), 0, st, x, (const float*)sq_ws, cl, C, ldx, k, tb);
+      tau0 = tb;
+    }
+    return dispatch_k_packed<4>(x, sq_ws, cl, max_n, C, ldx, k, vec_ok, idx, tau0, st);
+  }
+  if (C <= 16) return dispatch_k_packed<16>(x, sq_ws, cl, max_n, C, ldx, k, vec_ok, idx, nullptr, st);
+  if (C <= 64) return dispatch_k_packed<64>(x, sq_ws, cl, max_n, C, ldx, k, vec_ok, idx, nullptr, st);
+  return dispatch_k_packed<128>(x, sq_ws, cl, max_n, C, ldx, k, vec_ok, idx, nullptr, st);
 }

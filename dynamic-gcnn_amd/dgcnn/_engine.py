@@ -508,9 +508,47 @@ def rank4(v, B, N):
 KNN_SEED = os.environ.get("DGCNN_KNN_SEED", "1") != "0"   # seed a layer's k-NN filter with the previous layer's graph (A/B switch)
 
 
-def knn(x2d, B, N, k, seed=None):
+class Segments(object):
+    """A packed tower: nseg clouds of different sizes concatenated row-wise, cloud b = rows [offsets[b], offsets[b + 1]).  Holds the
+    host offsets (validated here, before any device work), their device copy (made once, on first use) and the smallest / largest
+    cloud, from which the k-NN picks its kernel forms."""
+
+    def __init__(self, offsets, rows=None):
+        if isinstance(offsets, torch.Tensor):
+            offsets = offsets.detach().cpu().numpy()
+        off = np.asarray(offsets)
+        if off.ndim != 1 or off.size < 2 or not np.issubdtype(off.dtype, np.integer):
+            raise ValueError("offsets: expected nseg + 1 >= 2 integers, got %r" % (offsets,))
+        off = off.astype(np.int64)
+        sizes = np.diff(off)
+        if off[0] != 0 or (sizes <= 0).any():
+            raise ValueError("offsets must start at 0 and increase strictly (no empty cloud): %s" % (off.tolist(),))
+        if rows is not None and off[-1] != rows:
+            raise ValueError("offsets end at %d, the tower has %d rows" % (off[-1], rows))
+        if off[-1] >= 1 << 31 or off.size - 1 > 65535:
+            raise ValueError("a packed tower holds < 2^31 rows in at most 65535 clouds")
+        self.host = off
+        self.nseg = int(off.size - 1)
+        self.rows = int(off[-1])
+        self.min_n, self.max_n = int(sizes.min()), int(sizes.max())
+        self._dev = None
+
+    def check_k(self, k):
+        if k <= 0 or k > self.min_n:
+            raise ValueError("k_nn: k=%d must be in [1, smallest cloud=%d] (tf.nn.top_k raises otherwise)" % (k, self.min_n))
+
+    def device(self, dev):
+        if self._dev is None or self._dev.device != dev:
+            self._dev = torch.from_numpy(self.host.astype(np.int32)).to(dev)
+        return self._dev
+
+
+def knn(x2d, B, N, k, seed=None, seg=None):
     """idx (B,N,k) of x2d (B*N, C).  seed: an earlier graph of the same clouds, (B,N,ks) int32 with ks >= k -- ks distinct candidates
-    per row whose largest distance bounds the row's k-th distance from above (dgcnn_knn_seeded_f32); the result does not depend on it."""
+    per row whose largest distance bounds the row's k-th distance from above (dgcnn_knn_seeded_f32); the result does not depend on it.
+    seg: a packed tower (Segments; B = 1, N = rows): every row searches its own cloud, idx holds tower rows (dgcnn_knn_seg_f32)."""
+    if seg is not None:
+        return knn_packed(x2d, k, seg, seed=seed)
     C = x2d.shape[1]
     idx = torch.empty((B, N, k), dtype=torch.int32, device=x2d.device)
     nws = int(H.load().dgcnn_knn_workspace_bytes(B, N, C, k))           # s_i, seed bounds (+ the cell grid's scratch for raw coordinates)
@@ -532,6 +570,30 @@ def knn(x2d, B, N, k, seed=None):
     else:
         H.call("dgcnn_knn_f32", x2d.data_ptr(), B, N, C, H.ld2(x2d), k, idx.data_ptr(), ws.data_ptr(), nws, tag=tag,
                work=2.0 * B * N * N * C)
+    return idx
+
+
+def knn_packed(x2d, k, seg, seed=None):
+    """idx (1,R,k) of the packed tower x2d (R, C): per cloud the dense k_nn of that cloud, as tower rows."""
+    R, C = x2d.shape
+    if R != seg.rows:
+        raise ValueError("offsets end at %d, the tower has %d rows" % (seg.rows, R))
+    seg.check_k(k)
+    off = seg.device(x2d.device)
+    idx = torch.empty((1, R, k), dtype=torch.int32, device=x2d.device)
+    nws = int(H.load().dgcnn_knn_seg_workspace_bytes(R, seg.max_n, C, k))
+    ws = torch.empty((nws,), dtype=torch.uint8, device=x2d.device)
+    Cp, kc = (4 if C <= 4 else 16 if C <= 16 else 64 if C <= 64 else 128), (8 if k <= 8 else 20 if k <= 20 else 40 if k <= 40 else 64)
+    seeded = (KNN_SEED and seed is not None and seed.dim() == 3 and seed.shape[0] == 1 and seed.shape[1] == R and seed.shape[2] >= k
+              and seed.dtype == torch.int32 and seed.is_contiguous())
+    if seeded and 16 < C <= 64:
+        tag = "knn_seg_call<C%d,k%d>[sqnorm_kernel+knn_seed_bound_kernel+knn_bf16a_kernel+knn_select_kernel]" % (Cp, kc)
+    else:
+        tag = "knn_seg_call<C%d,k%d>[sqnorm_kernel+%sknn_kernel]" % (Cp, kc, "knn_hist_bound_kernel+" if C <= 4 else "")
+    n = seg.host[1:] - seg.host[:-1]
+    H.call("dgcnn_knn_seg_f32", x2d.data_ptr(), H.ld2(x2d), C, k, seg.nseg, off.data_ptr(), R, seg.min_n, seg.max_n,
+           seed.data_ptr() if seeded else None, int(seed.shape[2]) if seeded else 0, int(seed.shape[2]) if seeded else 0,
+           idx.data_ptr(), ws.data_ptr(), nws, tag=tag, work=2.0 * float((n * n).sum()) * C)
     return idx
 
 
@@ -907,13 +969,19 @@ def build_csr(idx, B, N, k, side=None):
     return off, (rev if srt is None else srt)
 
 
-def edge_conv_block(x, B, N, k, num_filters, relu1=True, outs=None, net2=None, seed=None):
+def edge_conv_block(x, B, N, k, num_filters, relu1=True, outs=None, net2=None, seed=None, seg=None):
     """x: (B*N, C) view.  Returns (mm, net, idx): mm = (R,2F) [max | mean], net = (R,64).
     outs = (mm_view, net_view) destination slices (model path) or None (fresh buffers).
-    seed: the previous EdgeConv layer's graph (B,N,k') or None: seeds this layer's k-NN filter (same result, fewer inserts)."""
+    seed: the previous EdgeConv layer's graph (B,N,k') or None: seeds this layer's k-NN filter (same result, fewer inserts).
+    seg: a packed tower (Segments) with B = 1, N = R: only the k-NN is tied to a cloud (idx holds tower rows), every other pass is
+    row-wise -- BatchNorm statistics run over all rows of the tower, as in a dense (B, N) tower."""
     c = ctx()
     R, C = x.shape
     F = int(num_filters)
+    if seg is not None:
+        if B != 1 or N != seg.rows:
+            raise ValueError("a packed tower is one (1, R) block: got B=%d N=%d for %d rows" % (B, N, seg.rows))
+        seg.check_k(k)
     if k > N:
         raise ValueError("k_nn: k=%d > N=%d (tf.nn.top_k raises InvalidArgument)" % (k, N))
     with variable_scope("conv0"):
@@ -924,7 +992,7 @@ def edge_conv_block(x, B, N, k, num_filters, relu1=True, outs=None, net2=None, s
     bf16 = EDGE_MLP_DTYPE == "bf16"
     literal = EDGE_MLP_LITERAL or bf16
     gather = (not literal) and (not EDGE_MLP_NBR_GEMM) and F % 4 == 0 and F <= 1024
-    idx = knn(x, B, N, k, seed=seed)                                    # ops.py:8-19
+    idx = knn(x, B, N, k, seed=seed, seg=seg)                           # ops.py:8-19
     virtual = gather and not EDGE_MATERIALIZE_Y and k < 256   # conv0 output never written: recomputed from (V, U, idx)
     #                                                           (the edge BN passes pack tie / positive counts: k < 256)
     # the fused bf16 kernels write neither E nor y: decided BEFORE anything of (R*k, F) is allocated (1.3 GB per layer at configs[2])

@@ -26,11 +26,33 @@ def _is_relu(activation):
     raise NotImplementedError("only relu / None activations exist in the reference (ops.py:42,123)")
 
 
-def k_nn(points, k):
+def _segments(points, offsets, ks):
+    """Host-side checks of a packed tower, before any device work: points (R,C), (1,R,C) or (1,R,1,C); offsets (nseg + 1 ints from
+    0 to R, strictly increasing) or a Segments; every k at most the smallest cloud."""
+    shp = tuple(points.shape)
+    if len(shp) == 2 or (len(shp) in (3, 4) and shp[0] == 1 and (len(shp) == 3 or shp[2] == 1)):
+        R = shp[0] if len(shp) == 2 else shp[1]
+    else:
+        raise ValueError("a packed tower is (R,C), (1,R,C) or (1,R,1,C), got %s" % (shp,))
+    seg = offsets if isinstance(offsets, E.Segments) else E.Segments(offsets, R)
+    if seg.rows != R:
+        raise ValueError("offsets end at %d, the tower has %d rows" % (seg.rows, R))
+    for k in ks:
+        seg.check_k(int(k))
+    return seg
+
+
+def k_nn(points, k, offsets=None):
     """dgcnn/ops.py:8-19.  points (B,N,C) -> idx (B,N,k) int32: the k nearest (squared L2 via
-    (s_i+s_j)-2<x_i,x_j>), self included, ascending, ties -> lower index.  Bit-exact vs the oracle."""
-    x, B, N = E.as2d(points)
+    (s_i+s_j)-2<x_i,x_j>), self included, ascending, ties -> lower index.  Bit-exact vs the oracle.
+    offsets: a packed tower of clouds of different sizes, points (R,C) or (1,R,C), cloud b = rows [offsets[b], offsets[b + 1]):
+    idx (1,R,k) holds tower rows (offsets[b] + j), per cloud the dense k_nn of that cloud alone."""
     k = int(k)
+    if offsets is not None:
+        seg = _segments(points, offsets, [k])
+        x, _, R = E.as2d(points)
+        return E.knn(x, 1, R, k, seg=seg)
+    x, B, N = E.as2d(points)
     if k > N or k <= 0:
         raise ValueError("k_nn: k=%d must be in [1, N=%d] (tf.nn.top_k raises otherwise)" % (k, N))
     return E.knn(x, B, N, k)
@@ -39,22 +61,26 @@ def k_nn(points, k):
 knn = k_nn
 
 
-def edges(points, k=20):
-    """dgcnn/ops.py:21-40.  (B,N,C) -> edge features (B,N,k,2C) = concat[x_i, x_j - x_i]."""
+def edges(points, k=20, offsets=None):
+    """dgcnn/ops.py:21-40.  (B,N,C) -> edge features (B,N,k,2C) = concat[x_i, x_j - x_i].  offsets: a packed tower (k_nn), (1,R,k,2C)."""
+    idx = k_nn(points, k, offsets=offsets)
     x, B, N = E.as2d(points)
     C = x.shape[1]
-    idx = k_nn(points, k)
     out = torch.empty((B, N, int(k), 2 * C), dtype=torch.float32, device=x.device)
     H.call("dgcnn_edge_gather_f32", x.data_ptr(), H.ld2(x), idx.data_ptr(), B, N, C, int(k), out.data_ptr())
     return out
 
 
-def edge_conv(point_cloud, k, num_filters, trainable, activation=relu, debug=False, _outs=None, _net2=None, _seed=None):
+def edge_conv(point_cloud, k, num_filters, trainable, activation=relu, debug=False, _outs=None, _net2=None, _seed=None,
+              offsets=None):
     """dgcnn/ops.py:42-73.  Returns the list [net_max, net_mean, net], each (B,N,1,ch).
-    _seed: the previous layer's neighbour graph (the stacks pass it): only speeds this layer's k-NN up."""
+    _seed: the previous layer's neighbour graph (the stacks pass it): only speeds this layer's k-NN up.
+    offsets: a packed tower (k_nn): the neighbours come from the row's own cloud, every other pass (BatchNorm included) runs over
+    all R rows as in a dense tower; outputs (1,R,1,ch)."""
+    seg = None if offsets is None else _segments(point_cloud, offsets, [k])
     x, B, N = E.as2d(point_cloud)
     F = int(num_filters)
-    mm, net, idx = E.edge_conv_block(x, B, N, int(k), F, relu1=_is_relu(activation), outs=_outs, net2=_net2, seed=_seed)
+    mm, net, idx = E.edge_conv_block(x, B, N, int(k), F, relu1=_is_relu(activation), outs=_outs, net2=_net2, seed=_seed, seg=seg)
     res = [E.rank4(mm[:, :F], B, N), E.rank4(mm[:, F:], B, N), E.rank4(net, B, N)]
     if debug:
         for t in res:
@@ -75,30 +101,33 @@ def _listify(v, repeat, what):
     return [int(v)] * repeat
 
 
-def repeat_edge_conv(point_cloud, repeat, k, num_filters, trainable, debug=False, _plan=None):
+def repeat_edge_conv(point_cloud, repeat, k, num_filters, trainable, debug=False, _plan=None, offsets=None):
     """dgcnn/ops.py:75-98.  Flat list of 3*repeat tensors; layer i+1 builds its k-NN graph on
-    squeeze(tensors[-1]) -- the dynamic graph."""
+    squeeze(tensors[-1]) -- the dynamic graph.  offsets: a packed tower (edge_conv)."""
     repeat = int(repeat)
     k = _listify(k, repeat, "k")
     num_filters = _listify(num_filters, repeat, "num_filters")
+    seg = None if offsets is None else _segments(point_cloud, offsets, k)
     net = point_cloud
     tensors = []
     seed = None
     for i in range(repeat):
         with E.variable_scope("EdgeConv%d" % i):
             outs, net2 = _plan(i) if _plan is not None else (None, None)
-            tensors += edge_conv(net, k[i], num_filters[i], trainable, debug=debug, _outs=outs, _net2=net2, _seed=seed)
+            tensors += edge_conv(net, k[i], num_filters[i], trainable, debug=debug, _outs=outs, _net2=net2, _seed=seed,
+                                 offsets=seg)
             seed = edge_conv.last_idx                    # layer i's graph seeds layer i + 1's search (same points)
             net = tensors[-1][:, :, 0, :]
     return tensors
 
 
-def repeat_residual_edge_conv(point_cloud, repeat, k, num_filters, trainable, debug=False, _plan=None):
+def repeat_residual_edge_conv(point_cloud, repeat, k, num_filters, trainable, debug=False, _plan=None, offsets=None):
     """dgcnn/ops.py:100-140.  Layers >= 1: conv1 without activation, optional shortcut conv when
-    num_filters changes, tensors[-1] = relu(shortcut + tensors[-1])."""
+    num_filters changes, tensors[-1] = relu(shortcut + tensors[-1]).  offsets: a packed tower (edge_conv)."""
     repeat = int(repeat)
     k = _listify(k, repeat, "k")
     num_filters = _listify(num_filters, repeat, "num_filters")
+    seg = None if offsets is None else _segments(point_cloud, offsets, k)
     net = point_cloud
     tensors = []
     shortcut = None
@@ -107,11 +136,12 @@ def repeat_residual_edge_conv(point_cloud, repeat, k, num_filters, trainable, de
         with E.variable_scope("EdgeConv%d" % i):
             outs, net2 = _plan(i) if _plan is not None else (None, None)
             if shortcut is None:
-                tensors += edge_conv(net, k[i], num_filters[i], trainable, debug=debug, _outs=outs, _net2=net2, _seed=seed)
+                tensors += edge_conv(net, k[i], num_filters[i], trainable, debug=debug, _outs=outs, _net2=net2, _seed=seed,
+                                     offsets=seg)
             else:
                 # conv1 (no activation) goes to a scratch buffer; relu(shortcut + conv1) takes the planned slot
                 tensors += edge_conv(net, k[i], num_filters[i], trainable, activation=None, debug=debug,
-                                     _outs=None if outs is None else (outs[0], None), _seed=seed)
+                                     _outs=None if outs is None else (outs[0], None), _seed=seed, offsets=seg)
                 sc, B, N = E.as2d(shortcut)
                 if not num_filters[i] == num_filters[i - 1]:
                     sc = E.conv_bn_act(sc, "shortcut", num_filters[i], relu=False)       # ops.py:125-133

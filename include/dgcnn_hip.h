@@ -98,6 +98,15 @@ int dgcnn_knn_append_products(int n);
  * of ~k (1 + ln(N / k)) per list.  stride 0 = off, 1 / 2 (default) / 4; any other value only queries.  Identical indices either way.
  * Returns the previous setting.  (tools / tests; env DGCNN_KNN_HIST) */
 int dgcnn_knn_hist(int stride);
+/* Packed tower: nseg clouds of different sizes concatenated row-wise, cloud b = rows [seg_off[b], seg_off[b + 1]) of x (rows, C),
+ * seg_off (device, nseg + 1 int32) strictly increasing from 0 to rows.  Every row searches its own cloud only; idx (rows, k) holds
+ * TOWER rows (seg_off[b] + j).  Per cloud the result is dgcnn_knn_f32 of that cloud alone, bit for bit (same order, self included,
+ * ties -> lower row).  min_n / max_n: the smallest / largest cloud (host-known; they choose the kernel forms); k <= min_n.
+ * seed (rows, >= kseed, row stride ldseed) or NULL: an earlier packed graph of the same tower (tower rows); a seed outside the
+ * query row's cloud invalidates that row's bound (the row is searched without one).  Workspace: dgcnn_knn_seg_workspace_bytes. */
+int64_t dgcnn_knn_seg_workspace_bytes(int rows, int max_n, int C, int k);
+int dgcnn_knn_seg_f32(const float* x, int64_t ldx, int C, int k, int nseg, const int32_t* seg_off, int rows, int min_n, int max_n,
+                      const int32_t* seed, int64_t ldseed, int kseed, int32_t* idx, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- K3 in its bf16-operand form (BASELINE configs[2] "bf16 edge-MLP MFMA"): conv0 of an EdgeConv layer, ops.py:21-52 ------
  * E[e] = [x_i, x_j - x_i] formed in fp32 and rounded to bf16 once (RNE), W0 (2C x F, row-major) rounded to bf16 once,
