@@ -789,6 +789,7 @@ int launch_act_kreduce(const char* what, Src src, int64_t R, int k, int F, const
                        const float* beta, int relu, float* max_out, int64_t ldmax, float* mean_out, int64_t ldmean,
                        float* out2, int64_t ldout2, float* cnt_out, hipStream_t st) {
   DG_REQUIRE(mean && rstd && beta && max_out, DGCNN_EINVAL, "%s: null pointer", what);
+  DG_REQUIRE(relu == 0 || relu == 1, DGCNN_EINVAL, "%s: relu must be 0 or 1 (got %d; the bf16 flag belongs to the apply pass)", what, relu);
   const bool vec = (F % 4 == 0) && (ldmax % 4 == 0) && (G || a16(src.Y)) && a16(max_out) && a16(mean) && a16(rstd) &&
                    a16(beta) && (!mean_out || ((ldmean % 4 == 0) && a16(mean_out))) &&
                    (!out2 || ((ldout2 % 4 == 0) && a16(out2))) && (!cnt_out || a16(cnt_out));
@@ -818,6 +819,7 @@ int launch_bwd_reduce(const char* what, Src src, int64_t R, int k, int F, const 
   DG_REQUIRE(mean && rstd && beta && dmax && red, DGCNN_EINVAL, "%s: null pointer", what);
   DG_REQUIRE(F <= 8192, DGCNN_EINVAL, "%s: F > 8192", what);
   DG_REQUIRE(!mx_in || cnt_in, DGCNN_EINVAL, "%s: mx_in needs cnt_in", what);
+  DG_REQUIRE(relu == 0 || relu == 1, DGCNN_EINVAL, "%s: relu must be 0 or 1 (got %d; the bf16 flag belongs to the apply pass)", what, relu);
   const bool vec = (F % 4 == 0) && (lddmax % 4 == 0) && (G || a16(src.Y)) && a16(dmax) && a16(mean) && a16(rstd) &&
                    a16(beta) && (!dmean || ((lddmean % 4 == 0) && a16(dmean))) &&
                    (!mx_in || ((ldmx % 4 == 0) && a16(mx_in) && a16(cnt_in)));
@@ -852,6 +854,7 @@ int launch_bwd_apply(const char* what, Src src, int64_t R, int k, int F, const f
                      float* dYsum, int64_t lddysum, float* dbeta, float dbeta_beta, hipStream_t st) {
   DG_REQUIRE(mean && rstd && beta && dmax && red && dY, DGCNN_EINVAL, "%s: null pointer", what);
   DG_REQUIRE(!dYsum || lddysum >= F, DGCNN_EINVAL, "%s: lddysum < F", what);
+  DG_REQUIRE(relu >= 0 && relu <= 3, DGCNN_EINVAL, "%s: relu must be 0 .. 3 (bit 0 = ReLU, bit 1 = bf16 dY; got %d)", what, relu);
   dg::launch(bn_bwd_finalize_kernel, dim3((unsigned)dg::cdiv(F, FIN_COLS)), dim3(FIN_COLS * FIN_LANES), 0, st, red, F, dg::stat_slots(), dbeta,
                      dbeta_beta);
   const bool vec = (F % 4 == 0) && (lddmax % 4 == 0) && (G || a16(src.Y)) && a16(dY) && a16(dmax) && a16(mean) &&
@@ -863,7 +866,7 @@ int launch_bwd_apply(const char* what, Src src, int64_t R, int k, int F, const f
     dg::launch((bn_bwd_apply_kernel<4, true>), dim3(grid8(grid_for(R * (F / 4)))), dim3(256), 0, st, src, R, k, F,
                        mean, rstd, beta, relu, dmax, lddmax, dmean, lddmean, mx_in, ldmx, cnt_in, red, dY, dYsum, lddysum,
                        shift_of(F / 4));
-  } else if (vec && k == 1 && !mx_in) {
+  } else if (vec && k == 1 && !mx_in && !(relu & 2)) {       // (the column-fixed kernel has no bf16 rounding: bit 1 takes the general one)
     const K1Grid g = k1_grid(R, F, 4096);
     dg::launch((bn1_bwd_kernel<true>), g.grid, dim3(256), 0, st, src.Y, R, F, g.FVB, g.RP, mean, rstd, beta, relu,
                        dmax, lddmax, dmean, lddmean, red, dY, dYsum, lddysum, (const uint64_t*)nullptr, 1.0f, dg::stat_slots());
@@ -982,7 +985,8 @@ extern "C" int dgcnn_edge_bn_bwd_apply_f32(const float* V, int64_t ldv, const fl
 // ---- the last FC layer with tf.nn.dropout fused behind it (model.py:88-91): out = dropout(relu(bn(T))), and its backward
 // reading the gradient of the dropped output through the same mask.  (R, F) contiguous, F % 4 == 0.
 static int check_bn1_drop(const char* what, const float* T, int64_t R, int F, const float* mean, const float* rstd,
-                          const float* beta, float keep, const uint64_t* seed_dev) {
+                          const float* beta, int relu, float keep, const uint64_t* seed_dev) {
+  DG_REQUIRE(relu == 0 || relu == 1, DGCNN_EINVAL, "%s: relu must be 0 or 1 (got %d)", what, relu);
   DG_REQUIRE(T && mean && rstd && beta && seed_dev && R > 0 && F > 0 && keep > 0.f && keep <= 1.f, DGCNN_EINVAL, "%s: bad args", what);
   DG_REQUIRE(F % 4 == 0 && a16(T) && a16(mean) && a16(rstd) && a16(beta), DGCNN_EUNSUP, "%s: F %% 4 == 0 and 16-byte aligned operands required", what);
   return DGCNN_OK;
@@ -991,7 +995,7 @@ static int check_bn1_drop(const char* what, const float* T, int64_t R, int F, co
 extern "C" int dgcnn_bn1_act_dropout_f32(const float* T, int64_t R, int F, const float* mean, const float* rstd,
                                          const float* beta, int relu, float keep, const uint64_t* seed_dev, float* out,
                                          int64_t ldo, void* stream) {
-  int rc = check_bn1_drop("dgcnn_bn1_act_dropout_f32", T, R, F, mean, rstd, beta, keep, seed_dev);
+  int rc = check_bn1_drop("dgcnn_bn1_act_dropout_f32", T, R, F, mean, rstd, beta, relu, keep, seed_dev);
   if (rc) return rc;
   DG_REQUIRE(out && ldo % 4 == 0 && a16(out), DGCNN_EINVAL, "dgcnn_bn1_act_dropout_f32: out must be 16-byte aligned, ld %% 4 == 0");
   const K1Grid g = k1_grid(R, F, 4096);
@@ -1004,7 +1008,7 @@ extern "C" int dgcnn_bn1_bwd_dropout_f32(const float* T, int64_t R, int F, const
                                          const float* beta, int relu, float keep, const uint64_t* seed_dev,
                                          const float* dout, int64_t lddo, double* red, float* dT, float* dbeta,
                                          float dbeta_beta, void* stream) {
-  int rc = check_bn1_drop("dgcnn_bn1_bwd_dropout_f32", T, R, F, mean, rstd, beta, keep, seed_dev);
+  int rc = check_bn1_drop("dgcnn_bn1_bwd_dropout_f32", T, R, F, mean, rstd, beta, relu, keep, seed_dev);
   if (rc) return rc;
   DG_REQUIRE(dout && red && dT && lddo % 4 == 0 && a16(dout) && a16(dT) && F <= 8192, DGCNN_EINVAL, "dgcnn_bn1_bwd_dropout_f32: bad args");
   hipStream_t st = (hipStream_t)stream;

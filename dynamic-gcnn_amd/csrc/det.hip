@@ -186,6 +186,7 @@ extern "C" int dgcnn_bn_bwd_reduce_det_f32(const float* Y, int64_t R, int k, int
                                            const float* cnt_in, double* red, void* ws, size_t ws_bytes, void* stream) {
   DG_REQUIRE(Y && mean && rstd && beta && dmax && red && ws && R > 0 && k > 0 && F > 0 && F <= 256 * DET_C, DGCNN_EINVAL,
              "dgcnn_bn_bwd_reduce_det_f32: bad args");
+  DG_REQUIRE(relu == 0 || relu == 1, DGCNN_EINVAL, "dgcnn_bn_bwd_reduce_det_f32: relu must be 0 or 1 (got %d)", relu);
   DG_REQUIRE(!dmean || (mx_in && cnt_in), DGCNN_EINVAL, "dgcnn_bn_bwd_reduce_det_f32: the k > 1 form needs the forward's max / tie counts");
   DG_REQUIRE(ws_bytes >= sizeof(double) * DET_G * 2 * (size_t)F, DGCNN_ENOSPC, "dgcnn_bn_bwd_reduce_det_f32: workspace too small");
   double* part = reinterpret_cast<double*>(ws);

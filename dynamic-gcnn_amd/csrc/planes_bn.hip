@@ -309,6 +309,7 @@ extern "C" int dgcnn_bn_act_planes_f32(const float* T, int64_t ldt, int64_t R, i
                                        int64_t plane_stride, int64_t rows_alloc, float* out, int64_t ldo, float* out2,
                                        int64_t ldo2, void* stream) {
   DG_REQUIRE(T && mean && rstd && beta && planes && R > 0 && F > 0, DGCNN_EINVAL, "dgcnn_bn_act_planes_f32: bad args");
+  DG_REQUIRE(relu == 0 || relu == 1, DGCNN_EINVAL, "dgcnn_bn_act_planes_f32: relu must be 0 or 1 (got %d)", relu);
   DG_REQUIRE(fmt == DGCNN_PLANES_F16X2, DGCNN_EINVAL, "dgcnn_bn_act_planes_f32: unknown format %d", fmt);
   DG_REQUIRE(F % 8 == 0 && ldt % 4 == 0 && a16(T) && a16(mean) && a16(rstd) && a16(beta) && a16(planes) && plane_stride % 16 == 0 &&
                  rows_alloc % 64 == 0 && rows_alloc >= R && (!out || (a16(out) && ldo % 4 == 0)) && (!out2 || (a16(out2) && ldo2 % 4 == 0)),
@@ -324,6 +325,7 @@ extern "C" int dgcnn_bn1_bwd_reduce_max_f32(const float* T, int64_t R, int F, co
                                             const float* beta, int relu, const float* dout, int64_t lddo, double* red,
                                             void* maxbits, void* stream) {
   DG_REQUIRE(T && mean && rstd && beta && dout && red && maxbits && R > 0 && F > 0, DGCNN_EINVAL, "dgcnn_bn1_bwd_reduce_max_f32: bad args");
+  DG_REQUIRE(relu == 0 || relu == 1, DGCNN_EINVAL, "dgcnn_bn1_bwd_reduce_max_f32: relu must be 0 or 1 (got %d)", relu);
   DG_REQUIRE(F % 4 == 0 && lddo % 4 == 0 && a16(T) && a16(dout) && a16(mean) && a16(rstd) && a16(beta), DGCNN_EINVAL,
              "dgcnn_bn1_bwd_reduce_max_f32: float4-loadable operands required");
   const int FV = F / 4;
@@ -344,6 +346,7 @@ extern "C" int dgcnn_bn1_bwd_apply_planes_f32(const float* T, int64_t R, int F, 
                                               float* dbeta, float dbeta_beta, void* stream) {
   DG_REQUIRE(T && mean && rstd && beta && dout && red && maxbits && planes && scale_dev && R > 0 && F > 0, DGCNN_EINVAL,
              "dgcnn_bn1_bwd_apply_planes_f32: bad args");
+  DG_REQUIRE(relu == 0 || relu == 1, DGCNN_EINVAL, "dgcnn_bn1_bwd_apply_planes_f32: relu must be 0 or 1 (got %d)", relu);
   DG_REQUIRE(fmt == DGCNN_PLANES_F16X2, DGCNN_EINVAL, "dgcnn_bn1_bwd_apply_planes_f32: unknown format %d", fmt);
   DG_REQUIRE(F % 8 == 0 && lddo % 4 == 0 && a16(T) && a16(dout) && a16(planes) && plane_stride % 16 == 0 && rows_alloc % 64 == 0 &&
                  rows_alloc >= R && (!dT || a16(dT)), DGCNN_EINVAL, "dgcnn_bn1_bwd_apply_planes_f32: F %% 8, aligned operands required");

@@ -373,8 +373,11 @@ int dgcnn_bn_bwd_reduce_f32(const float* Y, int64_t R, int k, int F,
 /* backward, pass 2: dY = rstd*(dZ - red0/cnt - xhat*red1/cnt) written to dY (may alias Y);
  * dbeta[f] (+)= red0 ; dYsum[r][f] = sum_m dY (optional, feeds the centre dgrad).
  * `red` is reduced over its slots in place (slot 0 then holds the totals).
- * relu: bit 0 = the layer has a ReLU; bit 1 (value 2, k > 1 only) = dY is written as bf16 VALUES (nearest even, stored as fp32)
- * and dYsum adds those: the operand rounding of the bf16 edge-MLP's gradient products, done once where dY is formed. */
+ * relu: bit 0 = the layer has a ReLU; bit 1 (value 2) = dY is written as bf16 VALUES (nearest even, stored as fp32)
+ * and dYsum adds those: the operand rounding of the bf16 edge-MLP's gradient products, done once where dY is formed.
+ * Bit 1 exists in dgcnn_bn_bwd_apply_f32 and dgcnn_edge_bn_bwd_apply_f32 only (any k), which take relu in 0 .. 3; every
+ * other entry point with a `relu` argument (forward, reduce, deterministic reduce, dropout-fused and plane-writing passes)
+ * takes 0 or 1 and returns DGCNN_EINVAL otherwise, so that a reduce and an apply can never disagree about the ReLU. */
 int dgcnn_bn_bwd_apply_f32(const float* Y, int64_t R, int k, int F,
                            const float* mean, const float* rstd, const float* beta, int relu,
                            const float* dmax, int64_t lddmax, const float* dmean, int64_t lddmean,

@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from dgcnn import _hip as H, _planes as P, _engine as E
+from gpu_helpers import planes_to_host as _planes_to_host
 
 pytestmark = pytest.mark.gpu
 
@@ -12,20 +13,6 @@ pytestmark = pytest.mark.gpu
 def _rand(shape, seed, scale=1.0):
     rng = np.random.default_rng(seed)
     return (rng.standard_normal(shape) * scale).astype(np.float32)
-
-
-def _planes_to_host(ps):
-    """Reassemble the fp32 values a plane set represents (sum of its planes), on the host."""
-    npl = P.NPLANES[ps.fmt]
-    raw = ps.buf.cpu().numpy().reshape(npl, -1)
-    out = np.zeros((ps.rows, ps.cols), np.float64)
-    for p in range(npl):
-        a = raw[p].view(np.uint16).reshape(-1, ps.ra, 8)
-        v = a.view(np.float16).astype(np.float32)
-        o0 = ps.c0 // 8
-        blk = v[o0:o0 + ps.cols // 8]                         # (noct, ra, 8)
-        out += blk.transpose(1, 0, 2).reshape(ps.ra, -1)[:ps.rows].astype(np.float64)
-    return out / (1.0 if ps.scale is None else float(ps.scale))
 
 
 @pytest.mark.parametrize("rows,cols", [(64, 8), (100, 64), (1000, 200), (513, 1728)])
