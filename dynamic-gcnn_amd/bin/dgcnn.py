@@ -2,6 +2,7 @@
 """Command-line front end (reference bin/dgcnn.py): `dgcnn.py {train,inference,iotest} [options]`.
 For N GPUs launch one process per GPU:
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bin/dgcnn.py train ...
+A variable-N source with more than one cloud per micro-step: `--pack_towers 1` (clouds of different sizes run as one packed tower).
 """
 import os
 import sys

@@ -800,21 +800,24 @@ extern "C" int dgcnn_colmax_decode_f32(const void* keys, int64_t n, float* vals,
   return dg::check_launch("dgcnn_colmax_decode_f32");
 }
 
-extern "C" int dgcnn_gemm_f32(int transA, int transB, int M, int N, int K,
-                              const float* A, int64_t lda, const float* B, int64_t ldb,
-                              float* C, int64_t ldc, float beta,
-                              const float* gbias, int64_t ldgbias, int rows_per_group,
-                              double* stats, void* colmax_keys, int colmax_rows_per_group,
-                              void* ws, size_t ws_bytes, void* stream) {
+// dgcnn_gemm_f32 and dgcnn_gemm_seg_f32: the per-group bias row comes from rows_per_group (dense towers) or from the row -> cloud
+// map row_group (packed towers); everything else -- kernel choice, tiles, split-K -- is the same function of the shapes
+static int gemm_f32_impl(int transA, int transB, int M, int N, int K,
+                         const float* A, int64_t lda, const float* B, int64_t ldb,
+                         float* C, int64_t ldc, float beta,
+                         const float* gbias, int64_t ldgbias, int rows_per_group, const int32_t* row_group,
+                         double* stats, void* colmax_keys, int colmax_rows_per_group,
+                         void* ws, size_t ws_bytes, void* stream) {
   DG_REQUIRE(A && B && C, DGCNN_EINVAL, "dgcnn_gemm_f32: null pointer");
   DG_REQUIRE(M > 0 && N > 0 && K > 0, DGCNN_EINVAL, "dgcnn_gemm_f32: bad shape %d %d %d", M, N, K);
   DG_REQUIRE(!(transA && transB), DGCNN_EUNSUP, "dgcnn_gemm_f32: transA && transB unsupported");
-  DG_REQUIRE(!gbias || rows_per_group > 0, DGCNN_EINVAL, "dgcnn_gemm_f32: rows_per_group");
+  DG_REQUIRE(!gbias || rows_per_group > 0 || row_group, DGCNN_EINVAL, "dgcnn_gemm_f32: rows_per_group");
   GemmP p = {};
   p.stat_slots = dg::stat_slots();
   p.A = A; p.lda = lda; p.B = B; p.ldb = ldb; p.C = C; p.ldc = ldc;
   p.M = M; p.N = N; p.K = K; p.beta = beta;
   p.gbias = gbias; p.ldgbias = ldgbias; p.rpg = rows_per_group > 0 ? rows_per_group : 1;
+  p.row_group = gbias ? row_group : nullptr;
   p.stats = stats;
   p.splits = 1; p.kchunk = K;
   DG_REQUIRE(!colmax_keys || (colmax_rows_per_group > 0 && colmax_rows_per_group % 256 == 0 && !transA && N > 4), DGCNN_EUNSUP,
@@ -870,6 +873,27 @@ extern "C" int dgcnn_gemm_f32(int transA, int transB, int M, int N, int K,
   }
   if (transB) return launch<A_ROW, B_COL, E_STORE>(p, st, "dgcnn_gemm_f32(NT)");
   return launch<A_ROW, B_ROW, E_STORE>(p, st, "dgcnn_gemm_f32(NN)");
+}
+
+extern "C" int dgcnn_gemm_f32(int transA, int transB, int M, int N, int K,
+                              const float* A, int64_t lda, const float* B, int64_t ldb,
+                              float* C, int64_t ldc, float beta,
+                              const float* gbias, int64_t ldgbias, int rows_per_group,
+                              double* stats, void* colmax_keys, int colmax_rows_per_group,
+                              void* ws, size_t ws_bytes, void* stream) {
+  return gemm_f32_impl(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, beta, gbias, ldgbias, rows_per_group, nullptr,
+                       stats, colmax_keys, colmax_rows_per_group, ws, ws_bytes, stream);
+}
+
+extern "C" int dgcnn_gemm_seg_f32(int transA, int transB, int M, int N, int K,
+                                  const float* A, int64_t lda, const float* B, int64_t ldb,
+                                  float* C, int64_t ldc, float beta,
+                                  const float* gbias, int64_t ldgbias, const int32_t* row_group,
+                                  double* stats, void* ws, size_t ws_bytes, void* stream) {
+  DG_REQUIRE(!gbias || row_group, DGCNN_EINVAL, "dgcnn_gemm_seg_f32: a per-cloud bias needs the row -> cloud map");
+  DG_REQUIRE(!(gbias && transA), DGCNN_EUNSUP, "dgcnn_gemm_seg_f32: bias with transA unsupported");
+  return gemm_f32_impl(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, beta, gbias, ldgbias, 0, row_group,
+                       stats, nullptr, 0, ws, ws_bytes, stream);
 }
 
 // Row tiles of the dgcnn_gemm_f32 launch with these operands (transA = 0), i.e. how many workgroups add column sums into a `stats`

@@ -23,6 +23,9 @@ struct GemmP {
   int M, N, K;
   float beta;
   const float* gbias; int64_t ldgbias; int rpg;
+  // packed towers (clouds of different sizes): the bias row of output row r is gbias[row_group[r]] instead of gbias[r / rpg]
+  // (dgcnn_gemm_seg_f32); nullptr everywhere else
+  const int32_t* row_group;
   double* stats;
   // edge sources / scatter
   const float* x; int64_t ldx; const int32_t* idx; int npts; int cch; int knn;
@@ -131,12 +134,14 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, f32x16 (&acc)[TM][
   const int64_t ldo = split ? (int64_t)p.N : p.ldc;
   const bool vec_st = VEC && p.cvec && (gcol + 3 < p.N);
   const int rlast = imin(m0 + BM, p.M) - 1;
-  const bool gb_uniform = has_gb && ((m0 / p.rpg) == (rlast / p.rpg));
+  const int32_t* rgrp = p.row_group;
+  const int gfirst = !has_gb ? 0 : rgrp ? rgrp[m0] : m0 / p.rpg;
+  const bool gb_uniform = has_gb && (gfirst == (rgrp ? rgrp[rlast] : rlast / p.rpg));
   float gbu[4] = {0.f, 0.f, 0.f, 0.f};
   if (gb_uniform && col_ok) {
 #pragma unroll
     for (int q = 0; q < 4; ++q)
-      if (gcol + q < p.N) gbu[q] = p.gbias[(int64_t)(m0 / p.rpg) * p.ldgbias + gcol + q];
+      if (gcol + q < p.N) gbu[q] = p.gbias[(int64_t)gfirst * p.ldgbias + gcol + q];
   }
   float cs[4] = {0.f, 0.f, 0.f, 0.f}, cq[4] = {0.f, 0.f, 0.f, 0.f};
   float cmx[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
@@ -165,7 +170,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, f32x16 (&acc)[TM][
 #pragma unroll
               for (int q = 0; q < 4; ++q) v[q] += gbu[q];
             } else {
-              const float* gb = p.gbias + (int64_t)(grow / p.rpg) * p.ldgbias + gcol;
+              const float* gb = p.gbias + (int64_t)(rgrp ? rgrp[grow] : grow / p.rpg) * p.ldgbias + gcol;
               if (p.gbvec && gcol + 3 < p.N) {
                 const float4 g4 = *reinterpret_cast<const float4*>(gb);
                 v[0] += g4.x; v[1] += g4.y; v[2] += g4.z; v[3] += g4.w;

@@ -510,8 +510,8 @@ KNN_SEED = os.environ.get("DGCNN_KNN_SEED", "1") != "0"   # seed a layer's k-NN 
 
 class Segments(object):
     """A packed tower: nseg clouds of different sizes concatenated row-wise, cloud b = rows [offsets[b], offsets[b + 1]).  Holds the
-    host offsets (validated here, before any device work), their device copy (made once, on first use) and the smallest / largest
-    cloud, from which the k-NN picks its kernel forms."""
+    host offsets (validated here, before any device work), their device copy and the row -> cloud map row_group[r] = b (each made
+    once, on the host, on first use) and the smallest / largest cloud, from which the k-NN picks its kernel forms."""
 
     def __init__(self, offsets, rows=None):
         if isinstance(offsets, torch.Tensor):
@@ -532,6 +532,7 @@ class Segments(object):
         self.rows = int(off[-1])
         self.min_n, self.max_n = int(sizes.min()), int(sizes.max())
         self._dev = None
+        self._rg = None
 
     def check_k(self, k):
         if k <= 0 or k > self.min_n:
@@ -541,6 +542,13 @@ class Segments(object):
         if self._dev is None or self._dev.device != dev:
             self._dev = torch.from_numpy(self.host.astype(np.int32)).to(dev)
         return self._dev
+
+    def row_group(self, dev):
+        """int32[rows] on the device: the cloud of every tower row (the per-cloud bias of FC0, tf.tile)."""
+        if self._rg is None or self._rg.device != dev:
+            rg = np.repeat(np.arange(self.nseg, dtype=np.int32), np.diff(self.host))
+            self._rg = torch.from_numpy(rg).to(dev)
+        return self._rg
 
 
 def knn(x2d, B, N, k, seed=None, seg=None):
@@ -626,13 +634,18 @@ def _gemm_tag(M, N, K, transA, transB, A, Bm, colmax_rpg=0):
     return "gemm_kernel<%s,%s,STORE,%d,%d>" % ("A_COL" if transA else "A_ROW", "B_COL" if transB else "B_ROW", _tile_m(M, N), bn)
 
 
-def gemm(A, Bm, C, transA=False, transB=False, beta=0.0, gbias=None, rpg=0, stats=None, arith=None, colmax=None, colmax_rpg=0):
+def gemm(A, Bm, C, transA=False, transB=False, beta=0.0, gbias=None, rpg=0, stats=None, arith=None, colmax=None, colmax_rpg=0,
+         row_group=None):
     """C (+)= op(A) op(B); shapes are those of the stored matrices.  arith: arithmetic of THIS product (None = the
-    process-wide setting; 1 = plain bf16 operands: measurements only, not fp32 class)."""
+    process-wide setting; 1 = plain bf16 operands: measurements only, not fp32 class).
+    row_group: int32[M] row -> cloud map of a packed tower: the bias row of output row r is gbias[row_group[r]] (dgcnn_gemm_seg_f32;
+    no colmax -- a row tile may straddle clouds)."""
     if arith is not None and arith != H.gemm_arith():
         prev = H.gemm_arith()
         H.set_gemm_arith(arith)
         try:
+            if row_group is not None:
+                return gemm(A, Bm, C, transA, transB, beta, gbias, rpg, stats, None, colmax, colmax_rpg, row_group=row_group)
             return gemm(A, Bm, C, transA, transB, beta, gbias, rpg, stats, None, colmax, colmax_rpg)
         finally:
             H.set_gemm_arith(prev)
@@ -643,6 +656,16 @@ def gemm(A, Bm, C, transA=False, transB=False, beta=0.0, gbias=None, rpg=0, stat
     assert K == Kb and tuple(C.shape) == (M, N), (A.shape, Bm.shape, C.shape, transA, transB)
     ws = ctx().workspace()
     tag = _gemm_tag(M, N, K, transA, transB, A, Bm, colmax_rpg if colmax is not None else 0)
+    if row_group is not None:
+        if colmax is not None:
+            raise ValueError("gemm: the column-maximum epilogue does not take a packed tower")
+        if row_group.dtype != torch.int32 or row_group.numel() != M or not row_group.is_contiguous():
+            raise ValueError("gemm: row_group must be a contiguous int32[%d]" % M)
+        H.call("dgcnn_gemm_seg_f32", int(transA), int(transB), M, N, K, A.data_ptr(), H.ld2(A), Bm.data_ptr(), H.ld2(Bm),
+               C.data_ptr(), H.ld2(C), float(beta), H._p(gbias), 0 if gbias is None else H.ld2(gbias), row_group.data_ptr(),
+               H._p(stats), ws.data_ptr(), ws.numel(), tag=tag, work=2.0 * M * N * K,
+               nbytes=4.0 * (M * K + K * N + (2 if beta != 0.0 else 1) * M * N))
+        return
     H.call("dgcnn_gemm_f32", int(transA), int(transB), M, N, K, A.data_ptr(), H.ld2(A), Bm.data_ptr(), H.ld2(Bm),
            C.data_ptr(), H.ld2(C), float(beta), H._p(gbias), 0 if gbias is None else H.ld2(gbias), int(rpg),
            H._p(stats), H._p(colmax), int(colmax_rpg), ws.data_ptr(), ws.numel(), tag=tag, work=2.0 * M * N * K,
@@ -677,6 +700,15 @@ def bn_bwd_reduce(Y, R, k, F, mean, rstd, beta, relu, dmx, dmn, mx, cnt, red, ta
                H._p(cnt), red.data_ptr(), tag=tag, work=work)
 
 
+def seg_colsum(x, seg, out):
+    """out (nseg, F) <- the column sums of every cloud of the packed tower x (rows, F): tf.tile^T, summed in a fixed order."""
+    R, F = x.shape
+    ws = ctx().workspace()
+    H.call("dgcnn_seg_colsum_f32", x.data_ptr(), H.ld2(x), R, F, seg.device(x.device).data_ptr(), seg.nseg, out.data_ptr(),
+           ws.data_ptr(), ws.numel(), tag="seg_colsum_kernel", work=4.0 * R * F)
+    return out
+
+
 def bn_finalize(stats, F, count):
     dev = stats.device
     mr = torch.empty((2, F), dtype=torch.float32, device=dev)
@@ -689,7 +721,7 @@ def bn_finalize(stats, F, count):
 # dgcnn/ops.py:62-70,125-133,153-160 ; dgcnn/model.py:46-53,65-72,94-101
 # ----------------------------------------------------------------------------------------------
 def conv_bn_act(x, leaf_scope, num_outputs, relu=True, out=None, out2=None, gbias=None, rpg=0, w_rows=None, arith=None,
-                plane_out=None, f32_out=True, gmax=None, drop_keep=None):
+                plane_out=None, f32_out=True, gmax=None, drop_keep=None, seg=None):
     """x: (R,Cin) view.  Variables `<scope>/weights` [Cin(+extra), Cout], `<scope>/BatchNorm/beta`.
     w_rows: (lo, hi) row range of the weight that multiplies x (FC0 with the folded global feature).
     Returns the (R,Cout) output (a fresh tracked buffer unless `out` is given).
@@ -698,9 +730,17 @@ def conv_bn_act(x, leaf_scope, num_outputs, relu=True, out=None, out2=None, gbia
     names the tensor and carries its gradient); gmax = (B, N): also return the per-cloud max over the points of the output
     (model.py:76-77), taken on the GEMM output and normalised afterwards (BN + ReLU are monotone).
     drop_keep: tf.nn.dropout(out, drop_keep) behind the layer (model.py:90-91), fused into the BatchNorm passes where the
-    kernels allow it (the returned tensor is the DROPPED output either way)."""
+    kernels allow it (the returned tensor is the DROPPED output either way).
+    seg: a packed tower (Segments; x holds its seg.rows rows).  BatchNorm runs over all rows as in a dense tower; what is per
+    cloud goes through the segmented kernels (csrc/seg.hip): gbias is (nseg, Cout) and is addressed through the row -> cloud map
+    (rpg is ignored), its gradient is the per-cloud column sum, gmax (any value but None) is the max-pool over each cloud's own
+    rows -- always the separate pass over the GEMM output, never the epilogue.  The plane mode is NOT packed: a packed tower
+    runs the fp32-class GEMMs (bf16-split / fp32 MFMA) even when HEAD_PLANES is set."""
     c = ctx()
     R, Cin = x.shape
+    if seg is not None and seg.rows != R:
+        raise ValueError("offsets end at %d, the tower has %d rows" % (seg.rows, R))
+    rgrp = seg.row_group(x.device) if (seg is not None and gbias is not None) else None
     with variable_scope(leaf_scope):
         if w_rows is None:
             wname, W = c.get_variable("weights", (Cin, num_outputs))
@@ -716,13 +756,17 @@ def conv_bn_act(x, leaf_scope, num_outputs, relu=True, out=None, out2=None, gbia
     c.push_slots((H.load().dgcnn_gemm_stat_writers(0, R, F, Cin, x.data_ptr(), H.ld2(x), Wx.data_ptr(), H.ld2(Wx)) or c.step_slots)
                  if arith is None else c.step_slots)
     st = c.stats(F)
-    use_pl = arith is None and planes_ok(R, Cin, F)
+    use_pl = arith is None and seg is None and planes_ok(R, Cin, F)
     xp = None
     # the per-cloud column maximum (model.py:76-77), when asked for, comes out of the GEMM's epilogue as packed (value, first row)
     # keys -- every row tile must lie inside one cloud: clouds of a multiple of 256 points (the library then runs no 192-row tile,
     # gemm.hip:launch<>); otherwise a separate pass over T below
     keys = None
-    if gmax is not None and gmax[1] % 256 == 0 and gmax[0] * gmax[1] == R and F > 4:
+    if seg is not None:
+        plane_out, f32_out = None, True
+        if gmax is not None:
+            keys = c.stats_raw(seg.nseg * F)                                   # zeroed uint64[nseg][F], filled by the pass below
+    elif gmax is not None and gmax[1] % 256 == 0 and gmax[0] * gmax[1] == R and F > 4:
         keys = c.stats_raw(gmax[0] * F)                                    # zeroed uint64[B][F]
     if use_pl:
         c.ensure_plane_scales(R)
@@ -733,7 +777,13 @@ def conv_bn_act(x, leaf_scope, num_outputs, relu=True, out=None, out2=None, gbia
         PL.gemm(PL.KC, xp, wt, T, gbias=gbias, rpg=rpg, stats=st, colmax=keys, colmax_rpg=0 if keys is None else gmax[1])
     else:
         plane_out, f32_out = None, True
-        gemm(x, Wx, T, gbias=gbias, rpg=rpg, stats=st, arith=arith, colmax=keys, colmax_rpg=0 if keys is None else gmax[1])
+        if seg is not None:
+            gemm(x, Wx, T, gbias=gbias, stats=st, arith=arith, row_group=rgrp)
+            if gmax is not None:
+                H.call("dgcnn_colmax_seg_f32", T.data_ptr(), H.ld2(T), R, F, seg.device(x.device).data_ptr(), seg.nseg,
+                       keys.data_ptr(), tag="colmax_seg_kernel", work=4.0 * R * F)
+        else:
+            gemm(x, Wx, T, gbias=gbias, rpg=rpg, stats=st, arith=arith, colmax=keys, colmax_rpg=0 if keys is None else gmax[1])
     mean, rstd = bn_finalize(st, F, R)
     c.pop_slots()
     if out is None:
@@ -792,7 +842,10 @@ def conv_bn_act(x, leaf_scope, num_outputs, relu=True, out=None, out2=None, gbia
                     gemm(x, dT, dWx, transA=True, beta=1.0, arith=arith)      # weight gradient behind it, on the side stream
                 if dgb is not None:
                     tmp = torch.empty_like(gbias)
-                    H.call("dgcnn_group_colsum_f32", dT.data_ptr(), H.ld2(dT), gbias.shape[0], rpg, F, tmp.data_ptr())
+                    if seg is not None:
+                        seg_colsum(dT, seg, tmp)
+                    else:
+                        H.call("dgcnn_group_colsum_f32", dT.data_ptr(), H.ld2(dT), gbias.shape[0], rpg, F, tmp.data_ptr())
                     H.call("dgcnn_axpby_f32", tmp.data_ptr(), 1.0, dgb.data_ptr(), 1.0, tmp.numel())
                 return
             if use_pl:
@@ -847,7 +900,10 @@ def conv_bn_act(x, leaf_scope, num_outputs, relu=True, out=None, out2=None, gbia
                 gemm(x, dT, dWx, transA=True, beta=1.0, arith=arith)   # dW += x^T dT
             if dgb is not None:                                         # tf.tile^T: sum over the cloud
                 tmp = torch.empty_like(gbias)
-                H.call("dgcnn_group_colsum_f32", dT.data_ptr(), H.ld2(dT), gbias.shape[0], rpg, F, tmp.data_ptr())
+                if seg is not None:
+                    seg_colsum(dT, seg, tmp)
+                else:
+                    H.call("dgcnn_group_colsum_f32", dT.data_ptr(), H.ld2(dT), gbias.shape[0], rpg, F, tmp.data_ptr())
                 H.call("dgcnn_axpby_f32", tmp.data_ptr(), 1.0, dgb.data_ptr(), 1.0, tmp.numel())
         c.tape.append(bwd)
     if gmax is None:
@@ -856,7 +912,7 @@ def conv_bn_act(x, leaf_scope, num_outputs, relu=True, out=None, out2=None, gbia
         return out
     # model.py:76-77 max_pool over the points of each cloud, on the GEMM output: z = relu((t - mean) rstd + beta) is
     # non-decreasing in t, so max_n z[n] = z(max_n t[n]) and the first arg-max of t is an arg-max of z
-    Bc, Nc = gmax
+    Bc, Nc = (seg.nseg, 0) if seg is not None else gmax
     graw = torch.empty((Bc, F), dtype=torch.float32, device=x.device)
     arg = torch.empty((Bc, F), dtype=torch.int32, device=x.device)
     if keys is not None:
@@ -871,7 +927,11 @@ def conv_bn_act(x, leaf_scope, num_outputs, relu=True, out=None, out2=None, gbia
             dg_, dout = c.grad(g), c.grad(out)
             if dg_ is None or dout is None:
                 return
-            H.call("dgcnn_global_max_bwd_f32", dg_.data_ptr(), arg.data_ptr(), Bc, Nc, F, dout.data_ptr(), H.ld2(dout))
+            if seg is not None:
+                H.call("dgcnn_global_max_bwd_seg_f32", dg_.data_ptr(), arg.data_ptr(), seg.device(x.device).data_ptr(), Bc, F,
+                       dout.data_ptr(), H.ld2(dout))
+            else:
+                H.call("dgcnn_global_max_bwd_f32", dg_.data_ptr(), arg.data_ptr(), Bc, Nc, F, dout.data_ptr(), H.ld2(dout))
         c.tape.append(bwd_g)
     return out, g
 
@@ -1349,28 +1409,58 @@ def dropout(x, keep=DROPOUT_KEEP):
     return out
 
 
-def tile_rows(g, out, rows):
+def tile_rows(g, out, rows, seg=None):
     """tf.tile of a per-cloud (B,F) tensor over the `rows` points of its cloud into the (B*rows, F) view `out` (model.py:80-81);
-    backward: tf.tile^T = the sum over the cloud."""
+    backward: tf.tile^T = the sum over the cloud.  seg: a packed tower (Segments): row r receives the row of its own cloud
+    (`rows` is ignored)."""
     c = ctx()
     G, F = g.shape
-    H.call("dgcnn_tile_rows_f32", g.data_ptr(), H.ld2(g), G, int(rows), F, out.data_ptr(), H.ld2(out))
+    if seg is not None:
+        if G != seg.nseg or out.shape[0] != seg.rows:
+            raise ValueError("tile_rows: %d clouds / %d rows for a packed tower of %d / %d" % (G, out.shape[0], seg.nseg, seg.rows))
+        H.call("dgcnn_tile_rows_seg_f32", g.data_ptr(), H.ld2(g), seg.row_group(g.device).data_ptr(), seg.rows, F, out.data_ptr(),
+               H.ld2(out))
+    else:
+        H.call("dgcnn_tile_rows_f32", g.data_ptr(), H.ld2(g), G, int(rows), F, out.data_ptr(), H.ld2(out))
     if c.recording:
         def bwd():
             dout, dg_ = c.grad(out), c.grad(g)
             if dout is None or dg_ is None:
                 return
             tmp = torch.empty((G, F), dtype=torch.float32, device=g.device)
-            H.call("dgcnn_group_colsum_f32", dout.data_ptr(), H.ld2(dout), G, int(rows), F, tmp.data_ptr())
+            if seg is not None:
+                seg_colsum(dout, seg, tmp)
+            else:
+                H.call("dgcnn_group_colsum_f32", dout.data_ptr(), H.ld2(dout), G, int(rows), F, tmp.data_ptr())
             H.call("dgcnn_copy2d_f32", tmp.data_ptr(), F, dg_.data_ptr(), H.ld2(dg_), G, F, 1)
         c.tape.append(bwd)
     return out
 
 
-def global_max(x, B, N):
-    """(B*N,F) -> (B,F) max over the points of each cloud, first arg-max remembered for the backward."""
+def global_max(x, B, N, seg=None):
+    """(B*N,F) -> (B,F) max over the points of each cloud, first arg-max remembered for the backward.
+    seg: a packed tower (Segments; B, N ignored): (rows,F) -> (nseg,F), the max over each cloud's own rows."""
     c = ctx()
     F = x.shape[1]
+    if seg is not None:
+        if x.shape[0] != seg.rows:
+            raise ValueError("offsets end at %d, the tower has %d rows" % (seg.rows, x.shape[0]))
+        B = seg.nseg
+        off = seg.device(x.device)
+        out = c.new_buffer(B, F)
+        arg = torch.empty((B, F), dtype=torch.int32, device=x.device)
+        keys = c.stats_raw(B * F)
+        H.call("dgcnn_colmax_seg_f32", x.data_ptr(), H.ld2(x), seg.rows, F, off.data_ptr(), B, keys.data_ptr())
+        H.call("dgcnn_colmax_decode_f32", keys.data_ptr(), B * F, out.data_ptr(), arg.data_ptr())
+        if c.recording:
+            def bwd_seg():
+                dout = c.grad(out)
+                dx = c.grad(x)
+                if dout is None or dx is None:
+                    return
+                H.call("dgcnn_global_max_bwd_seg_f32", dout.data_ptr(), arg.data_ptr(), off.data_ptr(), B, F, dx.data_ptr(), H.ld2(dx))
+            c.tape.append(bwd_seg)
+        return out
     out = c.new_buffer(B, F)
     arg = torch.empty((B, F), dtype=torch.int32, device=x.device)
     H.call("dgcnn_global_max_f32", x.data_ptr(), H.ld2(x), B, N, F, out.data_ptr(), arg.data_ptr())

@@ -74,6 +74,8 @@ PROTOTYPES = {
     "dgcnn_gemm_f32": [c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_f32,
                        c_vp, c_i64, c_int, c_vp, c_vp, c_int, c_vp, c_sz, c_vp],
     "dgcnn_colmax_decode_f32": [c_vp, c_i64, c_vp, c_vp, c_vp],
+    "dgcnn_gemm_seg_f32": [c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_f32,
+                           c_vp, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp],
     "dgcnn_split_planes_f32": [c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_i64, c_i64, c_vp],
     "dgcnn_planes_scale_f32": [c_vp, c_i64, c_i64, c_int, c_f32, c_vp, c_vp, c_vp],
     "dgcnn_gemm_planes_f32": [c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_f32,
@@ -100,6 +102,11 @@ PROTOTYPES = {
     "dgcnn_global_max_bwd_f32": [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_i64, c_vp],
     "dgcnn_group_colsum_f32": [c_vp, c_i64, c_int, c_int, c_int, c_vp, c_vp],
     "dgcnn_tile_rows_f32": [c_vp, c_i64, c_int, c_int, c_int, c_vp, c_i64, c_vp],
+    "dgcnn_colmax_seg_f32": [c_vp, c_i64, c_int, c_int, c_vp, c_int, c_vp, c_vp],
+    "dgcnn_global_max_bwd_seg_f32": [c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_i64, c_vp],
+    "dgcnn_seg_colsum_workspace_bytes": [c_int, c_int, c_int],
+    "dgcnn_seg_colsum_f32": [c_vp, c_i64, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_sz, c_vp],
+    "dgcnn_tile_rows_seg_f32": [c_vp, c_i64, c_vp, c_int, c_int, c_vp, c_i64, c_vp],
     "dgcnn_dropout_f32": [c_vp, c_vp, c_i64, c_f32, c_u64, c_vp],
     "dgcnn_dropout_dev_f32": [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp],
     "dgcnn_add_relu_f32": [c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_vp, c_i64, c_vp],
@@ -141,7 +148,8 @@ PROTOTYPES = {
     "dgcnn_comm_counters": [c_vp, c_vp],
 }
 
-INT64_RESULTS = ("dgcnn_knn_workspace_bytes", "dgcnn_knn_seg_workspace_bytes", "dgcnn_edge_mlp_bf16_bwd_workspace_bytes")      # byte counts; every other entry point returns an int status
+INT64_RESULTS = ("dgcnn_knn_workspace_bytes", "dgcnn_knn_seg_workspace_bytes", "dgcnn_edge_mlp_bf16_bwd_workspace_bytes",
+                 "dgcnn_seg_colsum_workspace_bytes")      # byte counts; every other entry point returns an int status
 
 _lib = None
 

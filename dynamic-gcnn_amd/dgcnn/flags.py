@@ -55,6 +55,8 @@ _OPTIONS = [
                                                  "product on the bf16 MFMA pipe, fp32 accumulate: BASELINE configs[2])"),
     ("HEAD_PLANES", "-hp", str, None, "ti", "head GEMMs (MergedEdgeConv, FC*) from operand planes written by the BatchNorm passes: "
                                              "0 | f16 (2 fp16 planes, 3 products); default $DGCNN_HEAD_PLANES"),
+    ("PACK_TOWERS", "-pt", _BOOL, False, "ti", "a micro-batch of clouds with different point counts (-np -1 with -mbs > 1) runs as ONE packed "
+                                               "tower (clouds concatenated row-wise, per-cloud neighbours / max-pool) instead of being refused"),
 ]
 
 

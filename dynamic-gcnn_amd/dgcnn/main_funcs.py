@@ -180,21 +180,55 @@ def _tower_array(chunk, what):
     return np.stack(chunk)
 
 
+def _is_ragged(chunk):
+    return not isinstance(chunk, np.ndarray) and len({c.shape[0] for c in chunk}) != 1
+
+
+def _check_packed_k(flags, sizes):
+    """The host check of a packed tower (ops._segments / Segments.check_k), already where the tower is assembled: every
+    layer's k at most the smallest cloud."""
+    kv = flags.KVALUE if isinstance(flags.KVALUE, list) else [flags.KVALUE]
+    for k in kv:
+        if int(k) <= 0 or int(k) > min(sizes):
+            raise ValueError("k_nn: k=%d must be in [1, smallest cloud=%d] (tf.nn.top_k raises otherwise)" % (int(k), min(sizes)))
+
+
 def _micro_batches(flags, h, data, label, weight):
-    """Yield (data_v, label_v, weight_v) tower lists covering this replica's share of the batch."""
+    """Yield (data_v, label_v, weight_v) tower lists covering this replica's share of the batch.
+    PACK_TOWERS: yields (data_v, label_v, weight_v, offsets_v) instead; a chunk that mixes point counts becomes ONE packed tower --
+    data (R, C), label / weight (R,), the clouds concatenated in batch order, offsets_v[t] = [0, n_0, n_0 + n_1, ..., R] -- and
+    a chunk that stacks stays a dense tower with offsets_v[t] = None."""
     lo, hi = parallel.shard_bounds(int(flags.BATCH_SIZE), h.rank, h.world)
     mbs = int(flags.MINIBATCH_SIZE)
+    pack = bool(getattr(flags, "PACK_TOWERS", False))
     at = lo
     while at < hi:
-        dv, lv, wv = [], None if label is None else [], None if weight is None else []
+        dv, lv, wv, ov = [], None if label is None else [], None if weight is None else [], []
         for _ in flags.GPUS:
-            dv.append(_tower_array(data[at:at + mbs], "data"))
-            if lv is not None:
-                lv.append(_tower_array(label[at:at + mbs], "label"))
-            if wv is not None:
-                wv.append(_tower_array(weight[at:at + mbs], "weight"))
+            if pack and _is_ragged(data[at:at + mbs]):
+                sizes = [int(c.shape[0]) for c in data[at:at + mbs]]
+                _check_packed_k(flags, sizes)
+                for what, src, dst in (("label", label, lv), ("weight", weight, wv)):
+                    if dst is not None and [int(np.asarray(a).reshape(-1).shape[0]) for a in src[at:at + mbs]] != sizes:
+                        raise ValueError("clouds of %s in one micro-batch do not match the data's point counts %s" % (what, sizes))
+                ov.append(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64))
+                dv.append(np.concatenate([np.asarray(c) for c in data[at:at + mbs]], 0))
+                if lv is not None:
+                    lv.append(np.concatenate([np.asarray(a).reshape(-1) for a in label[at:at + mbs]]))
+                if wv is not None:
+                    wv.append(np.concatenate([np.asarray(a).reshape(-1) for a in weight[at:at + mbs]]))
+            else:
+                ov.append(None)
+                dv.append(_tower_array(data[at:at + mbs], "data"))
+                if lv is not None:
+                    lv.append(_tower_array(label[at:at + mbs], "label"))
+                if wv is not None:
+                    wv.append(_tower_array(weight[at:at + mbs], "weight"))
             at += mbs
-        yield dv, lv, wv
+        if pack:
+            yield dv, lv, wv, ov
+        else:
+            yield dv, lv, wv
 
 
 def _replica_mean(h, values, local_only=False):
@@ -308,9 +342,11 @@ def train_loop(flags, h):
             losses, accs = [], []
             h.trainer.zero_gradients(h.sess)
             micro = list(_micro_batches(flags, h, data, label, weight))
-            for mi, (dv, lv, wv) in enumerate(micro):
+            for mi, step in enumerate(micro):
+                dv, lv, wv = step[:3]
+                kw = {"offsets": step[3]} if len(step) > 3 else {}         # (PACK_TOWERS: packed towers carry their offsets)
                 # (last: the head's gradient bucket may start its all-reduce under this micro-step's EdgeConv backward)
-                res = h.trainer.accum_gradient(h.sess, dv, lv, wv, summary=p["summarize"], last=(mi == len(micro) - 1))
+                res = h.trainer.accum_gradient(h.sess, dv, lv, wv, summary=p["summarize"], last=(mi == len(micro) - 1), **kw)
                 accs.append(res[1])
                 losses.append(res[2])
             h.trainer.apply_gradient(h.sess)
@@ -368,14 +404,20 @@ def inference_loop(flags, h):
 
         t0 = time.time()
         softmax, losses, accs = [], [], []
-        for dv, lv, wv in _micro_batches(flags, h, data, label, weight):
-            res = h.trainer.inference(h.sess, dv, lv, wv)
+        for step in _micro_batches(flags, h, data, label, weight):
+            dv, lv, wv = step[:3]
+            ov = step[3] if len(step) > 3 else [None] * len(dv)          # (PACK_TOWERS: packed towers carry their offsets)
+            res = h.trainer.inference(h.sess, dv, lv, wv, **({"offsets": ov} if len(step) > 3 else {}))
+            towers = res[:-2] if has_label else res
+            for s, o in zip(towers, ov):
+                if o is None:
+                    softmax.append(s.clone())                 # the engine reuses its buffers every step
+                else:
+                    # a packed tower (1, R, ncls) goes back to one (1, n_b, ncls) array per entry, in batch order: what -mbs 1 yields
+                    softmax += [s[:, int(o[b]):int(o[b + 1])].clone() for b in range(len(o) - 1)]
             if has_label:
-                softmax += [s.clone() for s in res[:-2]]      # the engine reuses its buffers every step
                 accs.append(res[-2])
                 losses.append(res[-1])
-            else:
-                softmax += [s.clone() for s in res]
         loss, acc = _replica_mean(h, losses), _replica_mean(h, accs)
         if not has_label:
             torch.cuda.synchronize()

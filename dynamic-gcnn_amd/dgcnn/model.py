@@ -8,6 +8,11 @@ identical results up to fp32 rounding:
   * the tiled global feature (model.py:80-85: 1024 identical channels for all N points of a cloud)
     is not materialised: FC0 = x_local W[1024:] + (g_cloud W[:1024]) with the second term computed
     once per cloud and added in the GEMM epilogue (distributivity of the 1x1 convolution).
+
+`build(..., offsets=...)` takes a PACKED tower: clouds of different sizes concatenated row-wise into (R, C), cloud b = rows
+[offsets[b], offsets[b + 1]).  Neighbours, the max-pool and the tiled global feature are per cloud (segmented kernels,
+csrc/seg.hip); BatchNorm statistics run over all R rows, as over the B*N rows of a dense tower.  Not packed: the plane mode of
+the head GEMMs (a packed tower runs the fp32-class GEMMs whatever HEAD_PLANES says).
 """
 from __future__ import annotations
 
@@ -15,7 +20,7 @@ from . import _engine as E
 from . import ops
 
 
-def build(point_cloud, flags):
+def build(point_cloud, flags, offsets=None):
     num_edge_conv = int(flags.EDGE_CONV_LAYERS)
     num_edge_filters = flags.EDGE_CONV_FILTERS
     num_fc = int(flags.FC_LAYERS)
@@ -30,10 +35,14 @@ def build(point_cloud, flags):
         print("Unsupported MODEL_NAME: %s" % flags.MODEL_NAME)
         raise NotImplementedError("Unsupported MODEL_NAME: %s" % flags.MODEL_NAME)     # model.py:41-43
 
+    ecf = ops._listify(num_edge_filters, num_edge_conv, "num_filters")
+    seg = None
+    if offsets is not None:
+        # every check of the packed tower -- shape, offsets, each layer's k against the smallest cloud -- on the host, before any launch
+        seg = ops._segments(point_cloud, offsets, ops._listify(k, num_edge_conv, "k"))
     x, B, N = E.as2d(point_cloud)
     R = B * N
     c.configure_slots(R)                                           # (DETERMINISTIC: one writer per statistics slot)
-    ecf = ops._listify(num_edge_filters, num_edge_conv, "num_filters")
     nofc = flags.MODEL_NAME == "residual-dgcnn-nofc"
 
     plan = None
@@ -66,7 +75,7 @@ def build(point_cloud, flags):
     pl_head = False
     if not nofc:
         fcf = ops._listify(num_fc_filters, num_fc, "num_filters")
-        pl_head = (num_fc >= 1 and E.planes_ok(R, 64 * num_edge_conv, 1024) and E.planes_ok(R, ctot, fcf[0]) and ctot % 32 == 0 and
+        pl_head = (seg is None and num_fc >= 1 and E.planes_ok(R, 64 * num_edge_conv, 1024) and E.planes_ok(R, ctot, fcf[0]) and ctot % 32 == 0 and
                    (num_fc < 2 or E.planes_ok(R, fcf[0], fcf[1])))
     if c.flat_param is not None and R >= E.SIDE_STREAM_MIN_ROWS:
         edge_w0, cin = [], x.shape[1]
@@ -89,16 +98,16 @@ def build(point_cloud, flags):
 
     if flags.MODEL_NAME == "dgcnn":
         tensors = ops.repeat_edge_conv(point_cloud, repeat=num_edge_conv, k=k, num_filters=num_edge_filters,
-                                       trainable=is_training, debug=debug, _plan=plan)
+                                       trainable=is_training, debug=debug, _plan=plan, offsets=seg)
     else:
         tensors = ops.repeat_residual_edge_conv(point_cloud, repeat=num_edge_conv, k=k,
                                                 num_filters=num_edge_filters, trainable=is_training,
-                                                debug=debug, _plan=plan)
+                                                debug=debug, _plan=plan, offsets=seg)
 
     E.mark_head_gradients_complete()                               # (backward: the head's gradients are final from here on)
     if nofc:                                                       # model.py:45-58
         last, _, _ = E.as2d(tensors[-1])
-        fin = E.conv_bn_act(last, "Final", num_class, relu=True)
+        fin = E.conv_bn_act(last, "Final", num_class, relu=True, seg=seg)
         return fin.view(B, N, num_class)
 
     fcf = ops._listify(num_fc_filters, num_fc, "num_filters")
@@ -118,14 +127,15 @@ def build(point_cloud, flags):
     else:
         # model.py:65-77: MergedEdgeConv, then the max-pool over the points of each cloud -- taken on the GEMM output (in its
         # epilogue where the tile shape allows) and normalised afterwards: BN + ReLU are non-decreasing
-        merged, g = E.conv_bn_act(merged_in, "MergedEdgeConv", 1024, relu=True, out=big[:, ctot - 1024:], gmax=(B, N))
+        # (a packed tower: always the separate pass, over each cloud's own rows)
+        merged, g = E.conv_bn_act(merged_in, "MergedEdgeConv", 1024, relu=True, out=big[:, ctot - 1024:], gmax=(B, N), seg=seg)
     tensors.append(E.rank4(merged, B, N))                          # model.py:74
 
     if num_fc < 1:
         # model.py:80-101 with no FC layer: concat([tile(g)] + tensors) -> (dropout) -> Final
-        E.tile_rows(g, bigfull[:, :1024], N)                        # model.py:80-81
+        E.tile_rows(g, bigfull[:, :1024], N, seg=seg)               # model.py:80-81
         net = E.dropout(bigfull, E.DROPOUT_KEEP) if is_training else bigfull      # model.py:90-91
-        fin = E.conv_bn_act(net, "Final", num_class, relu=True)    # model.py:94-101
+        fin = E.conv_bn_act(net, "Final", num_class, relu=True, seg=seg)    # model.py:94-101
         return fin.view(B, N, num_class)
 
     # model.py:80-88: concat([tile(g)] + tensors) -> fc.  FC0 is split as described in the docstring.
@@ -139,8 +149,8 @@ def build(point_cloud, flags):
                             plane_out=c.new_planes(R, fcf[0], "act"), f32_out=False)
     else:
         net = E.conv_bn_act(big, "FC0", fcf[0], relu=True, gbias=gb, rpg=N, w_rows=(1024, 1024 + ctot, 1024 + ctot),
-                            drop_keep=keep if num_fc == 1 else None)
+                            drop_keep=keep if num_fc == 1 else None, seg=seg)
     for i in range(1, num_fc):                                     # ops.py:151-160
-        net = E.conv_bn_act(net, "FC%d" % i, fcf[i], relu=True, drop_keep=keep if i == num_fc - 1 else None)
-    fin = E.conv_bn_act(net, "Final", num_class, relu=True)        # model.py:94-101 (BN + ReLU on the logits)
+        net = E.conv_bn_act(net, "FC%d" % i, fcf[i], relu=True, drop_keep=keep if i == num_fc - 1 else None, seg=seg)
+    fin = E.conv_bn_act(net, "Final", num_class, relu=True, seg=seg)        # model.py:94-101 (BN + ReLU on the logits)
     return fin.view(B, N, num_class)                                # model.py:104 squeeze

@@ -156,9 +156,14 @@ class trainval(object):
     def gradients(self):
         return self._ctx.var_grads
 
-    def feed_dict(self, data, label=None, weight=None):
-        """trainval.py:87-95: one entry per tower (GPU) in each list."""
+    def feed_dict(self, data, label=None, weight=None, offsets=None):
+        """trainval.py:87-95: one entry per tower (GPU) in each list.  offsets: one entry per tower as well -- None for a dense
+        tower (MINIBATCH_SIZE, N, C), or the offsets (nseg + 1 ints, a tensor or a Segments) of a PACKED tower: data (R, C) or
+        (1, R, C), label / weight (R,) or (1, R), cloud b = rows [offsets[b], offsets[b + 1])."""
         res = {"data": list(data)}
+        res["offsets"] = [None] * len(res["data"]) if offsets is None else list(offsets)
+        if len(res["offsets"]) != len(res["data"]):
+            raise ValueError("feed_dict: %d data towers but %d offsets entries" % (len(res["data"]), len(res["offsets"])))
         if label is not None:
             res["label"] = list(label)
         if weight is not None:
@@ -175,8 +180,12 @@ class trainval(object):
         t = a if isinstance(a, torch.Tensor) else torch.as_tensor(a)
         return t.to(device=self._ctx.device, dtype=dtype, non_blocking=True).contiguous()
 
-    def _tower(self, data, label, weight, train):
-        """forward (+ backward when train) of one tower; returns (softmax (MBS,N,ncls), scal[loss, acc])."""
+    def _tower(self, data, label, weight, train, offsets=None):
+        """forward (+ backward when train) of one tower; returns (softmax (MBS,N,ncls), scal[loss, acc]).
+        offsets: a packed tower -- softmax (1,R,ncls), loss / accuracy the mean over its R rows (the reduce_mean of
+        trainval.py:52 on a (1, R) tower: the dense value when the clouds are equal-sized)."""
+        if offsets is not None:
+            return self._tower_packed(data, label, weight, train, offsets)
         pts = self._to_dev(data, torch.float32)
         lab = self._to_dev(label, torch.int32)
         wgt = self._to_dev(weight, torch.float32)
@@ -194,20 +203,41 @@ class trainval(object):
             return out
         return self._tower_eager(pts, lab, wgt, train)
 
-    def _wants_graph(self, rows):
+    def _tower_packed(self, data, label, weight, train, offsets):
+        from . import ops
+        shp = tuple(data.shape)
+        # everything the host can check -- the tower's rank, the offsets, every layer's k against the smallest cloud -- before any
+        # transfer or launch
+        seg = ops._segments(data, offsets, ops._listify(self._flags.KVALUE, int(self._flags.EDGE_CONV_LAYERS), "k"))
+        for what, a in (("label", label), ("weight", weight)):
+            if a is not None and (int(np.prod(tuple(a.shape))) != seg.rows or len(tuple(a.shape)) > 2):
+                raise ValueError("a packed tower of %d rows takes %s of shape (R,) or (1, R), got %s" % (seg.rows, what, tuple(a.shape)))
+        pts = self._to_dev(data, torch.float32)
+        if len(shp) == 4:
+            pts = pts[:, :, 0, :]
+        lab = self._to_dev(label, torch.int32)
+        wgt = self._to_dev(weight, torch.float32)
+        return self._tower_body(pts, lab, wgt, train, seg=seg)            # always eager (_wants_graph)
+
+    def _wants_graph(self, rows, packed=False):
         """How a tower over `rows` points is launched: None (eager), "plan" (recorded launch plan) or "graph" (HIP graph)."""
         use = self._use_graph
+        if packed:                        # a packed tower always runs eagerly: a plan / graph bakes one shape in, the offsets change every step
+            return None
         if H.TIMER is not None or not use:
             return None
         if use == "auto":                 # replay pays where the host matters (profiles/r05/launch_modes.txt)
             return "plan" if rows <= PLAN_AUTO_MAX_ROWS else None
         return "plan" if use == "plan" else "graph"
 
-    def _tower_body(self, pts, lab, wgt, train):
+    def _tower_body(self, pts, lab, wgt, train, seg=None):
         c = self._ctx
         c.begin_step()
         c.recording = bool(train)
-        logits = model.build(pts, self._flags)                       # trainval.py:38
+        if seg is not None:
+            logits = model.build(pts, self._flags, offsets=seg)      # (1, R, ncls)
+        else:
+            logits = model.build(pts, self._flags)                   # trainval.py:38
         B, N, ncls = logits.shape
         sm, scal = E.softmax_loss(logits.view(B * N, ncls), None if lab is None else lab.view(-1),
                                   None if wgt is None else wgt.view(-1), want_grad=bool(train))
@@ -401,13 +431,14 @@ class trainval(object):
         res = self.inference(sess, data, label, weight)
         return {"accuracy": float(res[-2]), "loss": float(res[-1])}
 
-    def inference(self, sess, data, label=None, weight=None):
-        """trainval.py:103-108: [softmax_tower0, ..., (accuracy, loss)]."""
-        fd = self.feed_dict(data, label, weight)
+    def inference(self, sess, data, label=None, weight=None, offsets=None):
+        """trainval.py:103-108: [softmax_tower0, ..., (accuracy, loss)].  offsets: feed_dict (packed towers: softmax (1,R,ncls))."""
+        fd = self.feed_dict(data, label, weight, offsets)
         outs, scals = [], []
         for i in range(len(fd["data"])):
             sm, scal = self._tower(fd["data"][i], fd["label"][i] if label is not None else None,
-                                   fd["weight"][i] if weight is not None else None, train=False)
+                                   fd["weight"][i] if weight is not None else None, train=False,
+                                   **({} if fd["offsets"][i] is None else {"offsets": fd["offsets"][i]}))
             outs.append(sm)
             scals.append(scal)
         if label is not None:
@@ -415,16 +446,17 @@ class trainval(object):
             outs += [s[1], s[0]]
         return outs
 
-    def accum_gradient(self, sess, data, label, weight=None, summary=False, last=False):
+    def accum_gradient(self, sess, data, label, weight=None, summary=False, last=False, offsets=None):
         """trainval.py:110-119: [accum_results, accuracy, loss(, summary)]; tower-mean gradient is
         ADDED to the accumulators (sum over micro-steps, trainval.py:79).
         last=True (not in the reference: its averaging happens inside apply_gradient's session run): this is the final
         micro-step before apply_gradient, so the head's share of the gradient bucket may be all-reduced as soon as the head's
-        backward has produced it, underneath the EdgeConv backward (RCCL group registered, one tower per process)."""
+        backward has produced it, underneath the EdgeConv backward (RCCL group registered, one tower per process).
+        offsets: feed_dict (one entry per tower; a packed tower always runs eagerly)."""
         if not self._flags.TRAIN:
             raise NotImplementedError
         c = self._ctx
-        fd = self.feed_dict(data, label, weight)
+        fd = self.feed_dict(data, label, weight, offsets)
         T = len(fd["data"])
         c.head_grads_hook = None
         d0 = fd["data"][0]
@@ -433,7 +465,7 @@ class trainval(object):
         # always travels as [head piece, rest piece] (apply_gradient sends whatever the hook did not), so ranks holding clouds
         # of different sizes (-np -1 -mbs 1) issue identical calls.
         # (a replayed HIP graph cannot carry the RCCL call; eager launches and a launch plan can)
-        eager = self._wants_graph(int(d0.shape[0]) * int(d0.shape[1])) != "graph"
+        eager = self._wants_graph(int(d0.shape[0]) * int(d0.shape[1]), packed=fd["offsets"][0] is not None) != "graph"
         if last and T == 1 and eager and self._split_reduce():
             def hook():
                 c.join_side()                                   # the head's weight-gradient GEMMs (side stream) have landed
@@ -446,7 +478,7 @@ class trainval(object):
         scals = []
         for i in range(T):
             _, scal = self._tower(fd["data"][i], fd["label"][i], fd["weight"][i] if weight is not None else None,
-                                  train=True)
+                                  train=True, **({} if fd["offsets"][i] is None else {"offsets": fd["offsets"][i]}))
             scals.append(scal)
         if T > 1:                                                     # mean over towers, trainval.py:64-73
             H.call("dgcnn_axpby_f32", saved.data_ptr(), 1.0, c.flat_grad.data_ptr(), 1.0 / T, c.flat_grad.numel())

@@ -292,6 +292,15 @@ int dgcnn_gemm_f32(int transA, int transB, int M, int N, int K,
                    double* stats, void* colmax_keys, int colmax_rows_per_group,
                    void* ws, size_t ws_bytes, void* stream);
 int dgcnn_colmax_decode_f32(const void* keys, int64_t n, float* vals, int32_t* arg, void* stream);
+/* dgcnn_gemm_f32 for a PACKED tower (clouds of different sizes concatenated row-wise): the per-cloud bias row of output row r
+ * is gbias[row_group[r]] (row_group: int32[M], the row -> cloud map) instead of gbias[r / rows_per_group].  Same kernels, tiles and
+ * arithmetic as dgcnn_gemm_f32: C equals the product without bias plus that one fp32 add, and the column statistics include the
+ * bias.  No column-maximum epilogue (a row tile may straddle clouds: dgcnn_colmax_seg_f32); no bias with transA.              */
+int dgcnn_gemm_seg_f32(int transA, int transB, int M, int N, int K,
+                       const float* A, int64_t lda, const float* B, int64_t ldb,
+                       float* C, int64_t ldc, float beta,
+                       const float* gbias, int64_t ldgbias, const int32_t* row_group,
+                       double* stats, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- GEMM from PRE-SPLIT operand planes (gemm_pl.hip) -------------------------------------------
  * The same 1x1 convolutions and their dgrad / wgrad (ops.py:62-70,153-160; model.py:65-72) when the
@@ -417,6 +426,25 @@ int dgcnn_group_colsum_f32(const float* x, int64_t ldx, int G, int rows_per_grou
  * feature (the dropout of model.py:90-91 then acts on it element by element); FC0 otherwise folds it into a per-cloud bias */
 int dgcnn_tile_rows_f32(const float* src, int64_t lds, int G, int rows_per_group, int F, float* dst, int64_t ldd,
                         void* stream);
+/* ---- the same per-cloud passes for a PACKED tower (csrc/seg.hip): cloud b = rows [seg_off[b], seg_off[b + 1]) of a row-major
+ * (rows, F) tensor, seg_off = int32[nseg + 1] on the device, strictly increasing from 0 to rows.  Grids are shaped over 64-row
+ * chunks of the tower, cut at the cloud boundaries inside them -- never one workgroup per cloud.
+ *   dgcnn_colmax_seg_f32           keys[b][f] (uint64, caller-zeroed) <- atomicMax(f32_ordered(value) << 32 | ~row-in-cloud): the key
+ *                                  format of dgcnn_gemm_f32's column-maximum epilogue; dgcnn_colmax_decode_f32 -> (max, FIRST arg-max),
+ *                                  (NaN, 0) for an all-NaN column.  Independent of the order in which the atomics land.
+ *   dgcnn_global_max_bwd_seg_f32   dx[seg_off[b] + arg[b][f]][f] += dout[b][f]
+ *   dgcnn_seg_colsum_f32           out[b][f] = sum over the rows of cloud b (tf.tile^T), summed in a fixed order (bit-reproducible);
+ *                                  ws: dgcnn_seg_colsum_workspace_bytes(rows, nseg, F) bytes of scratch, 4-byte aligned
+ *   dgcnn_tile_rows_seg_f32        dst[r][f] = src[row_group[r]][f] (tf.tile; row_group = int32[rows], the row -> cloud map)      */
+int dgcnn_colmax_seg_f32(const float* x, int64_t ldx, int rows, int F, const int32_t* seg_off, int nseg, void* keys,
+                         void* stream);
+int dgcnn_global_max_bwd_seg_f32(const float* dout, const int32_t* arg, const int32_t* seg_off, int nseg, int F,
+                                 float* dx, int64_t lddx, void* stream);
+int64_t dgcnn_seg_colsum_workspace_bytes(int rows, int nseg, int F);
+int dgcnn_seg_colsum_f32(const float* x, int64_t ldx, int rows, int F, const int32_t* seg_off, int nseg, float* out,
+                         void* ws, size_t ws_bytes, void* stream);
+int dgcnn_tile_rows_seg_f32(const float* src, int64_t lds, const int32_t* row_group, int rows, int F, float* dst, int64_t ldd,
+                            void* stream);
 /* tf.nn.dropout(net, keep) (model.py:91): counter-based RNG keyed by (seed, element index) so the
  * backward regenerates the same mask.  y may alias x. */
 int dgcnn_dropout_f32(const float* x, float* y, int64_t n, float keep, uint64_t seed, void* stream);

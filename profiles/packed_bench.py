@@ -4,6 +4,11 @@ one (k = 40): layer 0 on raw coordinates (C = 4; cell grid off, then on for the 
 on 64 features seeded with the previous layer's graph (append-form scan).  Device time from HIP events around the whole sequence of
 calls, after a synchronise; the dense sequence includes its launch gaps.  Every packed result is checked against the dense ones.
 
+Whole step: the same 24 clouds through trainval with BASELINE configs[1]'s model (3 EdgeConv (64, 64, 128), merged 1024, FC (512, 256),
+2 classes, k = 20; C = 4 as a variable-N source delivers) -- ONE packed accum_gradient(offsets=...) against 24 `-mbs 1` calls, both
+launched eagerly, default (deterministic) mode, same event timing.  The two compute different BatchNorm statistics (over the tower
+/ over each cloud), so only the times are compared.
+
     python profiles/packed_bench.py [--reps 20] [--out profiles/packed/bench.txt]
 """
 import argparse
@@ -33,6 +38,37 @@ def timed(fn, reps):
     return a.elapsed_time(b) / reps
 
 
+def whole_step(rng, sizes, off, reps):
+    """One packed training micro-step against 24 one-cloud micro-steps on the same clouds (zero_gradients + accum_gradient; no Adam)."""
+    import dgcnn
+    R = int(off[-1])
+    flags = dgcnn.DGCNN_FLAGS(MODEL_NAME="dgcnn", EDGE_CONV_LAYERS=3, EDGE_CONV_FILTERS=[64, 64, 128], FC_LAYERS=2, FC_FILTERS=[512, 256],
+                              NUM_CLASS=2, KVALUE=20, NUM_CHANNEL=4, LEARNING_RATE=1e-3, TRAIN=True, SEED=1)
+    tv = dgcnn.trainval(flags).initialize()
+    pts = torch.from_numpy(rng.random((R, 4), dtype=np.float32)).cuda()
+    lab = torch.from_numpy(rng.integers(0, 2, R).astype(np.int32)).cuda()
+    clouds = [(pts[off[b]:off[b + 1]][None], lab[off[b]:off[b + 1]][None]) for b in range(len(sizes))]
+
+    def packed():
+        tv.zero_gradients(None)
+        return tv.accum_gradient(None, [pts], [lab], offsets=[off])
+
+    def dense():
+        tv.zero_gradients(None)
+        return [tv.accum_gradient(None, [p], [l]) for p, l in clouds]
+
+    lp = float(packed()[2])
+    ld = float(np.mean([float(r[2]) for r in dense()]))
+    assert np.isfinite(lp) and np.isfinite(ld)
+    tp, td = timed(packed, reps), timed(dense, reps)
+    mode = "deterministic" if E.DETERMINISTIC else "atomics"
+    return ["",
+            "whole training micro-step (configs[1]'s model, C = 4, eager launches, %s mode, %d reps): zero_gradients + accum_gradient" % (mode, reps),
+            "%-34s %12s %12s %8s" % ("", "packed ms", "24 x mbs 1", "ratio"),
+            "%-34s %12.3f %12.3f %8.3f" % ("forward + backward, R = %d" % R, tp, td, tp / td),
+            "(loss of the first step: packed %.4f, mean of the 24 clouds %.4f -- BatchNorm over the tower / over each cloud)" % (lp, ld)]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -45,7 +81,9 @@ def main():
     off = np.concatenate([[0], np.cumsum(sizes)])
     R = int(off[-1])
     seg = E.Segments(off, R)
-    lines = ["clouds: 24, N ~ U[1024, 8192] (rng 0): R = %d rows, min %d, max %d" % (R, seg.min_n, seg.max_n),
+    prop = torch.cuda.get_device_properties(0)
+    lines = ["device: %s (%s, %d CUs), one GPU" % (prop.name or "AMD Instinct", getattr(prop, "gcnArchName", "?"), prop.multi_processor_count),
+             "clouds: 24, N ~ U[1024, 8192] (rng 0): R = %d rows, min %d, max %d" % (R, seg.min_n, seg.max_n),
              "%-34s %12s %12s %8s" % ("layer", "packed ms", "24 dense ms", "ratio")]
     x0 = torch.from_numpy(rng.random((R, 4), dtype=np.float32)).cuda()
     x1 = torch.from_numpy(np.maximum(rng.normal(size=(R, 64)), 0).astype(np.float32)).cuda()
@@ -74,6 +112,7 @@ def main():
             lines.append("%-34s %12.3f %12.3f %8.3f" % ("C=64 k=%d  seeded (append scan)" % k, tp, td, tp / td))
     finally:
         lib.dgcnn_knn_grid(prev_grid)
+    lines += whole_step(rng, sizes, off, max(2, args.reps // 4))
     text = "\n".join(lines)
     print(text)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
