@@ -414,10 +414,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
             else dz = dmx[v];
             if (relu && !(z > 0.f)) dz = 0.f;
             o[v] = rs[v] * (dz - c1[v] - xh * c2[v]);
-            if (round_dy) {
-              const unsigned u = __float_as_uint(o[v]);
-              o[v] = __uint_as_float((u + 0x7fffu + ((u >> 16) & 1u)) & 0xffff0000u);
-            }
+            if (round_dy) o[v] = round_bf16_rne(o[v]);
             acc[v] += o[v];
           }
           Vec<V>::st(dy + (int64_t)(m + b) * F, o);

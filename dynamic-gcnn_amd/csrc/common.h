@@ -97,3 +97,12 @@ __device__ __forceinline__ bool dropout_keeps(uint64_t seed, uint64_t i, uint32_
 __device__ __forceinline__ uint32_t dropout_threshold(float keep) {
   return (keep >= 1.f) ? 0xffffffffu : (uint32_t)((double)keep * 4294967296.0);
 }
+
+// fp32 -> the nearest bf16 value (ties to even), kept as fp32 bits.  The carry of the rounding add would run a NaN whose upper
+// mantissa bits are all ones into the exponent and sign (0x7fffffff -> -0.0): a NaN stays a (quiet) NaN of the same sign instead,
+// as v_cvt_pk_bf16_f32 keeps it.
+__device__ __forceinline__ float round_bf16_rne(float v) {
+  const unsigned u = __float_as_uint(v);
+  const unsigned r = (u + 0x7fffu + ((u >> 16) & 1u)) & 0xffff0000u;
+  return __uint_as_float(((u & 0x7fffffffu) > 0x7f800000u) ? ((u | 0x00400000u) & 0xffff0000u) : r);
+}

@@ -612,8 +612,7 @@ extern "C" int dgcnn_edge_gather_add_f32(const float* V, int64_t ldv, const floa
 // dst = src rounded to bf16 values (nearest even), kept as fp32: the weight operand of the bf16 edge-MLP's point-level gradient products
 __global__ void round_bf16_kernel(const float* __restrict__ src, float* __restrict__ dst, int64_t n) {
   GRID_STRIDE(i, n) {
-    const unsigned u = __float_as_uint(src[i]);
-    dst[i] = __uint_as_float((u + 0x7fffu + ((u >> 16) & 1u)) & 0xffff0000u);
+    dst[i] = round_bf16_rne(src[i]);
   }
 }
 

@@ -135,7 +135,9 @@ int dgcnn_edge_mlp_bf16_bwd(const float* x, int64_t ldx, const int32_t* idx, con
                             size_t ws_bytes, void* stream);
 int dgcnn_edge_gather_sum_bf16(const void* dY, const int32_t* off, const int32_t* rev, int64_t R, int F, float* S, int64_t lds,
                                void* stream);
-/* dst[i] = src[i] rounded to the nearest bf16 value (ties to even), kept as fp32 (weights of the mode's point-level gradient products) */
+/* dst[i] = src[i] rounded to the nearest bf16 value (ties to even), kept as fp32 (weights of the mode's point-level gradient products);
+ * a NaN stays a quiet NaN of its sign (also where the rounding add would carry it into the exponent: 0x7fffffff), as does the
+ * bf16 rounding of dY in dgcnn_bn_bwd_apply_f32 / dgcnn_edge_bn_bwd_apply_f32 (relu bit 1) */
 int dgcnn_round_bf16_f32(const float* src, float* dst, int64_t n, void* stream);
 int dgcnn_edge_mlp_bf16(const float* x, int64_t ldx, const int32_t* idx, const float* W0, int B, int N, int C, int k, int F,
                         float* Y, void* stream);

@@ -159,9 +159,11 @@ def two_pass_stats64(Y):
 
 # ------------------------------------------------------------------------------------------------------------------ replays
 def round_bf16(o):
-    """fp32 -> nearest-even bf16 VALUE stored as fp32 (bn_bwd_apply_kernel: (u + 0x7fff + ((u >> 16) & 1)) & 0xffff0000)."""
+    """fp32 -> nearest-even bf16 VALUE stored as fp32 (common.h:round_bf16_rne: (u + 0x7fff + ((u >> 16) & 1)) & 0xffff0000;
+    a NaN stays a quiet NaN of its sign, (u | 0x00400000) & 0xffff0000, instead of carrying into exponent and sign)."""
     u = f32(o).view(np.uint32).astype(np.uint64)
-    r = ((u + 0x7fff + ((u >> 16) & 1)) & 0xffff0000).astype(np.uint32)
+    r = (u + 0x7fff + ((u >> 16) & 1)) & 0xffff0000
+    r = np.where((u & 0x7fffffff) > 0x7f800000, (u | 0x00400000) & 0xffff0000, r).astype(np.uint32)
     return r.view(F32).reshape(np.shape(o))
 
 

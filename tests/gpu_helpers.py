@@ -138,21 +138,25 @@ def note_ratio(kernel, err, scale, n_terms, factor, record=True):
     assert ratio <= factor, "%s: %.6g > %.6g" % (kernel, ratio, factor)
 
 
-def ratio_table():
-    """Print the table of RATIOS: the rows of every module that has run in this process so far, so the table is complete after
-    the last of them (test_gpu_bn_kernels.py, then test_gpu_planes_bn.py).  Also written to $DGCNN_BN_ERROR_TABLE when set
-    (profiles/bn_kernel_errors.txt is a measured copy of a run of both modules)."""
-    lines = ["# worst |hip - float64| / (2^-24 * sum |term|) per column over the random-input cases of tests/test_gpu_bn_kernels.py and",
+BN_HEADER = ["# worst |hip - float64| / (2^-24 * sum |term|) per column over the random-input cases of tests/test_gpu_bn_kernels.py and",
              "# tests/test_gpu_planes_bn.py; n_terms = terms per column of the case that gave the worst ratio; bound = what the test allows",
              "# (n_terms + 8: any-order fp32 summation plus the roundings inside a term; 4 / 5: the float64-accumulating det kernel;",
-             "# edge_bwd_reduce_points: the summation term plus 4 sum |dz| (|xh| + 2 |beta|), smallest column of that case)",
-             "%-44s %12s %10s %12s" % ("kernel", "worst ratio", "n_terms", "bound")]
-    for name in sorted(RATIOS):
+             "# edge_bwd_reduce_points: the summation term plus 4 sum |dz| (|xh| + 2 |beta|), smallest column of that case)"]
+
+
+def ratio_table(header=None, env="DGCNN_BN_ERROR_TABLE", names=None):
+    """Print the table of RATIOS: the rows of every module that has run in this process so far, so the table is complete after
+    the last of them (test_gpu_bn_kernels.py, then test_gpu_planes_bn.py).  Also written to $DGCNN_BN_ERROR_TABLE when set
+    (profiles/bn_kernel_errors.txt is a measured copy of a run of both modules).  A module with a table of its own passes its
+    header lines, its environment variable and the kernels it recorded (`names`)."""
+    lines = list(BN_HEADER if header is None else header)
+    lines.append("%-44s %12s %10s %12s" % ("kernel", "worst ratio", "n_terms", "bound"))
+    for name in sorted(RATIOS if names is None else names):
         r, n, b = RATIOS[name]
         lines.append("%-44s %12.4g %10d %12.6g" % (name, r, n, b))
     text = "\n".join(lines) + "\n"
     print("\n" + text)
-    path = os.environ.get("DGCNN_BN_ERROR_TABLE")
+    path = os.environ.get(env)
     if path:
         with open(path, "w") as f:
             f.write(text)
