@@ -24,32 +24,6 @@ constexpr int WAVES = 4;
 constexpr int TJ = 128;
 constexpr int PERW = TJ / WAVES;
 
-// Which rows of x a grid row (blockIdx.y = b) searches.  Dense: cloud b = rows [b N, b N + N), indices cloud-local.  Packed tower:
-// cloud b = rows [off[b], off[b + 1]), indices tower rows (off[b] + j), grid cdiv(max_n, 64) x nseg -- a block past its cloud's rows
-// leaves before its first barrier.  Within a cloud the arithmetic is the same: per cloud the packed result is the dense one.
-struct DenseClouds {
-  int N;
-  __host__ __device__ constexpr DenseClouds(int n) : N(n) {}
-  static constexpr bool kPacked = false;
-  __device__ int64_t base(int b) const { return (int64_t)b * N; }
-  __device__ int size(int) const { return N; }
-};
-struct PackedClouds {
-  const int* __restrict__ off;               // nseg + 1 increasing tower rows, off[0] = 0
-  int nseg;
-  static constexpr bool kPacked = true;
-  __device__ int64_t base(int b) const { return off[b]; }
-  __device__ int size(int b) const { return off[b + 1] - off[b]; }
-  __device__ int cloud_of(int64_t row) const {                 // last b with off[b] <= row (row wave-uniform: a scalar loop)
-    int lo = 0, hi = nseg;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (off[mid] <= row) lo = mid; else hi = mid;
-    }
-    return lo;
-  }
-};
-
 // s_i = sequential sum of fl(x^2) over c ascending (the oracle's order: no FMA, no reassociation), one thread per row.
 // 64 rows per block (B*N/64 blocks: 768 at the headline shape -- the round-1 kernel ran 192 blocks of 256 rows, under one
 // block per CU, 24 us at C = 64): the block's rows are staged through LDS with coalesced loads (a thread walking its own
@@ -1485,6 +1459,9 @@ size_t knn_grid_workspace_bytes(int B, int N);
 bool knn_grid_applicable(int C, int k);
 int knn_grid_min_n();
 int launch_knn_grid(const float* x, const float* sq, int B, int N, int C, int64_t ldx, int k, int32_t* idx, void* ws, hipStream_t st);
+size_t knn_grid_seg_workspace_bytes(int rows, int nseg);
+int launch_knn_grid_seg(const float* x, const float* sq, int nseg, const int32_t* seg_off, int rows, int max_n, int C, int64_t ldx, int k,
+                        int32_t* idx, void* ws, hipStream_t st);
 }  // namespace dg
 
 // workspace = [s_i of every row (B*N floats, padded to 256 bytes) | seed bounds (same size) | scratch of the cell-grid search (C <= 4,
@@ -1736,4 +1713,35 @@ extern "C" int dgcnn_knn_seg_f32(const float* x, int64_t ldx, int C, int k, int 
   if (C <= 16) return dispatch_k_packed<16>(x, sq_ws, cl, max_n, C, ldx, k, vec_ok, idx, nullptr, st);
   if (C <= 64) return dispatch_k_packed<64>(x, sq_ws, cl, max_n, C, ldx, k, vec_ok, idx, nullptr, st);
   return dispatch_k_packed<128>(x, sq_ws, cl, max_n, C, ldx, k, vec_ok, idx, nullptr, st);
+}
+
+// ---- packed towers, raw coordinates (C <= 4, k <= 40): the exact cell-grid search of knn_grid.hip with one grid per cloud ---------
+// workspace = [s_i of every tower row (padded to 256 bytes) | sorted records, s_j and original indices of every row, one GridInfo and
+//              one cell table per cloud].  No seed: the grid never used one.  dgcnn_knn_seg_grid_use (knn_grid.hip) is the rule by
+// which a caller chooses between this entry and dgcnn_knn_seg_f32; the indices are the same either way.
+extern "C" int64_t dgcnn_knn_seg_grid_workspace_bytes(int rows, int nseg) {
+  if (rows <= 0 || nseg <= 0) return 0;
+  return (int64_t)(knn_sq_bytes(1, rows) + dg::knn_grid_seg_workspace_bytes(rows, nseg));
+}
+
+extern "C" int dgcnn_knn_seg_grid_f32(const float* x, int64_t ldx, int C, int k, int nseg, const int32_t* seg_off, int rows, int min_n,
+                                      int max_n, int32_t* idx, void* ws, size_t ws_bytes, void* stream) {
+  const char* what = "dgcnn_knn_seg_grid_f32";
+  DG_REQUIRE(x && idx && ws && seg_off, DGCNN_EINVAL, "%s: null pointer", what);
+  DG_REQUIRE(nseg > 0 && nseg <= 65535 && rows > 0 && C > 0 && ldx >= C, DGCNN_EINVAL, "%s: bad shape nseg=%d rows=%d C=%d", what,
+             nseg, rows, C);
+  DG_REQUIRE(C <= 4 && k <= 40, DGCNN_EINVAL, "%s: C=%d k=%d: the cell grid searches raw coordinates (C <= 4) for k <= 40", what, C, k);
+  DG_REQUIRE(min_n > 0 && min_n <= max_n && max_n <= rows && (int64_t)min_n * nseg <= rows && (int64_t)max_n * nseg >= rows,
+             DGCNN_EINVAL, "%s: cloud sizes min_n=%d max_n=%d do not fit %d rows in %d clouds", what, min_n, max_n, rows, nseg);
+  DG_REQUIRE(k > 0 && k <= min_n, DGCNN_EINVAL, "%s: k=%d must be in [1, smallest cloud=%d] (tf.nn.top_k raises otherwise)", what, k,
+             min_n);
+  DG_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0 && ws_bytes >= (size_t)dgcnn_knn_seg_grid_workspace_bytes(rows, nseg),
+             DGCNN_EINVAL, "%s: workspace must be 16-byte aligned and hold dgcnn_knn_seg_grid_workspace_bytes(rows, nseg) bytes (got %zu)",
+             what, ws_bytes);
+  hipStream_t st = (hipStream_t)stream;
+  float* sq_ws = reinterpret_cast<float*>(ws);
+  dg::launch(sqnorm_kernel, dim3((unsigned)dg::cdiv(rows, SQ_ROWS)), dim3(256), sizeof(float) * SQ_ROWS * (C + 1), st, x, ldx,
+             (int64_t)rows, C, sq_ws);
+  return dg::launch_knn_grid_seg(x, sq_ws, nseg, seg_off, rows, max_n, C, ldx, k, idx, reinterpret_cast<char*>(ws) + knn_sq_bytes(1, rows),
+                                 st);
 }

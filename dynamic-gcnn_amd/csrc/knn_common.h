@@ -1,9 +1,36 @@
-// knn_common.h -- lane-mask selects and the register-resident sorted (d, j) list shared by the k-NN kernels (knn.hip, knn_grid.hip).
+// knn_common.h -- the cloud maps (dense / packed tower), lane-mask selects and the register-resident sorted (d, j) list shared by the
+// k-NN kernels (knn.hip, knn_grid.hip).
 #pragma once
 #include "common.h"
 #include <math.h>
 
 namespace {
+
+// Which rows of x a grid row (blockIdx.y = b) searches.  Dense: cloud b = rows [b N, b N + N), indices cloud-local.  Packed tower:
+// cloud b = rows [off[b], off[b + 1]), indices tower rows (off[b] + j), grid cdiv(max_n, 64) x nseg -- a block past its cloud's rows
+// leaves before its first barrier.  Within a cloud the arithmetic is the same: per cloud the packed result is the dense one.
+struct DenseClouds {
+  int N;
+  __host__ __device__ constexpr DenseClouds(int n) : N(n) {}
+  static constexpr bool kPacked = false;
+  __device__ int64_t base(int b) const { return (int64_t)b * N; }
+  __device__ int size(int) const { return N; }
+};
+struct PackedClouds {
+  const int* __restrict__ off;               // nseg + 1 increasing tower rows, off[0] = 0
+  int nseg;
+  static constexpr bool kPacked = true;
+  __device__ int64_t base(int b) const { return off[b]; }
+  __device__ int size(int b) const { return off[b + 1] - off[b]; }
+  __device__ int cloud_of(int64_t row) const {                 // last b with off[b] <= row (row wave-uniform: a scalar loop)
+    int lo = 0, hi = nseg;
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (off[mid] <= row) lo = mid; else hi = mid;
+    }
+    return lo;
+  }
+};
 
 // ---- lane-mask helpers.  hipcc turns nested ?: on register arrays into exec-masked branches (20
 // s_and_saveexec/s_cbranch per insert, measured 10x slower); v_cmp -> SGPR-pair mask -> v_cndmask

@@ -26,6 +26,7 @@
 // Work per query at uniform density: the grid is sized for ~0.8 k points per cell, so ring 1 (27 cells, ~22 k candidates) decides
 // almost every query: 432 pair evaluations instead of 2048 at (24, 2048, 3, 20), 864 instead of 16384 / 65536 at k = 40.
 #include "knn_common.h"
+#include <limits.h>
 #include <stdlib.h>
 
 namespace {
@@ -96,8 +97,13 @@ __device__ __forceinline__ void list_insert64(unsigned long long (&kl)[KC], unsi
   kl[0] = sel_u64(ct, key, kl[0]);
 }
 
+// Clouds (knn_common.h): dense = cloud b is rows [b N, b N + N) and every cloud has the host's G (Gk = G); packed tower = cloud b is rows
+// [off[b], off[b + 1]) of x, of sq and of the sorted arrays, with its own GridInfo[b] and cell table b, and its own G from its own
+// size (Gk = k: the host's formula, launch_grid) -- the stop rule is exact for any grid, so a last-bit difference between the host's and
+// the device's cbrtf moves time, never an index.
+template <class Clouds>
 __global__ __launch_bounds__(1024) void knn_grid_build_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ sq,
-                                                              int N, int C, int G, float4* __restrict__ ps, float* __restrict__ s4,
+                                                              Clouds cl, int C, int Gk, float4* __restrict__ ps, float* __restrict__ s4,
                                                               int32_t* __restrict__ order, int32_t* __restrict__ cell_start,
                                                               GridInfo* __restrict__ info) {
   __shared__ int bins[GMAX * GMAX * GMAX];          // histogram, then cursors
@@ -106,8 +112,15 @@ __global__ __launch_bounds__(1024) void knn_grid_build_kernel(const float* __res
   __shared__ GridInfo gi;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int b = blockIdx.x;
-  const float* xb = x + (int64_t)b * N * ldx;
-  const float* sqb = sq + (int64_t)b * N;
+  const int N = cl.size(b);
+  const int64_t cb = cl.base(b);
+  const float* xb = x + cb * ldx;
+  const float* sqb = sq + cb;
+  int G = Gk;
+  if (Clouds::kPacked) {
+    G = (int)floorf(cbrtf((float)N / (0.1f * (float)Gk)));
+    G = G < 1 ? 1 : (G > GMAX ? GMAX : G);
+  }
   const int D = C < 3 ? C : 3;
   const int G3 = G * G * G;
 
@@ -204,9 +217,9 @@ __global__ __launch_bounds__(1024) void knn_grid_build_kernel(const float* __res
       if (d < C) v[d] = xb[(int64_t)j * ldx + d];
     const float sj = sqb[j];
     if (C <= 3) v[3] = sj;
-    ps[(int64_t)b * N + pos] = make_float4(v[0], v[1], v[2], v[3]);
-    s4[(int64_t)b * N + pos] = sj;
-    order[(int64_t)b * N + pos] = j;
+    ps[cb + pos] = make_float4(v[0], v[1], v[2], v[3]);
+    s4[cb + pos] = sj;
+    order[cb + pos] = j;
   }
 }
 
@@ -214,24 +227,31 @@ __global__ __launch_bounds__(1024) void knn_grid_build_kernel(const float* __res
 // walk is a chain of dependent loads -- cell table -> run bounds -> candidates -- and at (24, 2048) there is less than one wave
 // per SIMD to hide a global round trip behind (262 us with global loads against 155 us for the all-pairs kernel; LDS: see
 // profiles/r04/knn_grid.txt).  Large clouds have thousands of waves and read the records through L1 / L2.
-template <int KC, bool C4, bool LDSC>
+// Packed tower (grid cdiv(max_n, 64 QW) x nseg): a block whose first query is past its cloud leaves before anything else (this form has
+// no barrier: LDSC = false only); the keys keep the cloud-local j, so ties break as in the dense search, which is also the tower-row
+// order; off[b] is added when the indices are written, to the row and to the value.
+template <int KC, bool C4, bool LDSC, class Clouds = DenseClouds>
 __global__ __launch_bounds__(64 * QW) void knn_grid_query_kernel(const float4* __restrict__ ps, const float* __restrict__ s4,
                                                                  const int32_t* __restrict__ order, const int32_t* __restrict__ cell_start,
-                                                                 const GridInfo* __restrict__ info, int N, int k, int32_t* __restrict__ idx) {
+                                                                 const GridInfo* __restrict__ info, Clouds clouds, int k, int32_t* __restrict__ idx) {
+  static_assert(!(LDSC && Clouds::kPacked), "the LDS-copy form is sized per launch: dense towers only");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63, wv = tid >> 6;
   float* dq = reinterpret_cast<float*>(smem) + wv * (PARK * 64);
   int* pj = reinterpret_cast<int*>(smem) + QW * (PARK * 64) + wv * (PARK * 64);
   const int b = blockIdx.y;
+  const int N = clouds.size(b);
+  if (Clouds::kPacked && (int)blockIdx.x * (64 * QW) >= N) return;
   const int q = blockIdx.x * (64 * QW) + tid;
   const bool valid = q < N;
   const int qc = valid ? q : N - 1;
   const GridInfo g = info[b];
   const int G = g.G;
-  const float4* pbg = ps + (int64_t)b * N;
-  const float* sbg = s4 + (int64_t)b * N;
-  const int32_t* obg = order + (int64_t)b * N;
+  const int64_t cb = clouds.base(b);
+  const float4* pbg = ps + cb;
+  const float* sbg = s4 + cb;
+  const int32_t* obg = order + cb;
   const int32_t* csg = cell_start + (int64_t)b * (GMAX * GMAX * GMAX + 1);
   // LDS copies (LDSC): [records float4 N][order int N][cells int G^3 + 1][s_j float N (C4)]
   float4* pl = reinterpret_cast<float4*>(smem + 2 * QW * PARK * 64 * 4);
@@ -367,10 +387,10 @@ __global__ __launch_bounds__(64 * QW) void knn_grid_query_kernel(const float4* _
   }
 
   if (valid) {
-    int32_t* out = idx + ((int64_t)b * N + org(q)) * k;
+    int32_t* out = idx + (cb + org(q)) * k;
 #pragma unroll
     for (int t = 0; t < KC; ++t)
-      if (t < k) out[t] = (int32_t)(unsigned)kl[t];
+      if (t < k) out[t] = Clouds::kPacked ? (int32_t)cb + (int32_t)(unsigned)kl[t] : (int32_t)(unsigned)kl[t];
   }
 }
 
@@ -384,31 +404,17 @@ bool knn_grid_on() {
   return g_knn_grid == 1;
 }
 
-}  // namespace
-
-namespace dg {
-
-size_t knn_grid_workspace_bytes(int B, int N) {
-  const size_t rows = (size_t)B * (size_t)N;
-  return rows * (sizeof(float4) + sizeof(float) + sizeof(int32_t)) + (size_t)B * ((GMAX * GMAX * GMAX + 1) * sizeof(int32_t) + sizeof(GridInfo)) + 256;
+// Both towers share one layout: [records float4 rows][s_j float rows][order int rows] | 64-byte aligned: [GridInfo B][cell table B];
+// a packed tower's cloud b owns the tower rows [off[b], off[b + 1]) of the three row arrays.
+size_t grid_ws_bytes(size_t rows, size_t B) {
+  return rows * (sizeof(float4) + sizeof(float) + sizeof(int32_t)) + B * ((GMAX * GMAX * GMAX + 1) * sizeof(int32_t) + sizeof(GridInfo)) + 256;
 }
 
-// C <= 4, k <= 40.  sq = the s_j of the cloud (already computed); ws >= knn_grid_workspace_bytes(B, N), 16-byte aligned.
-bool knn_grid_applicable(int C, int k) { return knn_grid_on() && C <= 4 && k <= 40; }
-
-// Where it pays (profiles/r04/knn_grid.txt): the walk costs ~22 k candidates per row whatever N is, the all-pairs kernel N.
-// Measured cross-over between N = 2048 (all pairs 155 us, grid 207 us at B = 24: one 64-query wave per SIMD, bound by its own
-// dependent instruction chain) and N = 4096; at N = 16384 / 65536 the grid is 3.1x / 14x faster.  $DGCNN_KNN_GRID_MIN_N moves it
-// (tests run the grid at every N).
-int knn_grid_min_n() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("DGCNN_KNN_GRID_MIN_N"); v = e ? atoi(e) : 4096; }
-  return g_knn_grid_all ? 0 : v;
-}
-
-int launch_knn_grid(const float* x, const float* sq, int B, int N, int C, int64_t ldx, int k, int32_t* idx, void* ws, hipStream_t st) {
+// B clouds of at most max_n points, `rows` in all.  Dense: every cloud has max_n points.
+template <class Clouds>
+int launch_grid(const char* what, const float* x, const float* sq, Clouds cl, int B, int max_n, size_t rows, int C, int64_t ldx, int k,
+                int32_t* idx, void* ws, hipStream_t st) {
   char* w = reinterpret_cast<char*>(ws);
-  const size_t rows = (size_t)B * (size_t)N;
   float4* ps = reinterpret_cast<float4*>(w);
   w += rows * sizeof(float4);
   float* s4 = reinterpret_cast<float*>(w);
@@ -422,26 +428,33 @@ int launch_knn_grid(const float* x, const float* sq, int B, int N, int C, int64_
   // ~0.1 k points per cell (cell edge ~ 0.75 of the radius of a ball holding k points): rings are thin shells, a lane stops within
   // a fraction of a cell of its k-th distance.  Measured against 0.8 k / 0.2 k points per cell (profiles/r04/knn_grid.txt):
   // (8, 16384, 3, 40) 648 / 544 / 386 us, (24, 2048, 3, 20) 191 / 160 / 151 us; finer than that the empty runs cost more than the
-  // pairs they save.  G <= GMAX = 16: clouds of 65536 points stay at 16 points per cell.
-  int G = (int)floorf(cbrtf((float)N / (0.1f * (float)k)));
+  // pairs they save.  G <= GMAX = 16: clouds of 65536 points stay at 16 points per cell.  (A packed tower's build kernel evaluates
+  // the same formula per cloud and gets k instead of G.)
+  int G = (int)floorf(cbrtf((float)max_n / (0.1f * (float)k)));
   G = G < 1 ? 1 : (G > GMAX ? GMAX : G);
-  dg::launch(knn_grid_build_kernel, dim3((unsigned)B), dim3(1024), 0, st, x, ldx, sq, N, C, G, ps, s4, order, cell_start, info);
-  dim3 grid((unsigned)cdiv(N, 64 * QW), (unsigned)B);
+  dg::launch(knn_grid_build_kernel<Clouds>, dim3((unsigned)B), dim3(1024), 0, st, x, ldx, sq, cl, C, Clouds::kPacked ? k : G, ps, s4,
+             order, cell_start, info);
+  dim3 grid((unsigned)dg::cdiv(max_n, 64 * QW), (unsigned)B);
   const size_t park = (size_t)2 * QW * PARK * 64 * 4;
   const size_t G3 = (size_t)G * G * G;
-  const size_t cloud = (size_t)N * (16 + 4 + (C == 4 ? 4 : 0)) + (G3 + 1) * 4;
-  const bool in_lds = N <= LDS_CLOUD_MAX && park + cloud + 16 <= 160 * 1024;
+  const size_t cloud = (size_t)max_n * (16 + 4 + (C == 4 ? 4 : 0)) + (G3 + 1) * 4;
+  // A packed tower takes the global-load walk only.  The LDS-copy form exists because a (24, 2048) dense tower has under one wave per
+  // SIMD; its dynamic LDS is sized per LAUNCH, so in a mixed tower it would cap every block -- those of the large clouds, which have
+  // the waves to hide a global round trip, included -- at one per CU.
+  const bool in_lds = !Clouds::kPacked && max_n <= LDS_CLOUD_MAX && park + cloud + 16 <= 160 * 1024;
 #define DG_GRID2(KC, C4)                                                                                                          \
   do {                                                                                                                            \
-    if (in_lds) {                                                                                                                 \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&knn_grid_query_kernel<KC, C4, true>),                             \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                                          \
-      dg::launch((knn_grid_query_kernel<KC, C4, true>), grid, dim3(64 * QW), park + cloud + 16, st, ps, s4, order,        \
-                         cell_start, info, N, k, idx);                                                                            \
-    } else {                                                                                                                      \
-      dg::launch((knn_grid_query_kernel<KC, C4, false>), grid, dim3(64 * QW), park, st, ps, s4, order, cell_start, info,  \
-                         N, k, idx);                                                                                              \
+    if constexpr (!Clouds::kPacked) {                                                                                             \
+      if (in_lds) {                                                                                                               \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&knn_grid_query_kernel<KC, C4, true>),                           \
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                                        \
+        dg::launch((knn_grid_query_kernel<KC, C4, true>), grid, dim3(64 * QW), park + cloud + 16, st, ps, s4, order, cell_start, \
+                   info, cl, k, idx);                                                                                             \
+        break;                                                                                                                    \
+      }                                                                                                                           \
     }                                                                                                                             \
+    dg::launch((knn_grid_query_kernel<KC, C4, false, Clouds>), grid, dim3(64 * QW), park, st, ps, s4, order, cell_start, info,   \
+               cl, k, idx);                                                                                                       \
   } while (0)
 #define DG_GRID(KC)                    \
   do {                                 \
@@ -453,10 +466,68 @@ int launch_knn_grid(const float* x, const float* sq, int B, int N, int C, int64_
   else DG_GRID(40);
 #undef DG_GRID
 #undef DG_GRID2
-  return check_launch("dgcnn_knn_f32 (grid)");
+  (void)in_lds;
+  return dg::check_launch(what);
+}
+
+}  // namespace
+
+namespace dg {
+
+size_t knn_grid_workspace_bytes(int B, int N) { return grid_ws_bytes((size_t)B * (size_t)N, (size_t)B); }
+size_t knn_grid_seg_workspace_bytes(int rows, int nseg) { return grid_ws_bytes((size_t)rows, (size_t)nseg); }
+
+// C <= 4, k <= 40.  sq = the s_j of the cloud (already computed); ws >= knn_grid_workspace_bytes(B, N), 16-byte aligned.
+bool knn_grid_applicable(int C, int k) { return knn_grid_on() && C <= 4 && k <= 40; }
+
+// Where it pays (profiles/r04/knn_grid.txt): the walk costs ~22 k candidates per row whatever N is, the all-pairs kernel N.
+// Measured cross-over between N = 2048 (all pairs 155 us, grid 207 us at B = 24: one 64-query wave per SIMD, bound by its own
+// dependent instruction chain) and N = 4096; at N = 16384 / 65536 the grid is 3.1x / 14x faster.  $DGCNN_KNN_GRID_MIN_N moves it
+// (tests run the grid at every N).
+static int grid_min_env() {              // $DGCNN_KNN_GRID_MIN_N, or INT_MIN when it is not set
+  static int v = 0;
+  static bool read = false;
+  if (!read) { const char* e = getenv("DGCNN_KNN_GRID_MIN_N"); v = e ? atoi(e) : INT_MIN; read = true; }
+  return v;
+}
+int knn_grid_min_n() {
+  const int e = grid_min_env();
+  return g_knn_grid_all ? 0 : (e == INT_MIN ? 4096 : e);
+}
+// Packed towers: the smallest row-weighted mean cloud size (sum n_b^2 / rows = candidates per row of the all-pairs scan) from which
+// the grid is used.  Higher than the dense N: a packed tower never takes the LDS-copy form and its all-pairs scan is ONE launch with
+// the histogram bound.  Measured (profiles/packed/grid_bench.txt, grid_sweep.txt; C = 4, k = 20 / 40): the grid LOSES at k = 40 on 24
+// clouds of 1024 ... 8192 points (mean 5.7 k: 0.83x) and at both k on one 16384-point cloud among 23 small ones (mean 6.6 k: 0.88x /
+// 0.63x); it wins on equal-sized clouds from 6144 points on (1.0x ... 3.8x) and on one 32768-point cloud among 23 small ones (mean
+// 18.2 k: 1.5x / 1.08x).  The lopsided towers set the constant: between their losing and winning mean, at the k = 40 end.
+// $DGCNN_KNN_GRID_MIN_N overrides this value too.
+constexpr int GRID_SEG_MIN_MEAN = 16384;
+int knn_grid_seg_min_mean() {
+  const int e = grid_min_env();
+  return g_knn_grid_all ? 0 : (e == INT_MIN ? GRID_SEG_MIN_MEAN : e);
+}
+
+int launch_knn_grid(const float* x, const float* sq, int B, int N, int C, int64_t ldx, int k, int32_t* idx, void* ws, hipStream_t st) {
+  return launch_grid("dgcnn_knn_f32 (grid)", x, sq, DenseClouds(N), B, N, (size_t)B * (size_t)N, C, ldx, k, idx, ws, st);
+}
+
+// packed tower: sq = the s_j of every tower row; ws >= knn_grid_seg_workspace_bytes(rows, nseg), 16-byte aligned
+int launch_knn_grid_seg(const float* x, const float* sq, int nseg, const int32_t* seg_off, int rows, int max_n, int C, int64_t ldx, int k,
+                        int32_t* idx, void* ws, hipStream_t st) {
+  return launch_grid("dgcnn_knn_seg_grid_f32", x, sq, PackedClouds{seg_off, nseg}, nseg, max_n, (size_t)rows, C, ldx, k, idx, ws, st);
 }
 
 }  // namespace dg
+
+// Would the library send this packed tower through the cell grid?  (host only, no GPU call)  Mode 1: from a row-weighted mean cloud
+// size of knn_grid_seg_min_mean() on -- the all-pairs scan evaluates n_b candidates for each of cloud b's n_b rows, sum_n2 / rows on
+// average, against the grid's N-independent ~22 k; for a dense-shaped tower sum_n2 / rows is N.
+extern "C" int dgcnn_knn_seg_grid_use(int C, int k, int nseg, int rows, int min_n, int max_n, int64_t sum_n2) {
+  (void)min_n;
+  (void)max_n;
+  if (C <= 0 || k <= 0 || nseg <= 0 || rows <= 0 || !dg::knn_grid_applicable(C, k)) return 0;
+  return sum_n2 >= (int64_t)dg::knn_grid_seg_min_mean() * rows ? 1 : 0;
+}
 
 // 0 = never, 1 = where it pays (N >= knn_grid_min_n), 2 = whenever applicable (tests)
 extern "C" int dgcnn_knn_grid(int mode) {

@@ -554,7 +554,8 @@ class Segments(object):
 def knn(x2d, B, N, k, seed=None, seg=None):
     """idx (B,N,k) of x2d (B*N, C).  seed: an earlier graph of the same clouds, (B,N,ks) int32 with ks >= k -- ks distinct candidates
     per row whose largest distance bounds the row's k-th distance from above (dgcnn_knn_seeded_f32); the result does not depend on it.
-    seg: a packed tower (Segments; B = 1, N = rows): every row searches its own cloud, idx holds tower rows (dgcnn_knn_seg_f32)."""
+    seg: a packed tower (Segments; B = 1, N = rows): every row searches its own cloud, idx holds tower rows (dgcnn_knn_seg_f32, or
+    dgcnn_knn_seg_grid_f32 for raw coordinates where dgcnn_knn_seg_grid_use picks the cell grid)."""
     if seg is not None:
         return knn_packed(x2d, k, seg, seed=seed)
     C = x2d.shape[1]
@@ -589,16 +590,24 @@ def knn_packed(x2d, k, seg, seed=None):
     seg.check_k(k)
     off = seg.device(x2d.device)
     idx = torch.empty((1, R, k), dtype=torch.int32, device=x2d.device)
+    n = seg.host[1:] - seg.host[:-1]
+    Cp, kc = (4 if C <= 4 else 16 if C <= 16 else 64 if C <= 64 else 128), (8 if k <= 8 else 20 if k <= 20 else 40 if k <= 40 else 64)
+    # raw coordinates: the cell grid, one per cloud, where the library's rule picks it (the same indices; a seed is not needed)
+    if C <= 4 and H.load().dgcnn_knn_seg_grid_use(C, k, seg.nseg, R, seg.min_n, seg.max_n, int((n * n).sum())):
+        nws = int(H.load().dgcnn_knn_seg_grid_workspace_bytes(R, seg.nseg))
+        ws = torch.empty((nws,), dtype=torch.uint8, device=x2d.device)
+        H.call("dgcnn_knn_seg_grid_f32", x2d.data_ptr(), H.ld2(x2d), C, k, seg.nseg, off.data_ptr(), R, seg.min_n, seg.max_n,
+               idx.data_ptr(), ws.data_ptr(), nws, tag="knn_seg_call<C4,k%d>[sqnorm_kernel+knn_grid_*]" % kc,
+               work=2.0 * float((n * n).sum()) * C)
+        return idx
     nws = int(H.load().dgcnn_knn_seg_workspace_bytes(R, seg.max_n, C, k))
     ws = torch.empty((nws,), dtype=torch.uint8, device=x2d.device)
-    Cp, kc = (4 if C <= 4 else 16 if C <= 16 else 64 if C <= 64 else 128), (8 if k <= 8 else 20 if k <= 20 else 40 if k <= 40 else 64)
     seeded = (KNN_SEED and seed is not None and seed.dim() == 3 and seed.shape[0] == 1 and seed.shape[1] == R and seed.shape[2] >= k
               and seed.dtype == torch.int32 and seed.is_contiguous())
     if seeded and 16 < C <= 64:
         tag = "knn_seg_call<C%d,k%d>[sqnorm_kernel+knn_seed_bound_kernel+knn_bf16a_kernel+knn_select_kernel]" % (Cp, kc)
     else:
         tag = "knn_seg_call<C%d,k%d>[sqnorm_kernel+%sknn_kernel]" % (Cp, kc, "knn_hist_bound_kernel+" if C <= 4 else "")
-    n = seg.host[1:] - seg.host[:-1]
     H.call("dgcnn_knn_seg_f32", x2d.data_ptr(), H.ld2(x2d), C, k, seg.nseg, off.data_ptr(), R, seg.min_n, seg.max_n,
            seed.data_ptr() if seeded else None, int(seed.shape[2]) if seeded else 0, int(seed.shape[2]) if seeded else 0,
            idx.data_ptr(), ws.data_ptr(), nws, tag=tag, work=2.0 * float((n * n).sum()) * C)

@@ -60,7 +60,8 @@ const char* dgcnn_last_error(void);
  *   all-pairs, list-keeping kernels. */
 int64_t dgcnn_knn_workspace_bytes(int B, int N, int C, int k);
 /* 0 = all-pairs kernel for C <= 4 too, 1 (default) = cell grid where it pays (N >= 4096: $DGCNN_KNN_GRID_MIN_N), 2 = cell grid
- * whenever applicable (tests); returns the previous setting ($DGCNN_KNN_GRID=0 switches it off). */
+ * whenever applicable (tests); returns the previous setting ($DGCNN_KNN_GRID=0 switches it off).  Packed towers follow the same
+ * modes through dgcnn_knn_seg_grid_use. */
 int dgcnn_knn_grid(int mode);
 /* A/B switch: 1 = distances by VALU fmaf chains for every C (exact by construction), 0 (default) =
  * v_mfma_f32_32x32x2_f32 for C > 4 (bit-identical on gfx950; the tests compare both).  Returns the
@@ -107,6 +108,21 @@ int dgcnn_knn_hist(int stride);
 int64_t dgcnn_knn_seg_workspace_bytes(int rows, int max_n, int C, int k);
 int dgcnn_knn_seg_f32(const float* x, int64_t ldx, int C, int k, int nseg, const int32_t* seg_off, int rows, int min_n, int max_n,
                       const int32_t* seed, int64_t ldseed, int kseed, int32_t* idx, void* ws, size_t ws_bytes, void* stream);
+/* The same packed search for raw coordinates (C <= 4, k <= 40) through the exact cell grid of csrc/knn_grid.hip: one uniform grid per
+ * cloud (its cell count from the cloud's own size), every row walks the rings of cells around its own until its k-th distance
+ * provably beats everything further out -- ~22 k candidates per row whatever the cloud's size, where dgcnn_knn_seg_f32 scans all n_b
+ * rows of the cloud.  Same pairs' arithmetic, same (D, j) order: idx is dgcnn_knn_seg_f32's, bit for bit.  No seed (the grid needs
+ * none).  DGCNN_EINVAL for C > 4, k > 40, k > min_n, nseg outside [1, 65535], a null pointer, a misaligned workspace or one
+ * smaller than dgcnn_knn_seg_grid_workspace_bytes(rows, nseg) = the s_i of every row + 24 bytes per row (sorted records, s_j,
+ * original indices) + one cell table (16^3 + 1 int32) and one 64-byte grid description per cloud.
+ * dgcnn_knn_seg_grid_use: host only (no GPU call) -- 1 when the library's rule sends this tower through the grid: dgcnn_knn_grid
+ * mode 2 = whenever C <= 4 and k <= 40, mode 1 = also sum_n2 / rows >= 4096 ($DGCNN_KNN_GRID_MIN_N), sum_n2 = sum of n_b^2: the
+ * row-weighted mean cloud size, i.e. the candidates per row of the all-pairs scan (N for a dense tower: the dense rule), mode 0 =
+ * never.  dgcnn/_engine.py:knn_packed asks it and calls this entry or dgcnn_knn_seg_f32. */
+int64_t dgcnn_knn_seg_grid_workspace_bytes(int rows, int nseg);
+int dgcnn_knn_seg_grid_f32(const float* x, int64_t ldx, int C, int k, int nseg, const int32_t* seg_off, int rows, int min_n, int max_n,
+                           int32_t* idx, void* ws, size_t ws_bytes, void* stream);
+int dgcnn_knn_seg_grid_use(int C, int k, int nseg, int rows, int min_n, int max_n, int64_t sum_n2);
 
 /* ---- K3 in its bf16-operand form (BASELINE configs[2] "bf16 edge-MLP MFMA"): conv0 of an EdgeConv layer, ops.py:21-52 ------
  * E[e] = [x_i, x_j - x_i] formed in fp32 and rounded to bf16 once (RNE), W0 (2C x F, row-major) rounded to bf16 once,

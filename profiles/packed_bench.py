@@ -1,7 +1,7 @@
 """Packed towers, k-NN only: one segmented search over a tower of 24 clouds (N ~ U[1024, 8192], seeded rng) against the same 24
 clouds searched one dense call each, in the same kernel forms, for the layers of the default model (k = 20) and of the production
-one (k = 40): layer 0 on raw coordinates (C = 4; cell grid off, then on for the dense calls, which is not segmented) and a later layer
-on 64 features seeded with the previous layer's graph (append-form scan).  Device time from HIP events around the whole sequence of
+one (k = 40): layer 0 on raw coordinates (C = 4; cell grid off, then on by the library's rule for both sides) and a later layer on 64
+features seeded with the previous layer's graph (append-form scan).  Device time from HIP events around the whole sequence of
 calls, after a synchronise; the dense sequence includes its launch gaps.  Every packed result is checked against the dense ones.
 
 Whole step: the same 24 clouds through trainval with BASELINE configs[1]'s model (3 EdgeConv (64, 64, 128), merged 1024, FC (512, 256),
@@ -9,7 +9,14 @@ Whole step: the same 24 clouds through trainval with BASELINE configs[1]'s model
 launched eagerly, default (deterministic) mode, same event timing.  The two compute different BatchNorm statistics (over the tower
 / over each cloud), so only the times are compared.
 
-    python profiles/packed_bench.py [--reps 20] [--out profiles/packed/bench.txt]
+Cell grid on packed towers (--grid-out): one packed layer-0 call at C = 4, k = 20 and k = 40, the all-pairs scan with the histogram
+bound (dgcnn_knn_grid(0)) against the per-cloud cell grid (dgcnn_knn_grid(2)), alternating in the same process over several rounds, on
+three towers from fixed seeds: (a) the mix above, (b) 8 clouds N ~ U[8192, 32768], (c) one 65536-point cloud + 23 clouds N ~ U[512, 2048].
+Per path the min / median / max of the rounds; the indices of the two paths are asserted equal; the last column says what the
+library's default rule (mode 1: dgcnn_knn_seg_grid_use) picks for the tower.
+
+    python profiles/packed_bench.py [--reps 20] [--out profiles/packed/bench.txt] [--grid-out profiles/packed/grid_bench.txt] [--grid-only]
+                                   [--grid-sweep profiles/packed/grid_sweep.txt]   (more towers: where the two paths cross)
 """
 import argparse
 import os
@@ -69,13 +76,85 @@ def whole_step(rng, sizes, off, reps):
             "(loss of the first step: packed %.4f, mean of the 24 clouds %.4f -- BatchNorm over the tower / over each cloud)" % (lp, ld)]
 
 
+def grid_towers():
+    r0, r1, r2 = np.random.default_rng(0), np.random.default_rng(1), np.random.default_rng(2)
+    return [("a: 24 clouds N ~ U[1024, 8192]", r0.integers(1024, 8193, 24)),
+            ("b: 8 clouds N ~ U[8192, 32768]", r1.integers(8192, 32769, 8)),
+            ("c: 65536 + 23 clouds N ~ U[512, 2048]", np.concatenate([[65536], r2.integers(512, 2049, 23)]))]
+
+
+def grid_sweep_towers():
+    """Where the two paths cross: equal-sized clouds, a wider mix, and one large cloud among 23 small ones."""
+    r = np.random.default_rng(3)
+    tw = [("16 x %d" % n, np.full(16, n)) for n in (6144, 8192, 10240, 12288, 16384, 20480)]
+    tw.append(("24 clouds U[4096,16384]", r.integers(4096, 16385, 24)))
+    tw.append(("16384 + 23 U[512,2048]", np.concatenate([[16384], r.integers(512, 2049, 23)])))
+    tw.append(("32768 + 23 U[512,2048]", np.concatenate([[32768], r.integers(512, 2049, 23)])))
+    return tw
+
+
+def grid_section(lib, reps, rounds=5, towers=None):
+    """The packed raw-coordinate layer: all-pairs scan (grid mode 0) against the per-cloud cell grid (mode 2), alternating."""
+    prop = torch.cuda.get_device_properties(0)
+    lines = ["device: %s (%s, %d CUs), one GPU" % (prop.name or "AMD Instinct", getattr(prop, "gcnArchName", "?"), prop.multi_processor_count),
+             "one packed layer-0 k-NN call, C = 4: all-pairs scan + histogram bound (dgcnn_knn_grid(0)) vs per-cloud cell grid (dgcnn_knn_grid(2)),",
+             "%d rounds alternating the two, %d calls per round between HIP events; ms per call as min / median / max of the rounds" % (rounds, reps),
+             "%-40s %4s %26s %26s %8s %s" % ("tower", "k", "all-pairs ms", "cell grid ms", "speedup", "verdict; rule (mode 1)")]
+    prev = lib.dgcnn_knn_grid(0)
+    try:
+        for name, sizes in (towers or grid_towers()):
+            off = np.concatenate([[0], np.cumsum(sizes)])
+            R = int(off[-1])
+            seg = E.Segments(off, R)
+            s2 = int((sizes.astype(np.int64) ** 2).sum())
+            x = torch.from_numpy(np.random.default_rng(R).random((R, 4), dtype=np.float32)).cuda()
+            lines.append("%s: R = %d rows, min %d, max %d, row-weighted mean cloud size %.0f" % (name, R, seg.min_n, seg.max_n, s2 / R))
+            for k in (20, 40):
+                call = lambda: E.knn(x, 1, R, k, seg=seg)
+                lib.dgcnn_knn_grid(1)
+                rule = int(lib.dgcnn_knn_seg_grid_use(4, k, seg.nseg, R, seg.min_n, seg.max_n, s2))
+                res, t = {}, {0: [], 2: []}
+                for rd in range(rounds):
+                    for mode in (0, 2):
+                        lib.dgcnn_knn_grid(mode)
+                        if rd == 0:
+                            res[mode] = call().cpu().numpy()
+                        t[mode].append(timed(call, reps))
+                assert np.array_equal(res[0], res[2]), "%s, k=%d: cell grid != all-pairs scan" % (name, k)
+                a, g = np.array(t[0]), np.array(t[2])
+                verdict = "grid faster beyond the spread" if g.max() < a.min() else ("scan faster beyond the spread" if a.max() < g.min() else "within the spread")
+                lines.append("%-40s %4d %8.3f /%8.3f /%8.3f %8.3f /%8.3f /%8.3f %8.2f %s; rule picks the %s" % (
+                    "", k, a.min(), np.median(a), a.max(), g.min(), np.median(g), g.max(), np.median(a) / np.median(g), verdict,
+                    "grid" if rule else "scan"))
+    finally:
+        lib.dgcnn_knn_grid(prev)
+    return lines
+
+
+def write(path, lines):
+    text = "\n".join(lines)
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        f.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "packed", "bench.txt"))
+    ap.add_argument("--grid-out", default=os.path.join(ROOT, "profiles", "packed", "grid_bench.txt"))
+    ap.add_argument("--grid-only", action="store_true", help="only the cell-grid section")
+    ap.add_argument("--grid-sweep", default=None, metavar="FILE",
+                    help="also time the towers of grid_sweep_towers() (3 rounds) into FILE (profiles/packed/grid_sweep.txt)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "packed_bench measures on the GPU"
     lib = H.load()
+    write(args.grid_out, grid_section(lib, args.reps))
+    if args.grid_sweep:
+        write(args.grid_sweep, grid_section(lib, args.reps, rounds=3, towers=grid_sweep_towers()))
+    if args.grid_only:
+        return
     rng = np.random.default_rng(0)
     sizes = rng.integers(1024, 8193, 24)
     off = np.concatenate([[0], np.cumsum(sizes)])
@@ -98,7 +177,7 @@ def main():
                 di = np.concatenate([d.reshape(-1, k).cpu().numpy() + off[b] for b, d in enumerate(dense())])
                 assert np.array_equal(pi, di), "layer 0, k=%d: packed != dense" % k
                 tp, td = timed(packed, args.reps), timed(dense, args.reps)
-                lines.append("%-34s %12.3f %12.3f %8.3f" % ("C=4  k=%d  (dense cell grid %s)" % (k, "on" if grid else "off"),
+                lines.append("%-34s %12.3f %12.3f %8.3f" % ("C=4  k=%d  (cell grid %s)" % (k, "by the rule" if grid else "off"),
                                                             tp, td, tp / td))
             lib.dgcnn_knn_grid(0)
             sp = E.knn(x0, 1, R, k, seg=seg)
@@ -113,11 +192,7 @@ def main():
     finally:
         lib.dgcnn_knn_grid(prev_grid)
     lines += whole_step(rng, sizes, off, max(2, args.reps // 4))
-    text = "\n".join(lines)
-    print(text)
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+    write(args.out, lines)
 
 
 if __name__ == "__main__":
