@@ -511,9 +511,11 @@ KNN_SEED = os.environ.get("DGCNN_KNN_SEED", "1") != "0"   # seed a layer's k-NN 
 class Segments(object):
     """A packed tower: nseg clouds of different sizes concatenated row-wise, cloud b = rows [offsets[b], offsets[b + 1]).  Holds the
     host offsets (validated here, before any device work), their device copy and the row -> cloud map row_group[r] = b (each made
-    once, on the host, on first use) and the smallest / largest cloud, from which the k-NN picks its kernel forms."""
+    once, on the host, on first use) and the smallest / largest cloud, from which the k-NN picks its kernel forms.
+    bn_per_cloud: every BatchNorm of the tower takes the statistics of the row's own cloud instead of all rows (csrc/seg_bn.hip;
+    forward only) -- the mode travels with the `seg=` every pass already receives."""
 
-    def __init__(self, offsets, rows=None):
+    def __init__(self, offsets, rows=None, bn_per_cloud=False):
         if isinstance(offsets, torch.Tensor):
             offsets = offsets.detach().cpu().numpy()
         off = np.asarray(offsets)
@@ -533,6 +535,7 @@ class Segments(object):
         self.min_n, self.max_n = int(sizes.min()), int(sizes.max())
         self._dev = None
         self._rg = None
+        self.bn_per_cloud = bool(bn_per_cloud)
 
     def check_k(self, k):
         if k <= 0 or k > self.min_n:
@@ -718,6 +721,34 @@ def seg_colsum(x, seg, out):
     return out
 
 
+def per_cloud(seg):
+    """True when `seg` is a packed tower whose BatchNorm runs per cloud.  The mode has no backward: inside a recording it raises
+    here, on the host, before anything is launched."""
+    if seg is None or not seg.bn_per_cloud:
+        return False
+    if ctx().recording:
+        raise NotImplementedError("per-cloud BatchNorm has no backward yet")
+    return True
+
+
+def seg_stats_workspace(R, nseg, F, dev):
+    """Scratch of the two-stage per-cloud sums: the context's workspace, or a temporary where that is too small."""
+    need = int(H.load().dgcnn_seg_stats_workspace_bytes(R, nseg, F))
+    ws = ctx().workspace()
+    if ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    return ws
+
+
+def seg_bn_finalize(stats, seg, F, k):
+    """(mean, rstd), each (nseg, F): cloud b from its own sums and the count n_b * k."""
+    dev = stats.device
+    mr = torch.empty((2, seg.nseg, F), dtype=torch.float32, device=dev)
+    H.call("dgcnn_seg_bn_finalize_f32", stats.data_ptr(), seg.nseg, F, seg.device(dev).data_ptr(), int(k), BN_EPS,
+           mr[0].data_ptr(), mr[1].data_ptr())
+    return mr[0], mr[1]
+
+
 def bn_finalize(stats, F, count):
     dev = stats.device
     mr = torch.empty((2, F), dtype=torch.float32, device=dev)
@@ -740,7 +771,8 @@ def conv_bn_act(x, leaf_scope, num_outputs, relu=True, out=None, out2=None, gbia
     (model.py:76-77), taken on the GEMM output and normalised afterwards (BN + ReLU are monotone).
     drop_keep: tf.nn.dropout(out, drop_keep) behind the layer (model.py:90-91), fused into the BatchNorm passes where the
     kernels allow it (the returned tensor is the DROPPED output either way).
-    seg: a packed tower (Segments; x holds its seg.rows rows).  BatchNorm runs over all rows as in a dense tower; what is per
+    seg: a packed tower (Segments; x holds its seg.rows rows).  BatchNorm runs over all rows as in a dense tower (seg.bn_per_cloud:
+    over the rows of each cloud alone, _conv_bn_act_per_cloud -- forward only); what is per
     cloud goes through the segmented kernels (csrc/seg.hip): gbias is (nseg, Cout) and is addressed through the row -> cloud map
     (rpg is ignored), its gradient is the per-cloud column sum, gmax (any value but None) is the max-pool over each cloud's own
     rows -- always the separate pass over the GEMM output, never the epilogue.  The plane mode is NOT packed: a packed tower
@@ -749,6 +781,7 @@ def conv_bn_act(x, leaf_scope, num_outputs, relu=True, out=None, out2=None, gbia
     R, Cin = x.shape
     if seg is not None and seg.rows != R:
         raise ValueError("offsets end at %d, the tower has %d rows" % (seg.rows, R))
+    bpc = per_cloud(seg)
     rgrp = seg.row_group(x.device) if (seg is not None and gbias is not None) else None
     with variable_scope(leaf_scope):
         if w_rows is None:
@@ -759,6 +792,8 @@ def conv_bn_act(x, leaf_scope, num_outputs, relu=True, out=None, out2=None, gbia
             Wx = W[w_rows[0]:w_rows[1]]
         bname, beta = c.get_variable("BatchNorm/beta", (num_outputs,))
     F = num_outputs
+    if bpc:
+        return _conv_bn_act_per_cloud(c, x, Wx, beta, F, relu, out, out2, gbias, rgrp, arith, gmax, drop_keep, seg)
     T = torch.empty((R, F), dtype=torch.float32, device=x.device)
     # slots of this layer's statistics buffer = row tiles of its GEMM (asked from the library; another arithmetic: the step's maximum)
     # (0 = a kernel whose grid FOLLOWS the slot count -- the class dimension's streaming product: the step's maximum, more writers)
@@ -945,6 +980,41 @@ def conv_bn_act(x, leaf_scope, num_outputs, relu=True, out=None, out2=None, gbia
     return out, g
 
 
+def _conv_bn_act_per_cloud(c, x, Wx, beta, F, relu, out, out2, gbias, rgrp, arith, gmax, drop_keep, seg):
+    """conv_bn_act of a packed tower with per-cloud BatchNorm (forward only).  The GEMM runs WITHOUT epilogue statistics (a row
+    tile straddles clouds; the per-cloud bias through the row -> cloud map stays); then the per-cloud sums of T in a fixed
+    order, the (nseg, F) tables and the apply pass that picks the table row of the row's cloud.  gmax: the per-cloud maxima of T
+    are normalised with their own cloud's table row -- BN + ReLU are monotone per cloud, so the max-pool identity holds."""
+    R = x.shape[0]
+    dev = x.device
+    off = seg.device(dev)
+    rg = seg.row_group(dev)
+    T = torch.empty((R, F), dtype=torch.float32, device=dev)
+    gemm(x, Wx, T, gbias=gbias, arith=arith, row_group=rgrp)
+    st = torch.empty(seg.nseg * 2 * F, dtype=torch.float64, device=dev)
+    ws = seg_stats_workspace(R, seg.nseg, F, dev)
+    H.call("dgcnn_seg_colstats_f32", T.data_ptr(), H.ld2(T), R, F, off.data_ptr(), seg.nseg, st.data_ptr(), ws.data_ptr(), ws.numel(),
+           tag="seg_colstats_kernel", work=4.0 * R * F)
+    mean, rstd = seg_bn_finalize(st, seg, F, 1)
+    if out is None:
+        out = c.new_buffer(R, F)
+    H.call("dgcnn_seg_bn_act_f32", T.data_ptr(), H.ld2(T), R, F, rg.data_ptr(), mean.data_ptr(), rstd.data_ptr(), beta.data_ptr(),
+           int(relu), out.data_ptr(), H.ld2(out), H._p(out2), 0 if out2 is None else H.ld2(out2),
+           tag="seg_bn_act_kernel", work=4.0 * R * F * (2 if out2 is None else 3))
+    if gmax is None:
+        return out if drop_keep is None else dropout(out, drop_keep)
+    keys = c.stats_raw(seg.nseg * F)                                          # zeroed uint64[nseg][F]
+    H.call("dgcnn_colmax_seg_f32", T.data_ptr(), H.ld2(T), R, F, off.data_ptr(), seg.nseg, keys.data_ptr(),
+           tag="colmax_seg_kernel", work=4.0 * R * F)
+    graw = torch.empty((seg.nseg, F), dtype=torch.float32, device=dev)
+    arg = torch.empty((seg.nseg, F), dtype=torch.int32, device=dev)
+    H.call("dgcnn_colmax_decode_f32", keys.data_ptr(), seg.nseg * F, graw.data_ptr(), arg.data_ptr())
+    g = c.new_buffer(seg.nseg, F)
+    H.call("dgcnn_seg_bn_act_f32", graw.data_ptr(), F, seg.nseg, F, None, mean.data_ptr(), rstd.data_ptr(), beta.data_ptr(),
+           int(relu), g.data_ptr(), F, None, 0)
+    return out, g
+
+
 # ----------------------------------------------------------------------------------------------
 # dgcnn/ops.py:42-73 edge_conv as one block
 # ----------------------------------------------------------------------------------------------
@@ -1043,7 +1113,8 @@ def edge_conv_block(x, B, N, k, num_filters, relu1=True, outs=None, net2=None, s
     outs = (mm_view, net_view) destination slices (model path) or None (fresh buffers).
     seed: the previous EdgeConv layer's graph (B,N,k') or None: seeds this layer's k-NN filter (same result, fewer inserts).
     seg: a packed tower (Segments) with B = 1, N = R: only the k-NN is tied to a cloud (idx holds tower rows), every other pass is
-    row-wise -- BatchNorm statistics run over all rows of the tower, as in a dense (B, N) tower."""
+    row-wise -- BatchNorm statistics run over all rows of the tower, as in a dense (B, N) tower; seg.bn_per_cloud: over the rows
+    (conv0: the edges) of each cloud alone -- forward only, and only the default form of conv0 (the fold with the virtual Y)."""
     c = ctx()
     R, C = x.shape
     F = int(num_filters)
@@ -1053,9 +1124,40 @@ def edge_conv_block(x, B, N, k, num_filters, relu1=True, outs=None, net2=None, s
         seg.check_k(k)
     if k > N:
         raise ValueError("k_nn: k=%d > N=%d (tf.nn.top_k raises InvalidArgument)" % (k, N))
+    bpc = per_cloud(seg)
+    if bpc:
+        # every form of conv0 the per-cloud kernels do not take is refused here, on the host, before any launch
+        if EDGE_MLP_DTYPE == "bf16" or EDGE_MLP_LITERAL or EDGE_MLP_NBR_GEMM or EDGE_MATERIALIZE_Y:
+            raise ValueError("per-cloud BatchNorm takes the default conv0 only (fp32 fold, virtual edge tensor): EDGE_MLP_DTYPE=%r, "
+                             "literal / neighbour-GEMM / materialised switches off" % (EDGE_MLP_DTYPE,))
+        if F % 4 != 0 or F > 1024 or k >= 256:
+            raise ValueError("per-cloud BatchNorm needs EdgeConv filter counts that are multiples of 4, <= 1024, and k < 256 "
+                             "(got F=%d, k=%d)" % (F, k))
+        if R >= 1 << 24 or 2 * F * R >= 1 << 32:
+            raise ValueError("per-cloud BatchNorm: a tower of %d rows x %d filters exceeds the 32-bit row offsets of the gather" % (R, F))
     with variable_scope("conv0"):
         w0name, W0 = c.get_variable("weights", (2 * C, F))
         b0name, beta0 = c.get_variable("BatchNorm/beta", (F,))
+    if bpc:
+        dev = x.device
+        idx = knn(x, B, N, k, seed=seed, seg=seg)                           # ops.py:8-19
+        _, _, _, UV = _point_gemm(c, x, W0, R, C, F)                        # [U | V] = X [Wa-Wb | Wb]
+        esrc = (UV[:, F:].data_ptr(), 2 * F, UV.data_ptr(), 2 * F, idx.data_ptr(), R, k, F)
+        st = torch.empty(seg.nseg * 2 * F, dtype=torch.float64, device=dev)
+        ws = seg_stats_workspace(R, seg.nseg, F, dev)
+        H.call("dgcnn_seg_edge_stats_f32", *esrc, seg.device(dev).data_ptr(), seg.nseg, st.data_ptr(), ws.data_ptr(), ws.numel(),
+               tag="seg_edge_stats_kernel", work=4.0 * (2 * R * F) + 4.0 * R * k, nbytes=4.0 * (R * k * F + R * F))
+        mean, rstd = seg_bn_finalize(st, seg, F, k)                         # ops.py:53, count n_b * k
+        if outs is None:
+            mm, net_out = c.new_buffer(R, 2 * F), None
+        else:
+            mm, net_out = outs
+        mx, mn = mm[:, :F], mm[:, F:]
+        H.call("dgcnn_seg_edge_bn_act_kreduce_f32", *esrc, seg.row_group(dev).data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+               beta0.data_ptr(), 1, mx.data_ptr(), H.ld2(mx), mn.data_ptr(), H.ld2(mn),
+               tag="seg_edge_bn_act_kreduce_kernel", work=4.0 * (4 * R * F) + 4.0 * R * k, nbytes=4.0 * (R * k * F + R * F))   # ops.py:54-58
+        net = conv_bn_act(mm, "conv1", 64, relu=relu1, out=net_out, out2=net2, arith=None, seg=seg)   # ops.py:62-70
+        return mm, net, idx
     c.push_slots(c.step_slots)                   # conv0's statistics come from passes whose grids FOLLOW the slot count: the maximum
     st = c.stats(F)
     bf16 = EDGE_MLP_DTYPE == "bf16"

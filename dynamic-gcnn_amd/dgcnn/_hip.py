@@ -110,6 +110,13 @@ PROTOTYPES = {
     "dgcnn_seg_colsum_workspace_bytes": [c_int, c_int, c_int],
     "dgcnn_seg_colsum_f32": [c_vp, c_i64, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_sz, c_vp],
     "dgcnn_tile_rows_seg_f32": [c_vp, c_i64, c_vp, c_int, c_int, c_vp, c_i64, c_vp],
+    "dgcnn_seg_stats_workspace_bytes": [c_int, c_int, c_int],
+    "dgcnn_seg_colstats_f32": [c_vp, c_i64, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_sz, c_vp],
+    "dgcnn_seg_edge_stats_f32": [c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_sz, c_vp],
+    "dgcnn_seg_bn_finalize_f32": [c_vp, c_int, c_int, c_vp, c_int, c_f32, c_vp, c_vp, c_vp],
+    "dgcnn_seg_bn_act_f32": [c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_vp, c_i64, c_vp],
+    "dgcnn_seg_edge_bn_act_kreduce_f32": [c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int,
+                                          c_vp, c_i64, c_vp, c_i64, c_vp],
     "dgcnn_dropout_f32": [c_vp, c_vp, c_i64, c_f32, c_u64, c_vp],
     "dgcnn_dropout_dev_f32": [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp],
     "dgcnn_add_relu_f32": [c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_vp, c_i64, c_vp],
@@ -152,7 +159,8 @@ PROTOTYPES = {
 }
 
 INT64_RESULTS = ("dgcnn_knn_workspace_bytes", "dgcnn_knn_seg_workspace_bytes", "dgcnn_knn_seg_grid_workspace_bytes",
-                 "dgcnn_edge_mlp_bf16_bwd_workspace_bytes", "dgcnn_seg_colsum_workspace_bytes")      # byte counts; every other entry point returns an int status
+                 "dgcnn_edge_mlp_bf16_bwd_workspace_bytes", "dgcnn_seg_colsum_workspace_bytes",
+                 "dgcnn_seg_stats_workspace_bytes")      # byte counts; every other entry point returns an int status
 
 _lib = None
 

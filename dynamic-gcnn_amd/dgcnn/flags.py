@@ -57,6 +57,8 @@ _OPTIONS = [
                                              "0 | f16 (2 fp16 planes, 3 products); default $DGCNN_HEAD_PLANES"),
     ("PACK_TOWERS", "-pt", _BOOL, False, "ti", "a micro-batch of clouds with different point counts (-np -1 with -mbs > 1) runs as ONE packed "
                                                "tower (clouds concatenated row-wise, per-cloud neighbours / max-pool) instead of being refused"),
+    ("BN_PER_CLOUD", "-bpc", _BOOL, False, "i", "every BatchNorm of a tower of several clouds takes the statistics of the row's own cloud: "
+                                                "the predictions of -mbs 1, whatever shares the micro-batch (inference only)"),
 ]
 
 

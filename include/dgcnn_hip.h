@@ -463,6 +463,42 @@ int dgcnn_seg_colsum_f32(const float* x, int64_t ldx, int rows, int F, const int
                          void* ws, size_t ws_bytes, void* stream);
 int dgcnn_tile_rows_seg_f32(const float* src, int64_t lds, const int32_t* row_group, int rows, int F, float* dst, int64_t ldd,
                             void* stream);
+/* ---- BatchNorm of a packed tower with the statistics of the row's OWN cloud (csrc/seg_bn.hip; FORWARD ONLY: there is no backward
+ * yet).  Cloud b = rows [seg_off[b], seg_off[b + 1]); idx (rows, k) holds TOWER rows; statistics are double[nseg][2][F] (sum and sum
+ * of squares per cloud; WRITTEN, not accumulated: the caller does not zero them); mean / rstd are float[nseg][F] tables; row_group =
+ * int32[rows], the row -> cloud map.  With these a cloud's outputs do not depend on the other clouds of its tower.
+ *   dgcnn_seg_colstats_f32     per cloud, the column sums of a materialised (rows, F) tensor (the k = 1 layers)
+ *   dgcnn_seg_edge_stats_f32   the same over the never-materialised conv0 output y = V[idx[r, m]] + U[r] (the single fp32 add of
+ *                              dgcnn_edge_gather_add_f32).  F % 4 == 0, F <= 1024, 16-byte aligned rows, rows < 2^24, ldv < 2^24,
+ *                              rows * ldv < 2^32 (DGCNN_EUNSUP otherwise)
+ *     Both sum in ONE fixed order, whatever dgcnn_set_stat_slots says (two runs are bit-identical): stage 1 over 64-row chunks of
+ *     the tower cut at the cloud boundaries (grids over chunks, never one workgroup per cloud; the edge form keeps consecutive chunks
+ *     on one XCD), every (chunk, cloud) piece one double per column; stage 2 adds a cloud's pieces first chunk to last, in double.
+ *     ws: dgcnn_seg_stats_workspace_bytes(rows, nseg, F) bytes (host only; 0 for an empty tower), 8-byte aligned; DGCNN_ENOSPC with
+ *     the needed count in dgcnn_last_error otherwise.
+ *   dgcnn_seg_bn_finalize_f32  mean / rstd of cloud b from its sums and the count (seg_off[b + 1] - seg_off[b]) * k:
+ *                              dgcnn_bn_finalize_f32's arithmetic (double, biased variance clamped at 0)
+ *   dgcnn_seg_bn_act_f32       k = 1: out[r] = act((T[r] - mean[g]) * rstd[g] + beta), g = row_group[r]; row_group == NULL: g = r
+ *                              (normalises the per-cloud max-pool, rows = nseg).  out2: optional second copy.  float4 path when
+ *                              everything is 16-byte aligned with F, ld % 4 == 0, scalar path otherwise (the class dimension)
+ *   dgcnn_seg_edge_bn_act_kreduce_f32   BN + ReLU + max / mean (mean_out may be NULL) over the k recomputed edge rows of each point
+ *                              with the table row of the point's cloud; the shapes of dgcnn_seg_edge_stats_f32.  No tie / positive
+ *                              counts (they serve the backward only).
+ * A one-cloud tower with the dense kernels' mean / rstd gives dgcnn_bn_act_kreduce_f32 / dgcnn_edge_bn_act_kreduce_f32's outputs bit
+ * for bit.  DGCNN_EINVAL for null or misshapen arguments; nothing is written on error. */
+int64_t dgcnn_seg_stats_workspace_bytes(int rows, int nseg, int F);
+int dgcnn_seg_colstats_f32(const float* x, int64_t ldx, int rows, int F, const int32_t* seg_off, int nseg, double* stats,
+                           void* ws, size_t ws_bytes, void* stream);
+int dgcnn_seg_edge_stats_f32(const float* V, int64_t ldv, const float* U, int64_t ldu, const int32_t* idx, int rows, int k, int F,
+                             const int32_t* seg_off, int nseg, double* stats, void* ws, size_t ws_bytes, void* stream);
+int dgcnn_seg_bn_finalize_f32(const double* stats, int nseg, int F, const int32_t* seg_off, int k, float eps, float* mean,
+                              float* rstd, void* stream);
+int dgcnn_seg_bn_act_f32(const float* T, int64_t ldt, int rows, int F, const int32_t* row_group, const float* mean,
+                         const float* rstd, const float* beta, int relu, float* out, int64_t ldo, float* out2, int64_t ldo2,
+                         void* stream);
+int dgcnn_seg_edge_bn_act_kreduce_f32(const float* V, int64_t ldv, const float* U, int64_t ldu, const int32_t* idx, int rows, int k,
+                                      int F, const int32_t* row_group, const float* mean, const float* rstd, const float* beta,
+                                      int relu, float* max_out, int64_t ldmax, float* mean_out, int64_t ldmean, void* stream);
 /* tf.nn.dropout(net, keep) (model.py:91): counter-based RNG keyed by (seed, element index) so the
  * backward regenerates the same mask.  y may alias x. */
 int dgcnn_dropout_f32(const float* x, float* y, int64_t n, float keep, uint64_t seed, void* stream);
