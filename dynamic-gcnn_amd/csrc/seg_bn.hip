@@ -1,4 +1,4 @@
-// seg_bn.hip -- BatchNorm of a PACKED tower with the statistics of the row's OWN cloud (forward only).  Cloud b = rows
+// seg_bn.hip -- BatchNorm of a PACKED tower with the statistics of the row's OWN cloud, forward and backward.  Cloud b = rows
 // [seg_off[b], seg_off[b + 1]) of the tower; the statistics are double[nseg][2][F] (sum, sum of squares per cloud), mean / rstd are
 // float[nseg][F] tables, and the apply passes pick the table row through the row -> cloud map.  With these, a cloud's outputs do not
 // depend on which other clouds share its tower: packed inference reproduces the inference of every cloud alone.
@@ -7,6 +7,10 @@
 // cloud boundaries inside them (seg.hip: grids over chunks, never one workgroup per cloud), every (chunk, cloud) piece leaves its
 // workgroup as one double per (sum, column) in partial slot (chunk + b) -- slots grow strictly with (chunk, b), so the pieces of
 // cloud b are a contiguous run; stage 2 adds a cloud's slots first chunk to last, in double.
+//
+// The backward (second half of the file) takes its per-cloud sums red = double[nseg][2][F] (sum dz, sum dz * xhat) by the same two
+// stages, turns them into the float tables c1 / c2 = red / (n_b k) and applies dY = rstd_g ((dz - c1_g) - xhat c2_g) through the
+// row -> cloud map; the arithmetic of bn.hip's backward kernels, operation for operation.
 #include "gemm_common.h"
 
 namespace {
@@ -39,6 +43,13 @@ __device__ __forceinline__ int cloud_of_row(const int32_t* __restrict__ seg_off,
 // gives the dense kernels' outputs bit for bit
 __device__ __forceinline__ float bn_z(float y, float mu, float rs, float be, int relu) {
   const float xh = (y - mu) * rs;
+  float z = xh + be;
+  if (relu) z = fmaxf(z, 0.f);
+  return z;
+}
+
+__device__ __forceinline__ float bn_z(float y, float mu, float rs, float be, int relu, float& xh) {
+  xh = (y - mu) * rs;
   float z = xh + be;
   if (relu) z = fmaxf(z, 0.f);
   return z;
@@ -238,12 +249,17 @@ __global__ __launch_bounds__(256) void seg_bn_act_kernel(const float* __restrict
 // ---- conv0: BN + ReLU + max / mean over the k recomputed edge rows of each point, with the table row of the point's cloud ---------
 // item = (point, channel quad); XCD x (blockIdx % 8) owns the x-th eighth of the points and its blocks sweep it side by side (the
 // item map of bn.hip's edge kernels).  The k terms of the mean are added in ascending m and scaled by 1.0f / k, as there.
+// CNT: also cnt_out (rows, F) = #ties of the max + CNT_POS * #(z > 0), the packing of bn.hip's edge forward (exact small integers,
+// k < CNT_POS), which the backward reads; max_out / mean_out are formed by the same instructions in both instantiations.
+constexpr int CNT_POS = 256;
+template <bool CNT>
 __global__ __launch_bounds__(256) void seg_edge_bn_act_kreduce_kernel(const float* __restrict__ V, int64_t ldv, const float* __restrict__ U,
                                                                       int64_t ldu, const int32_t* __restrict__ idx, int64_t rows, int k,
                                                                       int F, const int32_t* __restrict__ row_group,
                                                                       const float* __restrict__ mean, const float* __restrict__ rstd,
                                                                       const float* __restrict__ beta, int relu, float* __restrict__ max_out,
-                                                                      int64_t ldmax, float* __restrict__ mean_out, int64_t ldmean) {
+                                                                      int64_t ldmax, float* __restrict__ mean_out, int64_t ldmean,
+                                                                      float* __restrict__ cnt_out) {
   const int FV = F >> 2;
   const int64_t per = (rows + 7) / 8;
   const int64_t rb = (int64_t)(blockIdx.x & 7) * per;
@@ -257,11 +273,11 @@ __global__ __launch_bounds__(256) void seg_edge_bn_act_kreduce_kernel(const floa
     const int64_t r = rb + qu / (unsigned)FV;
     const int f = (int)(qu % (unsigned)FV) * 4;
     const int64_t g = row_group[r];
-    float mu[4], rs[4], be[4], u[4], mx[4], sm[4];
+    float mu[4], rs[4], be[4], u[4], mx[4], sm[4], cn[4], np[4];
     Vec<4>::ld(mean + g * F + f, mu); Vec<4>::ld(rstd + g * F + f, rs); Vec<4>::ld(beta + f, be);
     Vec<4>::ld(U + r * ldu + f, u);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) { mx[j] = -INFINITY; sm[j] = 0.f; }
+    for (int j = 0; j < 4; ++j) { mx[j] = -INFINITY; sm[j] = 0.f; cn[j] = 0.f; np[j] = 0.f; }
     const int32_t* ip = idx + r * k;
     const float* vb = V + f;
     for (int m = 0; m < k; m += 4) {
@@ -277,12 +293,21 @@ __global__ __launch_bounds__(256) void seg_edge_bn_act_kreduce_kernel(const floa
 #pragma unroll
           for (int c = 0; c < 4; ++c) {
             const float z = bn_z(y[j][c] + u[c], mu[c], rs[c], be[c], relu);
+            if (CNT) {
+              cn[c] = (z > mx[c]) ? 1.f : ((z == mx[c]) ? cn[c] + 1.f : cn[c]);
+              np[c] += (z > 0.f) ? (float)CNT_POS : 0.f;
+            }
             mx[c] = (z > mx[c]) ? z : mx[c];
             sm[c] += z;
           }
         }
     }
     Vec<4>::st(max_out + r * ldmax + f, mx);
+    if (CNT) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) cn[c] += np[c];
+      Vec<4>::st(cnt_out + r * F + f, cn);
+    }
     if (mean_out) {
 #pragma unroll
       for (int c = 0; c < 4; ++c) sm[c] *= invk;
@@ -392,19 +417,389 @@ extern "C" int dgcnn_seg_bn_act_f32(const float* T, int64_t ldt, int rows, int F
   return dg::check_launch("dgcnn_seg_bn_act_f32");
 }
 
+static int seg_edge_act_kreduce(const char* what, const float* V, int64_t ldv, const float* U, int64_t ldu, const int32_t* idx, int rows,
+                                int k, int F, const int32_t* row_group, const float* mean, const float* rstd, const float* beta, int relu,
+                                float* max_out, int64_t ldmax, float* mean_out, int64_t ldmean, float* cnt_out, bool cnt, hipStream_t st) {
+  int rc = check_seg_edge(what, V, ldv, U, ldu, idx, rows, k, F);
+  if (rc) return rc;
+  DG_REQUIRE(row_group && mean && rstd && beta && max_out && (!cnt || cnt_out), DGCNN_EINVAL, "%s: null pointer", what);
+  DG_REQUIRE(relu == 0 || relu == 1, DGCNN_EINVAL, "%s: relu must be 0 or 1 (got %d)", what, relu);
+  DG_REQUIRE(!cnt || k < CNT_POS, DGCNN_EUNSUP, "%s: k must be < %d (the packed tie / positive counts)", what, CNT_POS);
+  DG_REQUIRE(ldmax >= F && ldmax % 4 == 0 && a16(max_out) && a16(mean) && a16(rstd) && a16(beta) &&
+                 (!mean_out || (ldmean >= F && ldmean % 4 == 0 && a16(mean_out))) && (!cnt || a16(cnt_out)),
+             DGCNN_EINVAL, "%s: outputs and tables must be 16-byte aligned with leading dimensions %% 4 == 0", what);
+  const unsigned grid = (grid_items((int64_t)rows * (F / 4)) + 7u) & ~7u;     // (the XCD item map needs a multiple of 8)
+  if (cnt)
+    dg::launch(seg_edge_bn_act_kreduce_kernel<true>, dim3(grid), dim3(256), 0, st, V, ldv, U, ldu, idx, (int64_t)rows, k, F, row_group, mean,
+               rstd, beta, relu, max_out, ldmax, mean_out, ldmean, cnt_out);
+  else
+    dg::launch(seg_edge_bn_act_kreduce_kernel<false>, dim3(grid), dim3(256), 0, st, V, ldv, U, ldu, idx, (int64_t)rows, k, F, row_group, mean,
+               rstd, beta, relu, max_out, ldmax, mean_out, ldmean, (float*)nullptr);
+  return dg::check_launch(what);
+}
+
 extern "C" int dgcnn_seg_edge_bn_act_kreduce_f32(const float* V, int64_t ldv, const float* U, int64_t ldu, const int32_t* idx, int rows,
                                                  int k, int F, const int32_t* row_group, const float* mean, const float* rstd,
                                                  const float* beta, int relu, float* max_out, int64_t ldmax, float* mean_out,
                                                  int64_t ldmean, void* stream) {
-  int rc = check_seg_edge("dgcnn_seg_edge_bn_act_kreduce_f32", V, ldv, U, ldu, idx, rows, k, F);
+  return seg_edge_act_kreduce("dgcnn_seg_edge_bn_act_kreduce_f32", V, ldv, U, ldu, idx, rows, k, F, row_group, mean, rstd, beta, relu,
+                              max_out, ldmax, mean_out, ldmean, nullptr, false, ST);
+}
+
+extern "C" int dgcnn_seg_edge_bn_act_kreduce_cnt_f32(const float* V, int64_t ldv, const float* U, int64_t ldu, const int32_t* idx, int rows,
+                                                     int k, int F, const int32_t* row_group, const float* mean, const float* rstd,
+                                                     const float* beta, int relu, float* max_out, int64_t ldmax, float* mean_out,
+                                                     int64_t ldmean, float* cnt_out, void* stream) {
+  return seg_edge_act_kreduce("dgcnn_seg_edge_bn_act_kreduce_cnt_f32", V, ldv, U, ldu, idx, rows, k, F, row_group, mean, rstd, beta, relu,
+                              max_out, ldmax, mean_out, ldmean, cnt_out, true, ST);
+}
+
+// =====================================================================================================================================
+// Backward.  red = double[nseg][2][F]: per cloud sum dz and sum dz * xhat (WRITTEN, not accumulated; not in the slot arena).
+// =====================================================================================================================================
+namespace {
+
+// ---- what a row contributes to the two sums: the integrands of the two reduce kernels ---------------------------------------------
+// k = 1 layers: dz = (dout + d2) [z > 0 if relu], terms (dz, dz * xhat) with z, xhat from bn_z -- bn1_bwd_kernel<false>'s row
+template <int VW>
+struct K1Terms {
+  static constexpr int UNROLL = SEG_UNROLL;
+  const float* T; int64_t ldt;
+  const float* mean; const float* rstd; const float* beta; int relu;
+  const float* dout; int64_t lddo;
+  const float* d2; int64_t ldd2;
+  struct Par { float mu[VW], rs[VW], be[VW]; };
+  struct Row { float y[VW], d[VW], e[VW]; };
+  __device__ __forceinline__ void par(int b, int F, int c0, Par& p) const {
+    Vec<VW>::ld(mean + (int64_t)b * F + c0, p.mu); Vec<VW>::ld(rstd + (int64_t)b * F + c0, p.rs); Vec<VW>::ld(beta + c0, p.be);
+  }
+  __device__ __forceinline__ void load(int r, int c0, Row& v) const {
+    Vec<VW>::ld(T + (int64_t)r * ldt + c0, v.y); Vec<VW>::ld(dout + (int64_t)r * lddo + c0, v.d);
+    if (d2) Vec<VW>::ld(d2 + (int64_t)r * ldd2 + c0, v.e);
+  }
+  __device__ __forceinline__ void add(const Row& v, const Par& p, float (&s0)[VW], float (&s1)[VW]) const {
+#pragma unroll
+    for (int j = 0; j < VW; ++j) {
+      float xh;
+      const float z = bn_z(v.y[j], p.mu[j], p.rs[j], p.be[j], relu, xh);
+      float dz = v.d[j];
+      if (d2) dz += v.e[j];                                   // the output had two consumers: one fp32 add
+      if (relu && !(z > 0.f)) dz = 0.f;
+      s0[j] += dz;
+      s1[j] += dz * xh;
+    }
+  }
+};
+
+// conv0 (a ReLU layer): the k rows of a point in closed form from the forward's per-point outputs -- edge_bwd_reduce_points_kernel's
+// row:  sum_m dz = [max > 0] dmax + dmean npos / k,   sum_m dz xhat = [max > 0] dmax (max - beta) + (dmean / k) (k mean - beta npos)
+struct PointTerms {
+  static constexpr int UNROLL = 2;
+  const float* mx; int64_t ldmx;
+  const float* mn; int64_t ldmn;
+  const float* cntpos;
+  const float* dmax; int64_t lddmax;
+  const float* dmean; int64_t lddmean;
+  const float* beta; int k; int F;                              // (cntpos is (rows, F) contiguous)
+  struct Par { float be[4]; };
+  struct Row { float a[4], b[4], c[4], d[4], e[4]; };
+  __device__ __forceinline__ void par(int, int, int c0, Par& p) const { Vec<4>::ld(beta + c0, p.be); }
+  __device__ __forceinline__ void load(int r, int c0, Row& v) const {
+    Vec<4>::ld(mx + (int64_t)r * ldmx + c0, v.a); Vec<4>::ld(mn + (int64_t)r * ldmn + c0, v.b);
+    Vec<4>::ld(cntpos + (int64_t)r * F + c0, v.c);
+    Vec<4>::ld(dmax + (int64_t)r * lddmax + c0, v.d); Vec<4>::ld(dmean + (int64_t)r * lddmean + c0, v.e);
+  }
+  __device__ __forceinline__ void add(const Row& v, const Par& p, float (&s0)[4], float (&s1)[4]) const {
+    const float invk = 1.0f / (float)k, kf = (float)k;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float npos = floorf(v.c[j] * (1.0f / CNT_POS));
+      const float g1 = (v.a[j] > 0.f) ? v.d[j] : 0.f;
+      const float g2 = v.e[j] * invk;
+      s0[j] += g1 + g2 * npos;
+      s1[j] += g1 * (v.a[j] - p.be[j]) + g2 * (kf * v.b[j] - p.be[j] * npos);
+    }
+  }
+};
+
+// ---- stage 1 of both reduces: seg_colstats_partial_kernel's scheme with the integrand TM.  grid = (row chunks, column blocks of
+// 64 * VW); a wave sums its <= 16 rows of a (chunk, cloud) piece in fp32 (ascending), the four waves are added in double (0..3) into
+// part[chunk + b][2][F]; seg_stats_final_kernel adds a cloud's slots.
+template <int VW, class TM>
+__global__ __launch_bounds__(64 * SEG_WAVES) void seg_bwd_partial_kernel(TM tm, int rows, int F, const int32_t* __restrict__ seg_off, int nseg,
+                                                                         double* __restrict__ part) {
+  __shared__ float sv[2][SEG_WAVES][64 * VW];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int c0 = (blockIdx.y * 64 + lane) * VW;
+  const bool col_ok = c0 < F;
+  const int chunk = blockIdx.x;
+  const int r0 = chunk * SEG_CHUNK;
+  const int r1 = imin(r0 + SEG_CHUNK, rows);
+  int b = cloud_of_row(seg_off, nseg, r0);
+  int ps = r0;
+  while (ps < r1 && b < nseg) {
+    const int pe = imin(seg_off[b + 1], r1);
+    float s0[VW], s1[VW];
+#pragma unroll
+    for (int j = 0; j < VW; ++j) { s0[j] = 0.f; s1[j] = 0.f; }
+    if (col_ok) {
+      typename TM::Par p;
+      tm.par(b, F, c0, p);
+      int i = ps + w;
+      for (; i + (TM::UNROLL - 1) * SEG_WAVES < pe; i += TM::UNROLL * SEG_WAVES) {
+        typename TM::Row v[TM::UNROLL];
+#pragma unroll
+        for (int u = 0; u < TM::UNROLL; ++u) tm.load(i + u * SEG_WAVES, c0, v[u]);
+#pragma unroll
+        for (int u = 0; u < TM::UNROLL; ++u) tm.add(v[u], p, s0, s1);
+      }
+      for (; i < pe; i += SEG_WAVES) {
+        typename TM::Row v;
+        tm.load(i, c0, v);
+        tm.add(v, p, s0, s1);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < VW; ++j) { sv[0][w][lane * VW + j] = s0[j]; sv[1][w][lane * VW + j] = s1[j]; }
+    __syncthreads();
+    for (int e = threadIdx.x; e < 2 * 64 * VW; e += 64 * SEG_WAVES) {
+      const int which = e / (64 * VW), cl = e % (64 * VW);
+      const int col = blockIdx.y * 64 * VW + cl;
+      double t = 0.0;
+      for (int ww = 0; ww < SEG_WAVES; ++ww) t += (double)sv[which][ww][cl];
+      if (col < F) part[((int64_t)(chunk + b) * 2 + which) * F + col] = t;
+    }
+    __syncthreads();
+    ps = pe;
+    ++b;
+  }
+}
+
+// ---- c1[b][f] = float(red0 * (1.0 / (n_b k))), c2 likewise (bn_bwd_apply_kernel's constants, per cloud);
+// dbeta[f] = dbeta_beta * dbeta[f] + float(sum_b red0[b][f]), b ascending, in double (bn_bwd_finalize_kernel's dbeta)
+__global__ void seg_bn_bwd_finalize_kernel(const double* __restrict__ red, int nseg, int F, const int32_t* __restrict__ seg_off, int k,
+                                           float* __restrict__ c1, float* __restrict__ c2, float* __restrict__ dbeta, float dbeta_beta) {
+  const int64_t total = (int64_t)nseg * F;
+  GRID_STRIDE(i, total) {
+    const int b = (int)(i / F);
+    const int f = (int)(i % F);
+    const double inv_cnt = 1.0 / ((double)(seg_off[b + 1] - seg_off[b]) * (double)k);
+    c1[i] = (float)(red[((int64_t)b * 2 + 0) * F + f] * inv_cnt);
+    c2[i] = (float)(red[((int64_t)b * 2 + 1) * F + f] * inv_cnt);
+    if (b == 0 && dbeta) {
+      double s = 0.0;
+      for (int bb = 0; bb < nseg; ++bb) s += red[(int64_t)bb * 2 * F + f];
+      dbeta[f] = (dbeta_beta != 0.f) ? (float)s + dbeta_beta * dbeta[f] : (float)s;
+    }
+  }
+}
+
+// ---- k = 1: dT[r] = rstd_g ((dz - c1_g) - xhat c2_g), g = row_group[r]; dT may be T (an item reads its elements before it writes them)
+template <int VW>
+__global__ __launch_bounds__(256) void seg_bn_bwd_apply_kernel(const float* T, int64_t ldt, int64_t rows, int F,
+                                                               const int32_t* __restrict__ row_group, const float* __restrict__ mean,
+                                                               const float* __restrict__ rstd, const float* __restrict__ beta, int relu,
+                                                               const float* __restrict__ dout, int64_t lddo, const float* __restrict__ d2,
+                                                               int64_t ldd2, const float* __restrict__ c1, const float* __restrict__ c2,
+                                                               float* dT, int64_t lddt) {
+  const int FV = F / VW;
+  GRID_STRIDE(it, rows * FV) {
+    const int64_t r = it / FV;
+    const int f = (int)(it % FV) * VW;
+    const int64_t g = row_group[r];
+    float y[VW], d[VW], mu[VW], rs[VW], be[VW], k1[VW], k2[VW], o[VW];
+    Vec<VW>::ld(T + r * ldt + f, y);
+    Vec<VW>::ld(dout + r * lddo + f, d);
+    if (d2) {
+      float e[VW];
+      Vec<VW>::ld(d2 + r * ldd2 + f, e);
+#pragma unroll
+      for (int j = 0; j < VW; ++j) d[j] += e[j];
+    }
+    Vec<VW>::ld(mean + g * F + f, mu); Vec<VW>::ld(rstd + g * F + f, rs); Vec<VW>::ld(beta + f, be);
+    Vec<VW>::ld(c1 + g * F + f, k1); Vec<VW>::ld(c2 + g * F + f, k2);
+#pragma unroll
+    for (int j = 0; j < VW; ++j) {
+      float xh;
+      const float z = bn_z(y[j], mu[j], rs[j], be[j], relu, xh);
+      float dz = d[j];
+      if (relu && !(z > 0.f)) dz = 0.f;
+      o[j] = rs[j] * (dz - k1[j] - xh * k2[j]);
+    }
+    Vec<VW>::st(dT + r * lddt + f, o);
+  }
+}
+
+// ---- conv0: y = V[idx] + U and z recomputed by the forward's instruction sequence (z == mx compares equal to the maximum it took);
+// dz = ((z == mx) ? dmax / ties : 0) + dmean * (1.0f / k), zero where relu and !(z > 0); dY (rows * k, F) and dYsum (rows, F) = the k
+// rows added in ascending m.  The item map of seg_edge_bn_act_kreduce_kernel.
+__global__ __launch_bounds__(256) void seg_edge_bn_bwd_apply_kernel(const float* __restrict__ V, int64_t ldv, const float* __restrict__ U,
+                                                                    int64_t ldu, const int32_t* __restrict__ idx, int64_t rows, int k, int F,
+                                                                    const int32_t* __restrict__ row_group, const float* __restrict__ mean,
+                                                                    const float* __restrict__ rstd, const float* __restrict__ beta, int relu,
+                                                                    const float* __restrict__ dmax, int64_t lddmax,
+                                                                    const float* __restrict__ dmean, int64_t lddmean,
+                                                                    const float* __restrict__ mx_in, int64_t ldmx,
+                                                                    const float* __restrict__ cnt_in, const float* __restrict__ c1,
+                                                                    const float* __restrict__ c2, float* __restrict__ dY,
+                                                                    float* __restrict__ dYsum, int64_t lddysum) {
+  const int FV = F >> 2;
+  const int64_t per = (rows + 7) / 8;
+  const int64_t rb = (int64_t)(blockIdx.x & 7) * per;
+  int64_t nr = rows - rb;
+  nr = nr < 0 ? 0 : (nr > per ? per : nr);
+  const int64_t count = nr * FV;
+  const int64_t step = (int64_t)(gridDim.x >> 3) * blockDim.x;
+  const float invk = 1.0f / (float)k;
+  for (int64_t q = (int64_t)(blockIdx.x >> 3) * blockDim.x + threadIdx.x; q < count; q += step) {
+    const unsigned qu = (unsigned)q;                          // (rows < 2^24, FV <= 256: an eighth of the items fits 32 bits)
+    const int64_t r = rb + qu / (unsigned)FV;
+    const int f = (int)(qu % (unsigned)FV) * 4;
+    const int64_t g = row_group[r];
+    float mu[4], rs[4], be[4], u[4], k1[4], k2[4], dmx[4], dmn[4], mx[4], ties[4], acc[4];
+    Vec<4>::ld(mean + g * F + f, mu); Vec<4>::ld(rstd + g * F + f, rs); Vec<4>::ld(beta + f, be);
+    Vec<4>::ld(c1 + g * F + f, k1); Vec<4>::ld(c2 + g * F + f, k2);
+    Vec<4>::ld(U + r * ldu + f, u);
+    Vec<4>::ld(dmax + r * lddmax + f, dmx); Vec<4>::ld(dmean + r * lddmean + f, dmn);
+    Vec<4>::ld(mx_in + r * ldmx + f, mx); Vec<4>::ld(cnt_in + r * F + f, ties);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      ties[c] -= (float)CNT_POS * floorf(ties[c] * (1.0f / CNT_POS));
+      acc[c] = 0.f;
+    }
+    const int32_t* ip = idx + r * k;
+    const float* vb = V + f;
+    float* dy = dY + (r * k) * F + f;
+    for (int m = 0; m < k; m += 4) {
+      unsigned row[4];
+      float y[4][4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) row[j] = __umul24((unsigned)ip[(m + j < k) ? (m + j) : (k - 1)], (unsigned)ldv);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) Vec<4>::ld(vb + row[j], y[j]);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (m + j < k) {
+          float o[4];
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            float xh;
+            const float z = bn_z(y[j][c] + u[c], mu[c], rs[c], be[c], relu, xh);
+            float dz = ((z == mx[c]) ? dmx[c] / ties[c] : 0.f) + dmn[c] * invk;
+            if (relu && !(z > 0.f)) dz = 0.f;
+            o[c] = rs[c] * (dz - k1[c] - xh * k2[c]);
+            acc[c] += o[c];
+          }
+          Vec<4>::st(dy + (int64_t)(m + j) * F, o);
+        }
+    }
+    if (dYsum) Vec<4>::st(dYsum + r * lddysum + f, acc);
+  }
+}
+
+// workspace check + stage 2 of the two reduces
+int seg_bwd_ws(const char* what, int rows, int nseg, int F, void* ws, size_t ws_bytes) {
+  const size_t need = (size_t)dgcnn_seg_stats_workspace_bytes(rows, nseg, F);
+  DG_REQUIRE(ws && ws_bytes >= need && (reinterpret_cast<uintptr_t>(ws) & 7) == 0, DGCNN_ENOSPC,
+             "%s: workspace too small or not 8-byte aligned (%zu < %zu bytes)", what, ws_bytes, need);
+  return DGCNN_OK;
+}
+
+}  // namespace
+
+extern "C" int dgcnn_seg_bn_bwd_reduce_f32(const float* T, int64_t ldt, int rows, int F, const int32_t* seg_off, int nseg,
+                                           const float* mean, const float* rstd, const float* beta, int relu, const float* dout,
+                                           int64_t lddo, const float* d2, int64_t ldd2, double* red, void* ws, size_t ws_bytes,
+                                           void* stream) {
+  const char* what = "dgcnn_seg_bn_bwd_reduce_f32";
+  DG_REQUIRE(T && seg_off && mean && rstd && beta && dout && red, DGCNN_EINVAL, "%s: null pointer", what);
+  DG_REQUIRE(rows > 0 && F > 0 && nseg > 0 && nseg <= rows && ldt >= F && lddo >= F && (!d2 || ldd2 >= F), DGCNN_EINVAL,
+             "%s: bad shape", what);
+  DG_REQUIRE(relu == 0 || relu == 1, DGCNN_EINVAL, "%s: relu must be 0 or 1 (got %d)", what, relu);
+  int rc = seg_bwd_ws(what, rows, nseg, F, ws, ws_bytes);
   if (rc) return rc;
-  DG_REQUIRE(row_group && mean && rstd && beta && max_out, DGCNN_EINVAL, "dgcnn_seg_edge_bn_act_kreduce_f32: null pointer");
-  DG_REQUIRE(relu == 0 || relu == 1, DGCNN_EINVAL, "dgcnn_seg_edge_bn_act_kreduce_f32: relu must be 0 or 1 (got %d)", relu);
-  DG_REQUIRE(ldmax >= F && ldmax % 4 == 0 && a16(max_out) && a16(mean) && a16(rstd) && a16(beta) &&
-                 (!mean_out || (ldmean >= F && ldmean % 4 == 0 && a16(mean_out))),
-             DGCNN_EINVAL, "dgcnn_seg_edge_bn_act_kreduce_f32: outputs and tables must be 16-byte aligned with leading dimensions %% 4 == 0");
+  double* part = reinterpret_cast<double*>(ws);
+  const unsigned chunks = (unsigned)dg::cdiv(rows, SEG_CHUNK);
+  const bool vec = F % 4 == 0 && ldt % 4 == 0 && lddo % 4 == 0 && a16(T) && a16(dout) && a16(mean) && a16(rstd) && a16(beta) &&
+                   (!d2 || (ldd2 % 4 == 0 && a16(d2)));
+  if (vec) {
+    const K1Terms<4> tm = {T, ldt, mean, rstd, beta, relu, dout, lddo, d2, ldd2};
+    dg::launch((seg_bwd_partial_kernel<4, K1Terms<4>>), dim3(chunks, (unsigned)dg::cdiv(F, 256)), dim3(64 * SEG_WAVES), 0, ST, tm, rows, F,
+               seg_off, nseg, part);
+  } else {
+    const K1Terms<1> tm = {T, ldt, mean, rstd, beta, relu, dout, lddo, d2, ldd2};
+    dg::launch((seg_bwd_partial_kernel<1, K1Terms<1>>), dim3(chunks, (unsigned)dg::cdiv(F, 64)), dim3(64 * SEG_WAVES), 0, ST, tm, rows, F,
+               seg_off, nseg, part);
+  }
+  return seg_stats_final(what, part, seg_off, nseg, F, red, ST);
+}
+
+extern "C" int dgcnn_seg_edge_bn_bwd_reduce_points_f32(const float* mx, int64_t ldmx, const float* mn, int64_t ldmn, const float* cntpos,
+                                                       const float* dmax, int64_t lddmax, const float* dmean, int64_t lddmean,
+                                                       const float* beta, int rows, int k, int F, const int32_t* seg_off, int nseg,
+                                                       double* red, void* ws, size_t ws_bytes, void* stream) {
+  const char* what = "dgcnn_seg_edge_bn_bwd_reduce_points_f32";
+  DG_REQUIRE(mx && mn && cntpos && dmax && dmean && beta && seg_off && red, DGCNN_EINVAL, "%s: null pointer", what);
+  DG_REQUIRE(rows > 0 && k > 0 && F > 0 && nseg > 0 && nseg <= rows, DGCNN_EINVAL, "%s: bad shape", what);
+  DG_REQUIRE(F % 4 == 0 && k < CNT_POS, DGCNN_EUNSUP, "%s: F must be a multiple of 4 (got %d) and k < %d (got %d)", what, F, CNT_POS, k);
+  DG_REQUIRE(a16(mx) && a16(mn) && a16(cntpos) && a16(dmax) && a16(dmean) && a16(beta) && ldmx % 4 == 0 && ldmn % 4 == 0 &&
+                 lddmax % 4 == 0 && lddmean % 4 == 0 && ldmx >= F && ldmn >= F && lddmax >= F && lddmean >= F, DGCNN_EINVAL,
+             "%s: operands must be 16-byte aligned with leading dimensions %% 4 == 0", what);
+  int rc = seg_bwd_ws(what, rows, nseg, F, ws, ws_bytes);
+  if (rc) return rc;
+  double* part = reinterpret_cast<double*>(ws);
+  const unsigned chunks = (unsigned)dg::cdiv(rows, SEG_CHUNK);
+  PointTerms tm = {mx, ldmx, mn, ldmn, cntpos, dmax, lddmax, dmean, lddmean, beta, k, F};
+  dg::launch((seg_bwd_partial_kernel<4, PointTerms>), dim3(chunks, (unsigned)dg::cdiv(F, 256)), dim3(64 * SEG_WAVES), 0, ST, tm, rows, F,
+             seg_off, nseg, part);
+  return seg_stats_final(what, part, seg_off, nseg, F, red, ST);
+}
+
+extern "C" int dgcnn_seg_bn_bwd_finalize_f32(const double* red, int nseg, int F, const int32_t* seg_off, int k, float* c1, float* c2,
+                                             float* dbeta, float dbeta_beta, void* stream) {
+  DG_REQUIRE(red && seg_off && c1 && c2 && nseg > 0 && F > 0 && k > 0, DGCNN_EINVAL, "dgcnn_seg_bn_bwd_finalize_f32: bad args");
+  dg::launch(seg_bn_bwd_finalize_kernel, dim3(grid1d((int64_t)nseg * F)), dim3(256), 0, ST, red, nseg, F, seg_off, k, c1, c2, dbeta,
+             dbeta_beta);
+  return dg::check_launch("dgcnn_seg_bn_bwd_finalize_f32");
+}
+
+extern "C" int dgcnn_seg_bn_bwd_apply_f32(const float* T, int64_t ldt, int rows, int F, const int32_t* row_group, const float* mean,
+                                          const float* rstd, const float* beta, int relu, const float* dout, int64_t lddo,
+                                          const float* d2, int64_t ldd2, const float* c1, const float* c2, float* dT, int64_t lddt,
+                                          void* stream) {
+  const char* what = "dgcnn_seg_bn_bwd_apply_f32";
+  DG_REQUIRE(T && row_group && mean && rstd && beta && dout && c1 && c2 && dT, DGCNN_EINVAL, "%s: null pointer", what);
+  DG_REQUIRE(rows > 0 && F > 0 && ldt >= F && lddo >= F && lddt >= F && (!d2 || ldd2 >= F), DGCNN_EINVAL, "%s: bad shape", what);
+  DG_REQUIRE(relu == 0 || relu == 1, DGCNN_EINVAL, "%s: relu must be 0 or 1 (got %d)", what, relu);
+  const bool vec = F % 4 == 0 && ldt % 4 == 0 && lddo % 4 == 0 && lddt % 4 == 0 && a16(T) && a16(dout) && a16(dT) && a16(mean) &&
+                   a16(rstd) && a16(beta) && a16(c1) && a16(c2) && (!d2 || (ldd2 % 4 == 0 && a16(d2)));
+  if (vec)
+    dg::launch(seg_bn_bwd_apply_kernel<4>, dim3(grid_items((int64_t)rows * (F / 4))), dim3(256), 0, ST, T, ldt, (int64_t)rows, F, row_group,
+               mean, rstd, beta, relu, dout, lddo, d2, ldd2, c1, c2, dT, lddt);
+  else
+    dg::launch(seg_bn_bwd_apply_kernel<1>, dim3(grid_items((int64_t)rows * F)), dim3(256), 0, ST, T, ldt, (int64_t)rows, F, row_group, mean,
+               rstd, beta, relu, dout, lddo, d2, ldd2, c1, c2, dT, lddt);
+  return dg::check_launch(what);
+}
+
+extern "C" int dgcnn_seg_edge_bn_bwd_apply_f32(const float* V, int64_t ldv, const float* U, int64_t ldu, const int32_t* idx, int rows, int k,
+                                               int F, const int32_t* row_group, const float* mean, const float* rstd, const float* beta,
+                                               int relu, const float* dmax, int64_t lddmax, const float* dmean, int64_t lddmean,
+                                               const float* mx_in, int64_t ldmx, const float* cnt_in, const float* c1, const float* c2,
+                                               float* dY, float* dYsum, int64_t lddysum, void* stream) {
+  const char* what = "dgcnn_seg_edge_bn_bwd_apply_f32";
+  int rc = check_seg_edge(what, V, ldv, U, ldu, idx, rows, k, F);
+  if (rc) return rc;
+  DG_REQUIRE(row_group && mean && rstd && beta && dmax && dmean && mx_in && cnt_in && c1 && c2 && dY, DGCNN_EINVAL, "%s: null pointer",
+             what);
+  DG_REQUIRE(relu == 0 || relu == 1, DGCNN_EINVAL, "%s: relu must be 0 or 1 (got %d)", what, relu);
+  DG_REQUIRE(k < CNT_POS, DGCNN_EUNSUP, "%s: k must be < %d (the packed tie / positive counts)", what, CNT_POS);
+  DG_REQUIRE(a16(mean) && a16(rstd) && a16(beta) && a16(c1) && a16(c2) && a16(dmax) && a16(dmean) && a16(mx_in) && a16(cnt_in) && a16(dY) &&
+                 lddmax >= F && lddmax % 4 == 0 && lddmean >= F && lddmean % 4 == 0 && ldmx >= F && ldmx % 4 == 0 &&
+                 (!dYsum || (a16(dYsum) && lddysum >= F && lddysum % 4 == 0)),
+             DGCNN_EINVAL, "%s: operands and tables must be 16-byte aligned with leading dimensions %% 4 == 0", what);
   const unsigned grid = (grid_items((int64_t)rows * (F / 4)) + 7u) & ~7u;     // (the XCD item map needs a multiple of 8)
-  dg::launch(seg_edge_bn_act_kreduce_kernel, dim3(grid), dim3(256), 0, ST, V, ldv, U, ldu, idx, (int64_t)rows, k, F, row_group, mean, rstd,
-             beta, relu, max_out, ldmax, mean_out, ldmean);
-  return dg::check_launch("dgcnn_seg_edge_bn_act_kreduce_f32");
+  dg::launch(seg_edge_bn_bwd_apply_kernel, dim3(grid), dim3(256), 0, ST, V, ldv, U, ldu, idx, (int64_t)rows, k, F, row_group, mean, rstd, beta,
+             relu, dmax, lddmax, dmean, lddmean, mx_in, ldmx, cnt_in, c1, c2, dY, dYsum, lddysum);
+  return dg::check_launch(what);
 }

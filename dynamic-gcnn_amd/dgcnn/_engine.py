@@ -513,9 +513,11 @@ class Segments(object):
     host offsets (validated here, before any device work), their device copy and the row -> cloud map row_group[r] = b (each made
     once, on the host, on first use) and the smallest / largest cloud, from which the k-NN picks its kernel forms.
     bn_per_cloud: every BatchNorm of the tower takes the statistics of the row's own cloud instead of all rows (csrc/seg_bn.hip;
-    forward only) -- the mode travels with the `seg=` every pass already receives."""
+    forward only) -- the mode travels with the `seg=` every pass already receives.
+    bn_per_cloud_train: the same mode WITH its backward (a recording is allowed); implies bn_per_cloud.  Two settings, because the
+    forward-only one keeps refusing a recording exactly as it did before the backward existed."""
 
-    def __init__(self, offsets, rows=None, bn_per_cloud=False):
+    def __init__(self, offsets, rows=None, bn_per_cloud=False, bn_per_cloud_train=False):
         if isinstance(offsets, torch.Tensor):
             offsets = offsets.detach().cpu().numpy()
         off = np.asarray(offsets)
@@ -535,7 +537,8 @@ class Segments(object):
         self.min_n, self.max_n = int(sizes.min()), int(sizes.max())
         self._dev = None
         self._rg = None
-        self.bn_per_cloud = bool(bn_per_cloud)
+        self.bn_per_cloud_train = bool(bn_per_cloud_train)
+        self.bn_per_cloud = bool(bn_per_cloud) or self.bn_per_cloud_train
 
     def check_k(self, k):
         if k <= 0 or k > self.min_n:
@@ -722,11 +725,11 @@ def seg_colsum(x, seg, out):
 
 
 def per_cloud(seg):
-    """True when `seg` is a packed tower whose BatchNorm runs per cloud.  The mode has no backward: inside a recording it raises
-    here, on the host, before anything is launched."""
+    """True when `seg` is a packed tower whose BatchNorm runs per cloud.  Without seg.bn_per_cloud_train the mode is forward only:
+    inside a recording it raises here, on the host, before anything is launched."""
     if seg is None or not seg.bn_per_cloud:
         return False
-    if ctx().recording:
+    if ctx().recording and not seg.bn_per_cloud_train:
         raise NotImplementedError("per-cloud BatchNorm has no backward yet")
     return True
 
@@ -747,6 +750,15 @@ def seg_bn_finalize(stats, seg, F, k):
     H.call("dgcnn_seg_bn_finalize_f32", stats.data_ptr(), seg.nseg, F, seg.device(dev).data_ptr(), int(k), BN_EPS,
            mr[0].data_ptr(), mr[1].data_ptr())
     return mr[0], mr[1]
+
+
+def seg_bn_bwd_finalize(red, seg, F, k, dbeta):
+    """(c1, c2), each (nseg, F): cloud b's sums over its count n_b * k; dbeta += the sum of red0 over the clouds."""
+    dev = red.device
+    cc = torch.empty((2, seg.nseg, F), dtype=torch.float32, device=dev)
+    H.call("dgcnn_seg_bn_bwd_finalize_f32", red.data_ptr(), seg.nseg, F, seg.device(dev).data_ptr(), int(k), cc[0].data_ptr(),
+           cc[1].data_ptr(), dbeta.data_ptr(), 1.0)
+    return cc[0], cc[1]
 
 
 def bn_finalize(stats, F, count):
@@ -772,7 +784,7 @@ def conv_bn_act(x, leaf_scope, num_outputs, relu=True, out=None, out2=None, gbia
     drop_keep: tf.nn.dropout(out, drop_keep) behind the layer (model.py:90-91), fused into the BatchNorm passes where the
     kernels allow it (the returned tensor is the DROPPED output either way).
     seg: a packed tower (Segments; x holds its seg.rows rows).  BatchNorm runs over all rows as in a dense tower (seg.bn_per_cloud:
-    over the rows of each cloud alone, _conv_bn_act_per_cloud -- forward only); what is per
+    over the rows of each cloud alone, _conv_bn_act_per_cloud -- recorded only with seg.bn_per_cloud_train); what is per
     cloud goes through the segmented kernels (csrc/seg.hip): gbias is (nseg, Cout) and is addressed through the row -> cloud map
     (rpg is ignored), its gradient is the per-cloud column sum, gmax (any value but None) is the max-pool over each cloud's own
     rows -- always the separate pass over the GEMM output, never the epilogue.  The plane mode is NOT packed: a packed tower
@@ -793,7 +805,7 @@ def conv_bn_act(x, leaf_scope, num_outputs, relu=True, out=None, out2=None, gbia
         bname, beta = c.get_variable("BatchNorm/beta", (num_outputs,))
     F = num_outputs
     if bpc:
-        return _conv_bn_act_per_cloud(c, x, Wx, beta, F, relu, out, out2, gbias, rgrp, arith, gmax, drop_keep, seg)
+        return _conv_bn_act_per_cloud(c, x, Wx, beta, F, relu, out, out2, gbias, rgrp, arith, gmax, drop_keep, seg, wname, w_rows, bname)
     T = torch.empty((R, F), dtype=torch.float32, device=x.device)
     # slots of this layer's statistics buffer = row tiles of its GEMM (asked from the library; another arithmetic: the step's maximum)
     # (0 = a kernel whose grid FOLLOWS the slot count -- the class dimension's streaming product: the step's maximum, more writers)
@@ -980,11 +992,14 @@ def conv_bn_act(x, leaf_scope, num_outputs, relu=True, out=None, out2=None, gbia
     return out, g
 
 
-def _conv_bn_act_per_cloud(c, x, Wx, beta, F, relu, out, out2, gbias, rgrp, arith, gmax, drop_keep, seg):
-    """conv_bn_act of a packed tower with per-cloud BatchNorm (forward only).  The GEMM runs WITHOUT epilogue statistics (a row
+def _conv_bn_act_per_cloud(c, x, Wx, beta, F, relu, out, out2, gbias, rgrp, arith, gmax, drop_keep, seg, wname, w_rows, bname):
+    """conv_bn_act of a packed tower with per-cloud BatchNorm.  The GEMM runs WITHOUT epilogue statistics (a row
     tile straddles clouds; the per-cloud bias through the row -> cloud map stays); then the per-cloud sums of T in a fixed
     order, the (nseg, F) tables and the apply pass that picks the table row of the row's cloud.  gmax: the per-cloud maxima of T
-    are normalised with their own cloud's table row -- BN + ReLU are monotone per cloud, so the max-pool identity holds."""
+    are normalised with their own cloud's table row -- BN + ReLU are monotone per cloud, so the max-pool identity holds.
+    Recording (seg.bn_per_cloud_train): one tape closure -- per-cloud sum dz / sum dz xhat (both gradient inputs read in place),
+    the c1 / c2 tables (+ dbeta), dT in place of T, then the dense branch's products: dx first, dW on the side stream, the
+    per-cloud bias gradient (mathematically 0 per cloud -- the literal form, as the forward keeps the bias in T)."""
     R = x.shape[0]
     dev = x.device
     off = seg.device(dev)
@@ -1001,6 +1016,35 @@ def _conv_bn_act_per_cloud(c, x, Wx, beta, F, relu, out, out2, gbias, rgrp, arit
     H.call("dgcnn_seg_bn_act_f32", T.data_ptr(), H.ld2(T), R, F, rg.data_ptr(), mean.data_ptr(), rstd.data_ptr(), beta.data_ptr(),
            int(relu), out.data_ptr(), H.ld2(out), H._p(out2), 0 if out2 is None else H.ld2(out2),
            tag="seg_bn_act_kernel", work=4.0 * R * F * (2 if out2 is None else 3))
+    if c.recording:
+        def bwd():
+            dout = c.grad(out)
+            if dout is None:
+                return
+            d2 = c.grad(out2) if out2 is not None else None
+            nsrc = 1 if d2 is None else 2
+            red = torch.empty(seg.nseg * 2 * F, dtype=torch.float64, device=dev)
+            wsb = seg_stats_workspace(R, seg.nseg, F, dev)
+            par = (mean.data_ptr(), rstd.data_ptr(), beta.data_ptr(), int(relu), dout.data_ptr(), H.ld2(dout), H._p(d2),
+                   0 if d2 is None else H.ld2(d2))
+            H.call("dgcnn_seg_bn_bwd_reduce_f32", T.data_ptr(), H.ld2(T), R, F, off.data_ptr(), seg.nseg, *par, red.data_ptr(),
+                   wsb.data_ptr(), wsb.numel(), tag="seg_bn_bwd_reduce_kernel", work=4.0 * R * F * (1 + nsrc))
+            c1, c2 = seg_bn_bwd_finalize(red, seg, F, 1, c.var_grads[bname])
+            H.call("dgcnn_seg_bn_bwd_apply_f32", T.data_ptr(), H.ld2(T), R, F, rg.data_ptr(), *par, c1.data_ptr(), c2.data_ptr(),
+                   T.data_ptr(), H.ld2(T), tag="seg_bn_bwd_apply_kernel", work=4.0 * R * F * (2 + nsrc))
+            dT = T
+            dWx = c.var_grads[wname] if w_rows is None else c.var_grads[wname][w_rows[0]:w_rows[1]]
+            dgb = c.grad(gbias) if gbias is not None else None
+            dx, bx = c.grad_w(x)
+            if dx is not None:
+                gemm(dT, Wx, dx, transB=True, beta=bx, arith=arith)    # dx (+)= dT W^T: on the critical path, first
+            with c.off_critical_path(rows=R):
+                gemm(x, dT, dWx, transA=True, beta=1.0, arith=arith)   # dW += x^T dT
+            if dgb is not None:                                         # tf.tile^T: sum over the cloud
+                tmp = torch.empty_like(gbias)
+                seg_colsum(dT, seg, tmp)
+                H.call("dgcnn_axpby_f32", tmp.data_ptr(), 1.0, dgb.data_ptr(), 1.0, tmp.numel())
+        c.tape.append(bwd)
     if gmax is None:
         return out if drop_keep is None else dropout(out, drop_keep)
     keys = c.stats_raw(seg.nseg * F)                                          # zeroed uint64[nseg][F]
@@ -1012,6 +1056,14 @@ def _conv_bn_act_per_cloud(c, x, Wx, beta, F, relu, out, out2, gbias, rgrp, arit
     g = c.new_buffer(seg.nseg, F)
     H.call("dgcnn_seg_bn_act_f32", graw.data_ptr(), F, seg.nseg, F, None, mean.data_ptr(), rstd.data_ptr(), beta.data_ptr(),
            int(relu), g.data_ptr(), F, None, 0)
+    if c.recording:
+        def bwd_g():
+            dg_, dout = c.grad(g), c.grad(out)
+            if dg_ is None or dout is None:
+                return
+            H.call("dgcnn_global_max_bwd_seg_f32", dg_.data_ptr(), arg.data_ptr(), off.data_ptr(), seg.nseg, F, dout.data_ptr(),
+                   H.ld2(dout))
+        c.tape.append(bwd_g)
     return out, g
 
 
@@ -1108,13 +1160,63 @@ def build_csr(idx, B, N, k, side=None):
     return off, (rev if srt is None else srt)
 
 
+def _edge_conv_record_per_cloud(c, x, C, k, F, seg, idx, esrc, UV, Cp, xg, wcat, mean, rstd, beta0, w0name, b0name, mm):
+    """conv0's BN + ReLU + max / mean of a packed tower with per-cloud statistics, inside a recording: the forward pass that also
+    keeps the packed tie / positive counts, and the tape closure -- per-cloud sums from the per-point outputs (no pass over the
+    edges), the c1 / c2 tables (+ dbeta), dY and dU = sum_m dY, dV = the incoming sum, then the gather branch's tail
+    (dx += [dU | dV] Wcat^T, dWcat = X^T [dU | dV] on the side stream).  UV stays referenced: esrc holds raw pointers into it."""
+    R = x.shape[0]
+    dev = x.device
+    off, rg = seg.device(dev), seg.row_group(dev)
+    mx, mn = mm[:, :F], mm[:, F:]
+    cnt = torch.empty((R, F), dtype=torch.float32, device=dev)             # ties of the max + 256 * positives
+    H.call("dgcnn_seg_edge_bn_act_kreduce_cnt_f32", *esrc, rg.data_ptr(), mean.data_ptr(), rstd.data_ptr(), beta0.data_ptr(), 1,
+           mx.data_ptr(), H.ld2(mx), mn.data_ptr(), H.ld2(mn), cnt.data_ptr(),
+           tag="seg_edge_bn_act_kreduce_kernel<cnt>", work=4.0 * (5 * R * F) + 4.0 * R * k, nbytes=4.0 * (R * k * F + R * F))   # ops.py:54-58
+    csr = None
+    if WGRAD_SIDE_STREAM and R >= SIDE_STREAM_MIN_ROWS:
+        csr = build_csr(idx, 1, R, k, side=(c, R))      # depends on idx only: built now, off the critical path
+
+    def bwd():
+        assert UV is not None
+        dmm = c.grad(mm)
+        if dmm is None:
+            return
+        dmx, dmn = dmm[:, :F], dmm[:, F:]
+        red = torch.empty(seg.nseg * 2 * F, dtype=torch.float64, device=dev)
+        wsb = seg_stats_workspace(R, seg.nseg, F, dev)
+        H.call("dgcnn_seg_edge_bn_bwd_reduce_points_f32", mx.data_ptr(), H.ld2(mx), mn.data_ptr(), H.ld2(mn), cnt.data_ptr(),
+               dmx.data_ptr(), H.ld2(dmx), dmn.data_ptr(), H.ld2(dmn), beta0.data_ptr(), R, k, F, off.data_ptr(), seg.nseg,
+               red.data_ptr(), wsb.data_ptr(), wsb.numel(), tag="seg_edge_bwd_reduce_points_kernel", work=4.0 * 5 * R * F)
+        c1, c2 = seg_bn_bwd_finalize(red, seg, F, k, c.var_grads[b0name])
+        dUV = torch.empty((R, 2 * F), dtype=torch.float32, device=dev)     # [dU | dV]
+        dY = torch.empty((R * k, F), dtype=torch.float32, device=dev)
+        H.call("dgcnn_seg_edge_bn_bwd_apply_f32", *esrc, rg.data_ptr(), mean.data_ptr(), rstd.data_ptr(), beta0.data_ptr(), 1,
+               dmx.data_ptr(), H.ld2(dmx), dmn.data_ptr(), H.ld2(dmn), mx.data_ptr(), H.ld2(mx), cnt.data_ptr(), c1.data_ptr(),
+               c2.data_ptr(), dY.data_ptr(), dUV.data_ptr(), 2 * F, tag="seg_edge_bn_bwd_apply_kernel",
+               work=4.0 * (R * k * F + 7 * R * F) + 4.0 * R * k, nbytes=4.0 * (R * k * F + R * F))
+        offt, rev = csr if csr is not None else build_csr(idx, 1, R, k)
+        S = dUV[:, F:]
+        H.call("dgcnn_edge_gather_sum_f32", dY.data_ptr(), offt.data_ptr(), rev.data_ptr(), R, F, S.data_ptr(), H.ld2(S),
+               tag="csr_gather_sum_kernel", work=4.0 * (R * k * F + R * F))
+        dwcat = torch.empty((Cp, 2 * F), dtype=torch.float32, device=dev)
+        dx = c.grad(x)
+        if dx is not None:                                                  # (layer 0, raw coordinates: nobody wants d(points))
+            gemm(dUV, wcat[:C], dx, transB=True, beta=1.0, arith=None)
+        with c.off_critical_path(dwcat, dUV, rows=R):
+            gemm(xg, dUV, dwcat, transA=True, arith=None)
+            H.call("dgcnn_edge_wgrad_combine_f32", dwcat.data_ptr(), C, F, c.var_grads[w0name].data_ptr())
+    c.tape.append(bwd)
+
+
 def edge_conv_block(x, B, N, k, num_filters, relu1=True, outs=None, net2=None, seed=None, seg=None):
     """x: (B*N, C) view.  Returns (mm, net, idx): mm = (R,2F) [max | mean], net = (R,64).
     outs = (mm_view, net_view) destination slices (model path) or None (fresh buffers).
     seed: the previous EdgeConv layer's graph (B,N,k') or None: seeds this layer's k-NN filter (same result, fewer inserts).
     seg: a packed tower (Segments) with B = 1, N = R: only the k-NN is tied to a cloud (idx holds tower rows), every other pass is
     row-wise -- BatchNorm statistics run over all rows of the tower, as in a dense (B, N) tower; seg.bn_per_cloud: over the rows
-    (conv0: the edges) of each cloud alone -- forward only, and only the default form of conv0 (the fold with the virtual Y)."""
+    (conv0: the edges) of each cloud alone -- only the default form of conv0 (the fold with the virtual Y); recorded only with
+    seg.bn_per_cloud_train (the general backward: dY is written, the fused layer-0 pass has no per-cloud form)."""
     c = ctx()
     R, C = x.shape
     F = int(num_filters)
@@ -1141,7 +1243,7 @@ def edge_conv_block(x, B, N, k, num_filters, relu1=True, outs=None, net2=None, s
     if bpc:
         dev = x.device
         idx = knn(x, B, N, k, seed=seed, seg=seg)                           # ops.py:8-19
-        _, _, _, UV = _point_gemm(c, x, W0, R, C, F)                        # [U | V] = X [Wa-Wb | Wb]
+        Cp, xg, wcat, UV = _point_gemm(c, x, W0, R, C, F)                   # [U | V] = X [Wa-Wb | Wb]
         esrc = (UV[:, F:].data_ptr(), 2 * F, UV.data_ptr(), 2 * F, idx.data_ptr(), R, k, F)
         st = torch.empty(seg.nseg * 2 * F, dtype=torch.float64, device=dev)
         ws = seg_stats_workspace(R, seg.nseg, F, dev)
@@ -1153,9 +1255,12 @@ def edge_conv_block(x, B, N, k, num_filters, relu1=True, outs=None, net2=None, s
         else:
             mm, net_out = outs
         mx, mn = mm[:, :F], mm[:, F:]
-        H.call("dgcnn_seg_edge_bn_act_kreduce_f32", *esrc, seg.row_group(dev).data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-               beta0.data_ptr(), 1, mx.data_ptr(), H.ld2(mx), mn.data_ptr(), H.ld2(mn),
-               tag="seg_edge_bn_act_kreduce_kernel", work=4.0 * (4 * R * F) + 4.0 * R * k, nbytes=4.0 * (R * k * F + R * F))   # ops.py:54-58
+        if not c.recording:
+            H.call("dgcnn_seg_edge_bn_act_kreduce_f32", *esrc, seg.row_group(dev).data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                   beta0.data_ptr(), 1, mx.data_ptr(), H.ld2(mx), mn.data_ptr(), H.ld2(mn),
+                   tag="seg_edge_bn_act_kreduce_kernel", work=4.0 * (4 * R * F) + 4.0 * R * k, nbytes=4.0 * (R * k * F + R * F))   # ops.py:54-58
+        else:
+            _edge_conv_record_per_cloud(c, x, C, k, F, seg, idx, esrc, UV, Cp, xg, wcat, mean, rstd, beta0, w0name, b0name, mm)
         net = conv_bn_act(mm, "conv1", 64, relu=relu1, out=net_out, out2=net2, arith=None, seg=seg)   # ops.py:62-70
         return mm, net, idx
     c.push_slots(c.step_slots)                   # conv0's statistics come from passes whose grids FOLLOW the slot count: the maximum

@@ -117,6 +117,17 @@ PROTOTYPES = {
     "dgcnn_seg_bn_act_f32": [c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_vp, c_i64, c_vp],
     "dgcnn_seg_edge_bn_act_kreduce_f32": [c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int,
                                           c_vp, c_i64, c_vp, c_i64, c_vp],
+    "dgcnn_seg_edge_bn_act_kreduce_cnt_f32": [c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int,
+                                              c_vp, c_i64, c_vp, c_i64, c_vp, c_vp],
+    "dgcnn_seg_bn_bwd_reduce_f32": [c_vp, c_i64, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_vp, c_i64, c_vp,
+                                    c_vp, c_sz, c_vp],
+    "dgcnn_seg_edge_bn_bwd_reduce_points_f32": [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_int, c_int,
+                                                c_vp, c_int, c_vp, c_vp, c_sz, c_vp],
+    "dgcnn_seg_bn_bwd_finalize_f32": [c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_f32, c_vp],
+    "dgcnn_seg_bn_bwd_apply_f32": [c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp,
+                                   c_vp, c_i64, c_vp],
+    "dgcnn_seg_edge_bn_bwd_apply_f32": [c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_i64,
+                                        c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
     "dgcnn_dropout_f32": [c_vp, c_vp, c_i64, c_f32, c_u64, c_vp],
     "dgcnn_dropout_dev_f32": [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp],
     "dgcnn_add_relu_f32": [c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_vp, c_i64, c_vp],

@@ -59,7 +59,14 @@ _OPTIONS = [
                                                "tower (clouds concatenated row-wise, per-cloud neighbours / max-pool) instead of being refused"),
     ("BN_PER_CLOUD", "-bpc", _BOOL, False, "i", "every BatchNorm of a tower of several clouds takes the statistics of the row's own cloud: "
                                                 "the predictions of -mbs 1, whatever shares the micro-batch (inference only)"),
+    ("BN_PER_CLOUD_TRAIN", "-bpct", _BOOL, False, "t", "per-cloud BatchNorm (BN_PER_CLOUD) with its backward: a tower of several clouds "
+                                                       "trains -- and validates -- cloud by cloud, as -mbs 1 does"),
 ]
+
+
+class _InferenceOnly(argparse.Action):
+    def __call__(self, parser, namespace, values, option_string=None):
+        parser.error("%s is offered by `inference` only; `train` takes --bn_per_cloud_train" % option_string)
 
 
 class DGCNN_FLAGS(object):
@@ -87,6 +94,10 @@ class DGCNN_FLAGS(object):
                 if key in where:
                     names = ([short] if short else []) + ["--" + attr.lower()]
                     p.add_argument(*names, type=typ, default=default, help="%s [default: %s]" % (text, default))
+            if key == "t":
+                # argparse would read the inference-only spelling as an abbreviation of --bn_per_cloud_train: keep refusing it
+                p.add_argument("-bpc", "--bn_per_cloud", action=_InferenceOnly, nargs="?", default=argparse.SUPPRESS,
+                               help=argparse.SUPPRESS)
         return parser
 
     def parse_args(self, argv=None, run=True):

@@ -14,10 +14,11 @@ identical results up to fp32 rounding:
 csrc/seg.hip); BatchNorm statistics run over all R rows, as over the B*N rows of a dense tower.  Not packed: the plane mode of
 the head GEMMs (a packed tower runs the fp32-class GEMMs whatever HEAD_PLANES says).
 
-flags.BN_PER_CLOUD (inference only: the mode has no backward yet): every BatchNorm of a packed tower takes the statistics of the
-row's own cloud (csrc/seg_bn.hip), so the logits of a cloud are those of `build` on that cloud alone -- what the reference computes
-at `-mbs 1`, where a tower IS one cloud -- whichever clouds share its tower.  A dense (B, N, C) input with B > 1 runs as the packed
-tower with offsets b * N; B = 1 is per cloud already and keeps the dense path.
+flags.BN_PER_CLOUD (inference only) / flags.BN_PER_CLOUD_TRAIN (with the backward: TRAIN true or false): every BatchNorm of a
+packed tower takes the statistics of the row's own cloud (csrc/seg_bn.hip), so the logits of a cloud are those of `build` on that
+cloud alone -- what the reference computes at `-mbs 1`, where a tower IS one cloud -- whichever clouds share its tower.  A dense
+(B, N, C) input with B > 1 runs as the packed tower with offsets b * N; B = 1 is per cloud already and keeps the dense path.
+BN_PER_CLOUD alone keeps refusing TRAIN=True and a recording, as it did before the backward existed.
 """
 from __future__ import annotations
 
@@ -43,20 +44,21 @@ def build(point_cloud, flags, offsets=None):
         raise NotImplementedError("Unsupported MODEL_NAME: %s" % flags.MODEL_NAME)     # model.py:41-43
 
     ecf = ops._listify(num_edge_filters, num_edge_conv, "num_filters")
-    bpc = bool(getattr(flags, "BN_PER_CLOUD", False))
+    bpct = bool(getattr(flags, "BN_PER_CLOUD_TRAIN", False))
+    bpc = bool(getattr(flags, "BN_PER_CLOUD", False)) or bpct
     if bpc:
-        if is_training or c.recording:
+        if (is_training or c.recording) and not bpct:
             raise NotImplementedError("per-cloud BatchNorm has no backward yet: BN_PER_CLOUD is an inference mode (TRAIN=False)")
         if offsets is None:
             x0, B0, N0 = E.as2d(point_cloud)
             if B0 > 1:                                             # equal-sized clouds: the packed tower with offsets b * N
                 return build(x0, flags, offsets=np.arange(B0 + 1, dtype=np.int64) * N0).view(B0, N0, num_class)
-        elif isinstance(offsets, E.Segments) and not offsets.bn_per_cloud:
-            offsets = E.Segments(offsets.host, bn_per_cloud=True)
+        elif isinstance(offsets, E.Segments) and not (offsets.bn_per_cloud_train if bpct else offsets.bn_per_cloud):
+            offsets = E.Segments(offsets.host, bn_per_cloud=True, bn_per_cloud_train=bpct)
     seg = None
     if offsets is not None:
         # every check of the packed tower -- shape, offsets, each layer's k against the smallest cloud -- on the host, before any launch
-        seg = ops._segments(point_cloud, offsets, ops._listify(k, num_edge_conv, "k"), bn_per_cloud=bpc)
+        seg = ops._segments(point_cloud, offsets, ops._listify(k, num_edge_conv, "k"), bn_per_cloud=bpc, bn_per_cloud_train=bpct)
     x, B, N = E.as2d(point_cloud)
     R = B * N
     c.configure_slots(R)                                           # (DETERMINISTIC: one writer per statistics slot)

@@ -26,12 +26,13 @@ def _is_relu(activation):
     raise NotImplementedError("only relu / None activations exist in the reference (ops.py:42,123)")
 
 
-def _segments(points, offsets, ks, bn_per_cloud=False):
+def _segments(points, offsets, ks, bn_per_cloud=False, bn_per_cloud_train=False):
     """Host-side checks of a packed tower, before any device work: points (R,C), (1,R,C) or (1,R,1,C); offsets (nseg + 1 ints from
     0 to R, strictly increasing) or a Segments; every k at most the smallest cloud.  Returns None for a dense tower (offsets None).
-    bn_per_cloud: BatchNorm with each cloud's own statistics (forward only) -- needs offsets; a Segments keeps its own setting."""
+    bn_per_cloud: BatchNorm with each cloud's own statistics (forward only) -- needs offsets; a Segments keeps its own setting.
+    bn_per_cloud_train: the same with its backward (allowed inside a recording); implies bn_per_cloud."""
     if offsets is None:
-        if bn_per_cloud:
+        if bn_per_cloud or bn_per_cloud_train:
             raise ValueError("bn_per_cloud=True needs offsets: per-cloud BatchNorm is a mode of a packed tower")
         return None
     shp = tuple(points.shape)
@@ -39,7 +40,8 @@ def _segments(points, offsets, ks, bn_per_cloud=False):
         R = shp[0] if len(shp) == 2 else shp[1]
     else:
         raise ValueError("a packed tower is (R,C), (1,R,C) or (1,R,1,C), got %s" % (shp,))
-    seg = offsets if isinstance(offsets, E.Segments) else E.Segments(offsets, R, bn_per_cloud=bn_per_cloud)
+    seg = offsets if isinstance(offsets, E.Segments) else E.Segments(offsets, R, bn_per_cloud=bn_per_cloud,
+                                                                               bn_per_cloud_train=bn_per_cloud_train)
     if seg.rows != R:
         raise ValueError("offsets end at %d, the tower has %d rows" % (seg.rows, R))
     for k in ks:
@@ -77,14 +79,15 @@ def edges(points, k=20, offsets=None):
 
 
 def edge_conv(point_cloud, k, num_filters, trainable, activation=relu, debug=False, _outs=None, _net2=None, _seed=None,
-              offsets=None, bn_per_cloud=False):
+              offsets=None, bn_per_cloud=False, bn_per_cloud_train=False):
     """dgcnn/ops.py:42-73.  Returns the list [net_max, net_mean, net], each (B,N,1,ch).
     _seed: the previous layer's neighbour graph (the stacks pass it): only speeds this layer's k-NN up.
     offsets: a packed tower (k_nn): the neighbours come from the row's own cloud, every other pass (BatchNorm included) runs over
     all R rows as in a dense tower; outputs (1,R,1,ch).
     bn_per_cloud (with offsets; forward only): both BatchNorms take the statistics of the row's own cloud, so a cloud's outputs do
-    not depend on the other clouds of the tower."""
-    seg = _segments(point_cloud, offsets, [k], bn_per_cloud)
+    not depend on the other clouds of the tower.
+    bn_per_cloud_train (with offsets): the same mode with its backward -- the call may be recorded."""
+    seg = _segments(point_cloud, offsets, [k], bn_per_cloud, bn_per_cloud_train)
     x, B, N = E.as2d(point_cloud)
     F = int(num_filters)
     mm, net, idx = E.edge_conv_block(x, B, N, int(k), F, relu1=_is_relu(activation), outs=_outs, net2=_net2, seed=_seed, seg=seg)
@@ -108,13 +111,14 @@ def _listify(v, repeat, what):
     return [int(v)] * repeat
 
 
-def repeat_edge_conv(point_cloud, repeat, k, num_filters, trainable, debug=False, _plan=None, offsets=None, bn_per_cloud=False):
+def repeat_edge_conv(point_cloud, repeat, k, num_filters, trainable, debug=False, _plan=None, offsets=None, bn_per_cloud=False,
+                     bn_per_cloud_train=False):
     """dgcnn/ops.py:75-98.  Flat list of 3*repeat tensors; layer i+1 builds its k-NN graph on
-    squeeze(tensors[-1]) -- the dynamic graph.  offsets / bn_per_cloud: a packed tower (edge_conv)."""
+    squeeze(tensors[-1]) -- the dynamic graph.  offsets / bn_per_cloud / bn_per_cloud_train: a packed tower (edge_conv)."""
     repeat = int(repeat)
     k = _listify(k, repeat, "k")
     num_filters = _listify(num_filters, repeat, "num_filters")
-    seg = _segments(point_cloud, offsets, k, bn_per_cloud)
+    seg = _segments(point_cloud, offsets, k, bn_per_cloud, bn_per_cloud_train)
     net = point_cloud
     tensors = []
     seed = None
@@ -129,13 +133,14 @@ def repeat_edge_conv(point_cloud, repeat, k, num_filters, trainable, debug=False
 
 
 def repeat_residual_edge_conv(point_cloud, repeat, k, num_filters, trainable, debug=False, _plan=None, offsets=None,
-                              bn_per_cloud=False):
+                              bn_per_cloud=False, bn_per_cloud_train=False):
     """dgcnn/ops.py:100-140.  Layers >= 1: conv1 without activation, optional shortcut conv when
-    num_filters changes, tensors[-1] = relu(shortcut + tensors[-1]).  offsets / bn_per_cloud: a packed tower (edge_conv)."""
+    num_filters changes, tensors[-1] = relu(shortcut + tensors[-1]).  offsets / bn_per_cloud / bn_per_cloud_train: a packed tower
+    (edge_conv)."""
     repeat = int(repeat)
     k = _listify(k, repeat, "k")
     num_filters = _listify(num_filters, repeat, "num_filters")
-    seg = _segments(point_cloud, offsets, k, bn_per_cloud)
+    seg = _segments(point_cloud, offsets, k, bn_per_cloud, bn_per_cloud_train)
     net = point_cloud
     tensors = []
     shortcut = None
@@ -180,13 +185,13 @@ def E_copy_grad(src, dst):
     c.tape.append(bwd)
 
 
-def fc(net, repeat, num_filters, trainable, debug=False, offsets=None, bn_per_cloud=False):
+def fc(net, repeat, num_filters, trainable, debug=False, offsets=None, bn_per_cloud=False, bn_per_cloud_train=False):
     """dgcnn/ops.py:142-163.  repeat x [1x1 conv + BN + ReLU] under scopes FC0, FC1, ...
     offsets: net is a packed tower (R,C), (1,R,C) or (1,R,1,C); bn_per_cloud (with offsets; forward only): every BatchNorm takes
-    the statistics of the row's own cloud."""
+    the statistics of the row's own cloud; bn_per_cloud_train: the same with its backward."""
     repeat = int(repeat)
     num_filters = _listify(num_filters, repeat, "num_filters")
-    seg = _segments(net, offsets, [], bn_per_cloud)
+    seg = _segments(net, offsets, [], bn_per_cloud, bn_per_cloud_train)
     x, B, N = E.as2d(net)
     for i in range(repeat):
         x = E.conv_bn_act(x, "FC%d" % i, num_filters[i], relu=True, seg=seg)

@@ -83,7 +83,7 @@ class trainval(object):
         f = self._flags
         if f.MODEL_NAME not in ("dgcnn", "residual-dgcnn", "residual-dgcnn-nofc"):
             raise NotImplementedError("Unsupported MODEL_NAME: %s" % f.MODEL_NAME)
-        if getattr(f, "BN_PER_CLOUD", False) and getattr(f, "TRAIN", False):
+        if getattr(f, "BN_PER_CLOUD", False) and getattr(f, "TRAIN", False) and not getattr(f, "BN_PER_CLOUD_TRAIN", False):
             raise NotImplementedError("per-cloud BatchNorm has no backward yet: BN_PER_CLOUD needs TRAIN=False")
         self._ctx = E.reset()
         self._ctx.seed = int(getattr(f, "SEED", 1)) if int(getattr(f, "SEED", 1)) >= 0 else 1
@@ -193,7 +193,7 @@ class trainval(object):
         wgt = self._to_dev(weight, torch.float32)
         if pts.dim() != 3:
             raise ValueError("points must be (MINIBATCH_SIZE, N, NUM_CHANNEL), got %s" % (tuple(pts.shape),))
-        if getattr(self._flags, "BN_PER_CLOUD", False) and pts.shape[0] > 1:
+        if (getattr(self._flags, "BN_PER_CLOUD", False) or getattr(self._flags, "BN_PER_CLOUD_TRAIN", False)) and pts.shape[0] > 1:
             return self._tower_eager(pts, lab, wgt, train)          # (model.build runs it as a packed tower: always eager)
         kind = self._wants_graph(pts.shape[0] * pts.shape[1])
         if kind is not None:
@@ -213,7 +213,8 @@ class trainval(object):
         # everything the host can check -- the tower's rank, the offsets, every layer's k against the smallest cloud -- before any
         # transfer or launch
         seg = ops._segments(data, offsets, ops._listify(self._flags.KVALUE, int(self._flags.EDGE_CONV_LAYERS), "k"),
-                            bn_per_cloud=bool(getattr(self._flags, "BN_PER_CLOUD", False)))
+                            bn_per_cloud=bool(getattr(self._flags, "BN_PER_CLOUD", False)),
+                            bn_per_cloud_train=bool(getattr(self._flags, "BN_PER_CLOUD_TRAIN", False)))
         for what, a in (("label", label), ("weight", weight)):
             if a is not None and (int(np.prod(tuple(a.shape))) != seg.rows or len(tuple(a.shape)) > 2):
                 raise ValueError("a packed tower of %d rows takes %s of shape (R,) or (1, R), got %s" % (seg.rows, what, tuple(a.shape)))
@@ -460,7 +461,7 @@ class trainval(object):
         offsets: feed_dict (one entry per tower; a packed tower always runs eagerly)."""
         if not self._flags.TRAIN:
             raise NotImplementedError
-        if getattr(self._flags, "BN_PER_CLOUD", False):
+        if getattr(self._flags, "BN_PER_CLOUD", False) and not getattr(self._flags, "BN_PER_CLOUD_TRAIN", False):
             raise NotImplementedError("per-cloud BatchNorm has no backward yet: BN_PER_CLOUD is an inference mode")
         c = self._ctx
         fd = self.feed_dict(data, label, weight, offsets)

@@ -463,8 +463,8 @@ int dgcnn_seg_colsum_f32(const float* x, int64_t ldx, int rows, int F, const int
                          void* ws, size_t ws_bytes, void* stream);
 int dgcnn_tile_rows_seg_f32(const float* src, int64_t lds, const int32_t* row_group, int rows, int F, float* dst, int64_t ldd,
                             void* stream);
-/* ---- BatchNorm of a packed tower with the statistics of the row's OWN cloud (csrc/seg_bn.hip; FORWARD ONLY: there is no backward
- * yet).  Cloud b = rows [seg_off[b], seg_off[b + 1]); idx (rows, k) holds TOWER rows; statistics are double[nseg][2][F] (sum and sum
+/* ---- BatchNorm of a packed tower with the statistics of the row's OWN cloud (csrc/seg_bn.hip; the forward here, the backward
+ * below).  Cloud b = rows [seg_off[b], seg_off[b + 1]); idx (rows, k) holds TOWER rows; statistics are double[nseg][2][F] (sum and sum
  * of squares per cloud; WRITTEN, not accumulated: the caller does not zero them); mean / rstd are float[nseg][F] tables; row_group =
  * int32[rows], the row -> cloud map.  With these a cloud's outputs do not depend on the other clouds of its tower.
  *   dgcnn_seg_colstats_f32     per cloud, the column sums of a materialised (rows, F) tensor (the k = 1 layers)
@@ -499,6 +499,50 @@ int dgcnn_seg_bn_act_f32(const float* T, int64_t ldt, int rows, int F, const int
 int dgcnn_seg_edge_bn_act_kreduce_f32(const float* V, int64_t ldv, const float* U, int64_t ldu, const int32_t* idx, int rows, int k,
                                       int F, const int32_t* row_group, const float* mean, const float* rstd, const float* beta,
                                       int relu, float* max_out, int64_t ldmax, float* mean_out, int64_t ldmean, void* stream);
+/* ---- the backward of the per-cloud BatchNorm (csrc/seg_bn.hip).  red = double[nseg][2][F]: per cloud sum dz and sum dz * xhat
+ * (WRITTEN, not accumulated: no zeroing, not in the slot arena); c1 / c2 = float[nseg][F] tables red / (n_b k).  The arithmetic is
+ * that of dgcnn_bn_bwd_reduce_f32 / dgcnn_bn_bwd_apply_f32 and their edge forms, operation for operation: a one-cloud tower gives
+ * their dY / dYsum bit for bit.  Both reduces sum in ONE fixed order in every dgcnn_set_stat_slots setting (no atomics variant), by
+ * the two stages of dgcnn_seg_colstats_f32 (64-row chunks cut at the cloud boundaries; per piece fp32 per wave over <= 16 rows, the
+ * four waves in double; then a cloud's pieces first chunk to last); ws: dgcnn_seg_stats_workspace_bytes(rows, nseg, F), 8-byte
+ * aligned (DGCNN_ENOSPC otherwise).  relu must be 0 or 1.  DGCNN_EINVAL for null / misshapen / (edge entries) misaligned arguments,
+ * DGCNN_EUNSUP for F % 4 != 0 or k >= 256 in the edge entries; nothing is written on error.
+ *   dgcnn_seg_edge_bn_act_kreduce_cnt_f32    dgcnn_seg_edge_bn_act_kreduce_f32 (one kernel template; max_out / mean_out bit-identical)
+ *                              that also writes cnt_out (rows, F) = #ties of the max + 256 * #(z > 0), dgcnn_edge_bn_act_kreduce_f32's
+ *                              packing (k < 256)
+ *   dgcnn_seg_bn_bwd_reduce_f32   k = 1: the sums of dz = (dout + d2) [z > 0 if relu] and dz * xhat over the rows of each cloud, z and
+ *                              xhat from T with the cloud's mean / rstd row; d2 (optional): the gradient of a second copy of the
+ *                              output.  float4 path when everything is 16-byte aligned with F, ld % 4 == 0, scalar path otherwise
+ *   dgcnn_seg_edge_bn_bwd_reduce_points_f32  conv0 (a ReLU layer): the same sums in closed form from the forward's per-point outputs
+ *                              (max, mean, packed counts) and dmax / dmean -- dgcnn_edge_bn_bwd_reduce_points_f32's integrand, no pass
+ *                              over the edges
+ *   dgcnn_seg_bn_bwd_finalize_f32  c1[b][f] = float(red0 * (1.0 / (n_b k))), c2 likewise; dbeta (may be NULL):
+ *                              dbeta[f] = dbeta_beta * dbeta[f] + float(sum_b red0[b][f]), b ascending, in double
+ *   dgcnn_seg_bn_bwd_apply_f32    k = 1: dT[r] = rstd_g ((dz - c1_g) - xhat c2_g), g = row_group[r]; dT may alias T
+ *   dgcnn_seg_edge_bn_bwd_apply_f32  conv0: y = V[idx] + U and z recomputed by the forward's instructions (z == mx compares equal),
+ *                              dz = ((z == mx) ? dmax / ties : 0) + dmean * (1.0f / k), zero where relu and !(z > 0); writes
+ *                              dY (rows * k, F) and dYsum (rows, F; may be NULL) = the k rows of dY added in ascending m */
+int dgcnn_seg_edge_bn_act_kreduce_cnt_f32(const float* V, int64_t ldv, const float* U, int64_t ldu, const int32_t* idx, int rows, int k,
+                                          int F, const int32_t* row_group, const float* mean, const float* rstd, const float* beta,
+                                          int relu, float* max_out, int64_t ldmax, float* mean_out, int64_t ldmean, float* cnt_out,
+                                          void* stream);
+int dgcnn_seg_bn_bwd_reduce_f32(const float* T, int64_t ldt, int rows, int F, const int32_t* seg_off, int nseg, const float* mean,
+                                const float* rstd, const float* beta, int relu, const float* dout, int64_t lddo, const float* d2,
+                                int64_t ldd2, double* red, void* ws, size_t ws_bytes, void* stream);
+int dgcnn_seg_edge_bn_bwd_reduce_points_f32(const float* mx, int64_t ldmx, const float* mn, int64_t ldmn, const float* cntpos,
+                                            const float* dmax, int64_t lddmax, const float* dmean, int64_t lddmean, const float* beta,
+                                            int rows, int k, int F, const int32_t* seg_off, int nseg, double* red, void* ws,
+                                            size_t ws_bytes, void* stream);
+int dgcnn_seg_bn_bwd_finalize_f32(const double* red, int nseg, int F, const int32_t* seg_off, int k, float* c1, float* c2,
+                                  float* dbeta, float dbeta_beta, void* stream);
+int dgcnn_seg_bn_bwd_apply_f32(const float* T, int64_t ldt, int rows, int F, const int32_t* row_group, const float* mean,
+                               const float* rstd, const float* beta, int relu, const float* dout, int64_t lddo, const float* d2,
+                               int64_t ldd2, const float* c1, const float* c2, float* dT, int64_t lddt, void* stream);
+int dgcnn_seg_edge_bn_bwd_apply_f32(const float* V, int64_t ldv, const float* U, int64_t ldu, const int32_t* idx, int rows, int k, int F,
+                                    const int32_t* row_group, const float* mean, const float* rstd, const float* beta, int relu,
+                                    const float* dmax, int64_t lddmax, const float* dmean, int64_t lddmean, const float* mx_in,
+                                    int64_t ldmx, const float* cnt_in, const float* c1, const float* c2, float* dY, float* dYsum,
+                                    int64_t lddysum, void* stream);
 /* tf.nn.dropout(net, keep) (model.py:91): counter-based RNG keyed by (seed, element index) so the
  * backward regenerates the same mask.  y may alias x. */
 int dgcnn_dropout_f32(const float* x, float* y, int64_t n, float keep, uint64_t seed, void* stream);
