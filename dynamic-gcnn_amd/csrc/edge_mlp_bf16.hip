@@ -603,14 +603,14 @@ size_t bwd_lds_bytes(int C, int k, int F) {
   const int K = 16 * (C <= 4 ? 1 : 8), P = RT / k;
   return (size_t)2 * RT * (2 * K + 16) + (size_t)RT * (2 * F + 16) + (size_t)2 * 4 * P * F * sizeof(float);
 }
-// k >= 8 bounds P at 16; the widest layers (C = 64, F = 128) need k >= 10 to fit 160 KB
+// k >= 8 bounds P at 16; the widest layers (C = 64, F = 128) need k >= 9 (P <= 14) to fit 160 KB
 bool bwd_shape_ok(int C, int k, int F) { return shape_ok(C, k, F) && k >= 8 && k < CNT_POS && bwd_lds_bytes(C, k, F) <= 160 * 1024; }
 
 }  // namespace
 
 // 1 when the fused kernels take this layer shape (C <= 4 or C == 64; F in {32, 64, 128}; k <= 128), else 0
 extern "C" int dgcnn_edge_mlp_bf16_supported(int C, int k, int F) { return shape_ok(C, k, F) ? 1 : 0; }
-// 1 when dgcnn_edge_mlp_bf16_bwd takes this layer shape (the forward's shapes with 8 <= k < 256)
+// 1 when dgcnn_edge_mlp_bf16_bwd takes this layer shape (the forward's shapes with 8 <= k <= 128)
 extern "C" int dgcnn_edge_mlp_bf16_bwd_supported(int C, int k, int F) { return bwd_shape_ok(C, k, F) ? 1 : 0; }
 
 #define DG_EDGE_COMMON(name)                                                                                                  \
@@ -674,7 +674,7 @@ extern "C" int dgcnn_edge_mlp_bf16_bwd(const float* x, int64_t ldx, const int32_
                                        int64_t lddmn, double* red, void* dYb, float* dysum, int64_t lddysum, float* dW0,
                                        float* dbeta, float dbeta_beta, void* ws, size_t ws_bytes, void* stream) {
   DG_EDGE_COMMON("dgcnn_edge_mlp_bf16_bwd");
-  DG_REQUIRE(bwd_shape_ok(C, k, F), DGCNN_EUNSUP, "dgcnn_edge_mlp_bf16_bwd: needs 8 <= k < %d and %zu bytes of LDS <= 160 KB (k=%d)", CNT_POS, bwd_lds_bytes(C, k, F), k);
+  DG_REQUIRE(bwd_shape_ok(C, k, F), DGCNN_EUNSUP, "dgcnn_edge_mlp_bf16_bwd: needs 8 <= k <= %d and %zu bytes of LDS <= 160 KB (k=%d)", RT, bwd_lds_bytes(C, k, F), k);
   DG_REQUIRE(mean && rstd && beta && mx && cnt && dmx && dmn && red && dW0 && ws && ldmx >= F && lddmx >= F && lddmn >= F, DGCNN_EINVAL,
              "dgcnn_edge_mlp_bf16_bwd: bad args");
   DG_REQUIRE(!dysum || lddysum >= F, DGCNN_EINVAL, "dgcnn_edge_mlp_bf16_bwd: lddysum < F");

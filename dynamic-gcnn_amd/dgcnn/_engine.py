@@ -1296,7 +1296,7 @@ def edge_conv_block(x, B, N, k, num_filters, relu1=True, outs=None, net2=None, s
 
     if bf16:
         bsrc = (x.data_ptr(), H.ld2(x), idx.data_ptr(), W0.data_ptr(), B, N, C, k, F)
-        # the backward in one pass over the edges (8 <= k < 256): the forward then packs (#ties, #positives) as the fp32 edge kernels do
+        # the backward in one pass over the edges (8 <= k <= 128): the forward then packs (#ties, #positives) as the fp32 edge kernels do
         fused_bwd = fused_bf16 and c.recording and BF16_FUSED_BWD and bool(H.load().dgcnn_edge_mlp_bf16_bwd_supported(C, k, F))
         if fused_bf16:
             # csrc/edge_mlp_bf16.hip: E = [x_i, x_j - x_i] gathered, rounded and multiplied tile by tile on the bf16 MFMA pipe;
