@@ -1430,6 +1430,18 @@ int dispatch_k_packed(const float* x, const float* sq, PackedClouds cl, int max_
   return dg::check_launch("dgcnn_knn_seg_f32");
 }
 
+// the listed clouds of a packed tower (raw coordinates, k <= 40: dgcnn_knn_seg_mix_f32), at most max_n points each
+int dispatch_k_listed(const char* what, const float* x, const float* sq, ListedClouds cl, int max_n, int C, int64_t ldx, int k, int vec_ok,
+                      int32_t* idx, const float* tau0, hipStream_t st) {
+  const dim3 grid((unsigned)dg::cdiv(max_n, ROWS), (unsigned)cl.nlist);
+#define DG_KL(KCV) dg::launch((knn_kernel<4, KCV, ListedClouds>), grid, dim3(256), 0, st, x, sq, cl, C, ldx, k, vec_ok, idx, tau0)
+  if (k <= 8) DG_KL(8);
+  else if (k <= 20) DG_KL(20);
+  else DG_KL(40);
+#undef DG_KL
+  return dg::check_launch(what);
+}
+
 template <int CP>
 int dispatch_k(const float* x, const float* sq, int B, int N, int C, int64_t ldx, int k, int vec_ok,
                int32_t* idx, const float* tau0, hipStream_t st) {
@@ -1462,6 +1474,8 @@ int launch_knn_grid(const float* x, const float* sq, int B, int N, int C, int64_
 size_t knn_grid_seg_workspace_bytes(int rows, int nseg);
 int launch_knn_grid_seg(const float* x, const float* sq, int nseg, const int32_t* seg_off, int rows, int max_n, int C, int64_t ldx, int k,
                         int32_t* idx, void* ws, hipStream_t st);
+int launch_knn_grid_listed(const char* what, const float* x, const float* sq, const int32_t* seg_off, const int32_t* list, int nlist,
+                           int rows, int max_n, int C, int64_t ldx, int k, int32_t* idx, void* ws, hipStream_t st);
 }  // namespace dg
 
 // workspace = [s_i of every row (B*N floats, padded to 256 bytes) | seed bounds (same size) | scratch of the cell-grid search (C <= 4,
@@ -1744,4 +1758,63 @@ extern "C" int dgcnn_knn_seg_grid_f32(const float* x, int64_t ldx, int C, int k,
              (int64_t)rows, C, sq_ws);
   return dg::launch_knn_grid_seg(x, sq_ws, nseg, seg_off, rows, max_n, C, ldx, k, idx, reinterpret_cast<char*>(ws) + knn_sq_bytes(1, rows),
                                  st);
+}
+
+// ---- packed towers, raw coordinates: every cloud through the search that suits its own size, in one call ----------------------------
+// cloud_list (device, nseg int32) names the tower's clouds in two classes: the first n_grid go through the cell grid, the others through
+// the all-pairs scan with the histogram bound; both sub-searches are the kernels of the two entries above instantiated with
+// ListedClouds (knn_common.h), launched over their own class only -- grids cdiv(grid_max_n, 256) x n_grid and cdiv(scan_max_n, 64) x
+// (nseg - n_grid), so a small cloud launches no row of blocks for the large ones and owns no cell table.  A pair's D has the same bits
+// in either kernel and both select by (D, j): idx is dgcnn_knn_seg_f32's and dgcnn_knn_seg_grid_f32's, bit for bit.
+// workspace = [s_i of every tower row (padded to 256 bytes) | the scan rows' histogram bounds (same size) | sorted records, s_j and
+//              original indices of every row (24 bytes per row, indexed by tower row), one GridInfo and one cell table per GRID cloud]
+extern "C" int64_t dgcnn_knn_seg_mix_workspace_bytes(int rows, int n_grid) {
+  if (rows <= 0 || n_grid <= 0) return 0;
+  return (int64_t)(2 * knn_sq_bytes(1, rows) + dg::knn_grid_seg_workspace_bytes(rows, n_grid));
+}
+
+extern "C" int dgcnn_knn_seg_mix_f32(const float* x, int64_t ldx, int C, int k, int nseg, const int32_t* seg_off, int rows,
+                                     const int32_t* cloud_list, int n_grid, int grid_max_n, int scan_min_n, int scan_max_n,
+                                     int32_t* idx, void* ws, size_t ws_bytes, void* stream) {
+  const char* what = "dgcnn_knn_seg_mix_f32";
+  DG_REQUIRE(x && idx && ws && seg_off && cloud_list, DGCNN_EINVAL, "%s: null pointer", what);
+  DG_REQUIRE(nseg > 0 && nseg <= 65535 && rows > 0 && C > 0 && ldx >= C, DGCNN_EINVAL, "%s: bad shape nseg=%d rows=%d C=%d", what,
+             nseg, rows, C);
+  DG_REQUIRE(C <= 4 && k <= 40, DGCNN_EINVAL, "%s: C=%d k=%d: the cell grid searches raw coordinates (C <= 4) for k <= 40", what, C, k);
+  DG_REQUIRE(n_grid > 0 && n_grid < nseg, DGCNN_EINVAL,
+             "%s: n_grid=%d must be in [1, nseg=%d): a tower of one class goes to dgcnn_knn_seg_f32 or dgcnn_knn_seg_grid_f32", what,
+             n_grid, nseg);
+  DG_REQUIRE(grid_max_n > 0 && scan_min_n > 0 && scan_min_n <= scan_max_n &&
+                 (int64_t)grid_max_n + (int64_t)scan_min_n * (nseg - n_grid) <= rows &&
+                 (int64_t)grid_max_n * n_grid + (int64_t)scan_max_n * (nseg - n_grid) >= rows,
+             DGCNN_EINVAL, "%s: cloud sizes grid_max_n=%d scan_min_n=%d scan_max_n=%d do not fit %d rows in %d + %d clouds", what,
+             grid_max_n, scan_min_n, scan_max_n, rows, n_grid, nseg - n_grid);
+  DG_REQUIRE(k > 0 && k <= scan_min_n && k <= grid_max_n, DGCNN_EINVAL,
+             "%s: k=%d must be in [1, smallest cloud=%d] (tf.nn.top_k raises otherwise)", what, k,
+             scan_min_n < grid_max_n ? scan_min_n : grid_max_n);
+  DG_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0 && ws_bytes >= (size_t)dgcnn_knn_seg_mix_workspace_bytes(rows, n_grid),
+             DGCNN_EINVAL, "%s: workspace must be 16-byte aligned and hold dgcnn_knn_seg_mix_workspace_bytes(rows, n_grid) bytes (got %zu)",
+             what, ws_bytes);
+  hipStream_t st = (hipStream_t)stream;
+  float* sq_ws = reinterpret_cast<float*>(ws);
+  float* tb = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + knn_sq_bytes(1, rows));
+  void* grid_ws = reinterpret_cast<char*>(ws) + 2 * knn_sq_bytes(1, rows);
+  dg::launch(sqnorm_kernel, dim3((unsigned)dg::cdiv(rows, SQ_ROWS)), dim3(256), sizeof(float) * SQ_ROWS * (C + 1), st, x, ldx,
+             (int64_t)rows, C, sq_ws);
+  const int rc = dg::launch_knn_grid_listed(what, x, sq_ws, seg_off, cloud_list, n_grid, rows, grid_max_n, C, ldx, k, idx, grid_ws, st);
+  if (rc != 0) return rc;
+  const int nscan = nseg - n_grid;
+  const ListedClouds cl{seg_off, cloud_list + n_grid, nscan};
+  const int vec_ok = (ldx % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
+  // the histogram bound's precondition N >= 4 k stride must hold for the smallest cloud of the SCAN class
+  const int hs = knn_hist_stride(scan_min_n);
+  const float* tau0 = nullptr;
+  if (hs > 0 && !knn_force_valu() && scan_min_n >= 4 * k * hs) {
+    const dim3 hg((unsigned)dg::cdiv(scan_max_n, 64), (unsigned)nscan);
+    if (hs == 1) dg::launch(knn_hist_bound_kernel<1, ListedClouds>, hg, dim3(256), 0, st, x, (const float*)sq_ws, cl, C, ldx, k, tb);
+    else if (hs == 2) dg::launch(knn_hist_bound_kernel<2, ListedClouds>, hg, dim3(256), 0, st, x, (const float*)sq_ws, cl, C, ldx, k, tb);
+    else dg::launch(knn_hist_bound_kernel<4, ListedClouds>, hg, dim3(256), 0, st, x, (const float*)sq_ws, cl, C, ldx, k, tb);
+    tau0 = tb;
+  }
+  return dispatch_k_listed(what, x, sq_ws, cl, scan_max_n, C, ldx, k, vec_ok, idx, tau0, st);
 }

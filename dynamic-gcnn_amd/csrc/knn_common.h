@@ -31,6 +31,18 @@ struct PackedClouds {
     return lo;
   }
 };
+// Some clouds of a packed tower, in a listed order: grid row (slot) y = cloud list[y].  base() is still the cloud's first tower row, so
+// keys keep the cloud-local j and written indices are tower rows, while everything a kernel indexes by its grid row -- GridInfo[y], cell
+// table y, the early exit of blocks past the cloud's rows -- is per slot: a launch over nlist clouds is shaped cdiv(max n of the LIST,
+// ...) x nlist and holds scratch for nlist clouds, whatever the tower holds besides (dgcnn_knn_seg_mix_f32).
+struct ListedClouds {
+  const int* __restrict__ off;               // the tower's nseg + 1 offsets
+  const int* __restrict__ list;              // nlist clouds of the tower
+  int nlist;
+  static constexpr bool kPacked = true;
+  __device__ int64_t base(int y) const { return off[list[y]]; }
+  __device__ int size(int y) const { const int b = list[y]; return off[b + 1] - off[b]; }
+};
 
 // ---- lane-mask helpers.  hipcc turns nested ?: on register arrays into exec-masked branches (20
 // s_and_saveexec/s_cbranch per insert, measured 10x slower); v_cmp -> SGPR-pair mask -> v_cndmask

@@ -517,6 +517,13 @@ int launch_knn_grid_seg(const float* x, const float* sq, int nseg, const int32_t
   return launch_grid("dgcnn_knn_seg_grid_f32", x, sq, PackedClouds{seg_off, nseg}, nseg, max_n, (size_t)rows, C, ldx, k, idx, ws, st);
 }
 
+// the nlist listed clouds of a packed tower (at most max_n points each): the row arrays are indexed by tower row as above, GridInfo and
+// cell tables by the cloud's place in the list; ws >= knn_grid_seg_workspace_bytes(rows, nlist), 16-byte aligned
+int launch_knn_grid_listed(const char* what, const float* x, const float* sq, const int32_t* seg_off, const int32_t* list, int nlist,
+                           int rows, int max_n, int C, int64_t ldx, int k, int32_t* idx, void* ws, hipStream_t st) {
+  return launch_grid(what, x, sq, ListedClouds{seg_off, list, nlist}, nlist, max_n, (size_t)rows, C, ldx, k, idx, ws, st);
+}
+
 }  // namespace dg
 
 // Would the library send this packed tower through the cell grid?  (host only, no GPU call)  Mode 1: from a row-weighted mean cloud
@@ -534,5 +541,24 @@ extern "C" int dgcnn_knn_grid(int mode) {
   const int prev = knn_grid_on() ? (g_knn_grid_all ? 2 : 1) : 0;
   g_knn_grid = mode ? 1 : 0;
   g_knn_grid_all = mode == 2;
+  return prev;
+}
+
+// Packed towers, mode 1: the per-cloud size from which a cloud goes to the cell grid while the smaller clouds of the same tower keep
+// the all-pairs scan (dgcnn_knn_seg_mix_f32; dgcnn/_engine.py:knn_packed splits the tower).  0 = no split: the whole tower follows
+// dgcnn_knn_seg_grid_use.  $DGCNN_KNN_MIX_MIN_N is read once, at the first call.
+// The default is 0 by measurement (profiles/packed/mix_bench.txt; T = 4096 ... 16384, C = 4, k = 20 / 40): the two sub-searches run one
+// after the other on one stream and neither fills the GPU, so the mix costs about their sum -- one 16384 / 32768 / 65536-point cloud
+// among 23 small ones 0.80x / 0.83x / 0.88x of what the mean rule picks at k = 20 (0.63x / 0.99x / 0.98x at k = 40) at every T.
+constexpr int GRID_SEG_MIX_MIN_N = 0;
+extern "C" int dgcnn_knn_seg_mix_min_n(int n) {
+  static int v = -1;
+  if (v < 0) {
+    const char* e = getenv("DGCNN_KNN_MIX_MIN_N");
+    v = e ? atoi(e) : GRID_SEG_MIX_MIN_N;
+    if (v < 0) v = 0;
+  }
+  const int prev = v;
+  if (n >= 0) v = n;
   return prev;
 }

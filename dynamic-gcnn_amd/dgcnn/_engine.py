@@ -537,6 +537,7 @@ class Segments(object):
         self.min_n, self.max_n = int(sizes.min()), int(sizes.max())
         self._dev = None
         self._rg = None
+        self._mix = {}
         self.bn_per_cloud_train = bool(bn_per_cloud_train)
         self.bn_per_cloud = bool(bn_per_cloud) or self.bn_per_cloud_train
 
@@ -548,6 +549,23 @@ class Segments(object):
         if self._dev is None or self._dev.device != dev:
             self._dev = torch.from_numpy(self.host.astype(np.int32)).to(dev)
         return self._dev
+
+    def mix(self, T, dev):
+        """The tower's clouds in two classes for dgcnn_knn_seg_mix_f32: (list, n_grid, grid_max_n, scan_min_n, scan_max_n) -- list =
+        int32[nseg] on the device, the clouds of at least T points (the grid class: n_grid of them, the largest grid_max_n) first, then
+        the smaller ones (the scan class, scan_min_n ... scan_max_n points), each part ascending.  From the host offsets; made once
+        per threshold.  An empty class: its numbers are 0."""
+        T = int(T)
+        m = self._mix.get(T)
+        if m is None:
+            sizes = np.diff(self.host)
+            grid, scan = np.flatnonzero(sizes >= T), np.flatnonzero(sizes < T)
+            lst = np.concatenate([grid, scan]).astype(np.int32)
+            m = self._mix[T] = [lst, int(grid.size), int(sizes[grid].max()) if grid.size else 0,
+                                int(sizes[scan].min()) if scan.size else 0, int(sizes[scan].max()) if scan.size else 0, None]
+        if m[5] is None or m[5].device != dev:
+            m[5] = torch.from_numpy(m[0]).to(dev)
+        return m[5], m[1], m[2], m[3], m[4]
 
     def row_group(self, dev):
         """int32[rows] on the device: the cloud of every tower row (the per-cloud bias of FC0, tf.tile)."""
@@ -561,7 +579,8 @@ def knn(x2d, B, N, k, seed=None, seg=None):
     """idx (B,N,k) of x2d (B*N, C).  seed: an earlier graph of the same clouds, (B,N,ks) int32 with ks >= k -- ks distinct candidates
     per row whose largest distance bounds the row's k-th distance from above (dgcnn_knn_seeded_f32); the result does not depend on it.
     seg: a packed tower (Segments; B = 1, N = rows): every row searches its own cloud, idx holds tower rows (dgcnn_knn_seg_f32, or
-    dgcnn_knn_seg_grid_f32 for raw coordinates where dgcnn_knn_seg_grid_use picks the cell grid)."""
+    dgcnn_knn_seg_grid_f32 for raw coordinates where dgcnn_knn_seg_grid_use picks the cell grid, or dgcnn_knn_seg_mix_f32 where
+    dgcnn_knn_seg_mix_min_n splits the tower's clouds between the two)."""
     if seg is not None:
         return knn_packed(x2d, k, seg, seed=seed)
     C = x2d.shape[1]
@@ -588,6 +607,14 @@ def knn(x2d, B, N, k, seed=None, seg=None):
     return idx
 
 
+def _knn_grid_mode(lib, C, k):
+    """dgcnn_knn_grid's mode for this shape, as dgcnn_knn_seg_grid_use answers for a one-point tower: 0 = never (switched off, or C > 4
+    or k > 40), 2 = whenever applicable (its threshold on the mean cloud size is 0), 1 = where the library's rule says it pays."""
+    if not lib.dgcnn_knn_seg_grid_use(C, k, 1, 1, 1, 1, 1 << 62):
+        return 0
+    return 2 if lib.dgcnn_knn_seg_grid_use(C, k, 1, 1, 1, 1, 0) else 1
+
+
 def knn_packed(x2d, k, seg, seed=None):
     """idx (1,R,k) of the packed tower x2d (R, C): per cloud the dense k_nn of that cloud, as tower rows."""
     R, C = x2d.shape
@@ -598,8 +625,24 @@ def knn_packed(x2d, k, seg, seed=None):
     idx = torch.empty((1, R, k), dtype=torch.int32, device=x2d.device)
     n = seg.host[1:] - seg.host[:-1]
     Cp, kc = (4 if C <= 4 else 16 if C <= 16 else 64 if C <= 64 else 128), (8 if k <= 8 else 20 if k <= 20 else 40 if k <= 40 else 64)
-    # raw coordinates: the cell grid, one per cloud, where the library's rule picks it (the same indices; a seed is not needed)
-    if C <= 4 and H.load().dgcnn_knn_seg_grid_use(C, k, seg.nseg, R, seg.min_n, seg.max_n, int((n * n).sum())):
+    # raw coordinates: the cell grid, one per cloud, where the library's rule picks it (the same indices; a seed is not needed).  Mode 1
+    # with a per-cloud threshold T > 0: the clouds of at least T points through the grid, the others through the scan, in one call
+    lib = H.load()
+    T = int(lib.dgcnn_knn_seg_mix_min_n(-1)) if C <= 4 and _knn_grid_mode(lib, C, k) == 1 else 0
+    if T > 0:
+        lst, n_grid, grid_max, scan_min, scan_max = seg.mix(T, x2d.device)
+        use_grid = n_grid == seg.nseg
+        if 0 < n_grid < seg.nseg:
+            nws = int(lib.dgcnn_knn_seg_mix_workspace_bytes(R, n_grid))
+            ws = torch.empty((nws,), dtype=torch.uint8, device=x2d.device)
+            H.call("dgcnn_knn_seg_mix_f32", x2d.data_ptr(), H.ld2(x2d), C, k, seg.nseg, off.data_ptr(), R, lst.data_ptr(), n_grid, grid_max,
+                   scan_min, scan_max, idx.data_ptr(), ws.data_ptr(), nws,
+                   tag="knn_seg_call<C4,k%d>[sqnorm_kernel+knn_grid_*+knn_hist_bound_kernel+knn_kernel]" % kc,
+                   work=2.0 * float((n * n).sum()) * C)
+            return idx
+    else:
+        use_grid = C <= 4 and lib.dgcnn_knn_seg_grid_use(C, k, seg.nseg, R, seg.min_n, seg.max_n, int((n * n).sum()))
+    if use_grid:
         nws = int(H.load().dgcnn_knn_seg_grid_workspace_bytes(R, seg.nseg))
         ws = torch.empty((nws,), dtype=torch.uint8, device=x2d.device)
         H.call("dgcnn_knn_seg_grid_f32", x2d.data_ptr(), H.ld2(x2d), C, k, seg.nseg, off.data_ptr(), R, seg.min_n, seg.max_n,

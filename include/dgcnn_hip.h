@@ -123,6 +123,27 @@ int64_t dgcnn_knn_seg_grid_workspace_bytes(int rows, int nseg);
 int dgcnn_knn_seg_grid_f32(const float* x, int64_t ldx, int C, int k, int nseg, const int32_t* seg_off, int rows, int min_n, int max_n,
                            int32_t* idx, void* ws, size_t ws_bytes, void* stream);
 int dgcnn_knn_seg_grid_use(int C, int k, int nseg, int rows, int min_n, int max_n, int64_t sum_n2);
+/* The same packed search for raw coordinates (C <= 4, k <= 40) with every cloud in the search that suits its own size, in ONE call:
+ * cloud_list (device, nseg int32) names every cloud of the tower once -- the n_grid clouds of the grid class first, then the
+ * nseg - n_grid clouds of the scan class, each part ascending.  The grid class goes through the cell grid of dgcnn_knn_seg_grid_f32,
+ * launched over its n_grid clouds only (grid_max_n: its largest cloud); the scan class through the all-pairs scan with the histogram
+ * bound of dgcnn_knn_seg_f32, launched over its clouds only (scan_min_n / scan_max_n: its smallest / largest cloud; the bound needs
+ * scan_min_n >= 4 k stride, as there).  Same kernels, same pairs' arithmetic, same (D, j) order: idx is the two other entries', bit
+ * for bit.  0 < n_grid < nseg -- a tower of one class belongs to one of the two other entries.  The list's contents are trusted, as
+ * seg_off is.  DGCNN_EINVAL, before any launch, for a null pointer, C > 4, k > 40, k > scan_min_n, n_grid outside (0, nseg), sizes
+ * that do not fit `rows`, a misaligned workspace or one smaller than dgcnn_knn_seg_mix_workspace_bytes(rows, n_grid) = the s_i of
+ * every row and one bound per row (each rows floats rounded up to 256 bytes) + 24 bytes per row (sorted records, s_j, original
+ * indices) + one cell table (16^3 + 1 int32) and one 64-byte grid description per GRID cloud (+ 256): it grows with n_grid, not with
+ * nseg. */
+int64_t dgcnn_knn_seg_mix_workspace_bytes(int rows, int n_grid);
+int dgcnn_knn_seg_mix_f32(const float* x, int64_t ldx, int C, int k, int nseg, const int32_t* seg_off, int rows,
+                          const int32_t* cloud_list, int n_grid, int grid_max_n, int scan_min_n, int scan_max_n, int32_t* idx, void* ws,
+                          size_t ws_bytes, void* stream);
+/* The per-cloud size from which a cloud of a packed tower goes to the grid class in dgcnn_knn_grid mode 1 (dgcnn/_engine.py:knn_packed
+ * splits the tower and calls dgcnn_knn_seg_mix_f32 when both classes are non-empty); 0 = the mix is off and the whole tower follows
+ * dgcnn_knn_seg_grid_use; n < 0 only queries.  Returns the previous value.  Initialised once from $DGCNN_KNN_MIX_MIN_N if set, else
+ * from the library's default. */
+int dgcnn_knn_seg_mix_min_n(int n);
 
 /* ---- K3 in its bf16-operand form (BASELINE configs[2] "bf16 edge-MLP MFMA"): conv0 of an EdgeConv layer, ops.py:21-52 ------
  * E[e] = [x_i, x_j - x_i] formed in fp32 and rounded to bf16 once (RNE), W0 (2C x F, row-major) rounded to bf16 once,

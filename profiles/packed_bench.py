@@ -15,6 +15,10 @@ three towers from fixed seeds: (a) the mix above, (b) 8 clouds N ~ U[8192, 32768
 Per path the min / median / max of the rounds; the indices of the two paths are asserted equal; the last column says what the
 library's default rule (mode 1: dgcnn_knn_seg_grid_use) picks for the tower.
 
+Per-cloud mix (--mix-out): the same call on all of those towers in mode 1 with dgcnn_knn_seg_mix_min_n = T for T in MIX_T, next to the
+scan, the all-grid call and the baseline (what mode 1 picks with the mix off), alternating in one process.
+
+    python profiles/packed_bench.py --mix-out profiles/packed/mix_bench.txt --reps 10
     python profiles/packed_bench.py [--reps 20] [--out profiles/packed/bench.txt] [--grid-out profiles/packed/grid_bench.txt] [--grid-only]
                                    [--grid-sweep profiles/packed/grid_sweep.txt]   (more towers: where the two paths cross)
 """
@@ -131,6 +135,71 @@ def grid_section(lib, reps, rounds=5, towers=None):
     return lines
 
 
+MIX_T = (4096, 6144, 8192, 12288, 16384)
+
+
+def mix_section(lib, reps, rounds=5):
+    """The per-cloud mix (dgcnn_knn_seg_mix_f32 through knn_packed: mode 1 with dgcnn_knn_seg_mix_min_n = T) at every T of MIX_T against
+    the scan (mode 0), the all-grid call (mode 2) and the baseline = whichever of the two mode 1 picks with the mix off (T = 0: the
+    mean rule, dgcnn_knn_seg_grid_use), all alternating in one process."""
+    prop = torch.cuda.get_device_properties(0)
+    paths = ["scan", "grid"] + ["T=%d" % t for t in MIX_T]
+    lines = ["device: %s (%s, %d CUs), one GPU" % (prop.name or "AMD Instinct", getattr(prop, "gcnArchName", "?"), prop.multi_processor_count),
+             "one packed layer-0 k-NN call, C = 4: all-pairs scan (dgcnn_knn_grid(0)), all-grid (dgcnn_knn_grid(2)) and mode 1 with the per-cloud",
+             "threshold dgcnn_knn_seg_mix_min_n = T (clouds of >= T points through the grid, the others through the scan, one call; [g/s] = clouds",
+             "per class; a tower of one class issues the existing scan / all-grid call).  %d rounds alternating all paths, %d calls per round" % (rounds, reps),
+             "between HIP events; ms per call as min / median / max of the rounds.  base = what mode 1 picks with the mix off (the mean rule).",
+             "vs base: median(base) / median(path); + faster / - slower than base beyond the spread of the rounds (no overlap), = within it"]
+    prev = lib.dgcnn_knn_grid(0)
+    prev_t = lib.dgcnn_knn_seg_mix_min_n(0)
+    verdicts = {t: [] for t in MIX_T}
+    try:
+        for name, sizes in grid_towers() + grid_sweep_towers():
+            sizes = np.asarray(sizes)
+            off = np.concatenate([[0], np.cumsum(sizes)])
+            R = int(off[-1])
+            seg = E.Segments(off, R)
+            s2 = int((sizes.astype(np.int64) ** 2).sum())
+            x = torch.from_numpy(np.random.default_rng(R).random((R, 4), dtype=np.float32)).cuda()
+            lines.append("%s: R = %d rows, min %d, max %d, row-weighted mean cloud size %.0f" % (name, R, seg.min_n, seg.max_n, s2 / R))
+            for k in (20, 40):
+                call = lambda: E.knn(x, 1, R, k, seg=seg)
+                lib.dgcnn_knn_grid(1)
+                base = "grid" if lib.dgcnn_knn_seg_grid_use(4, k, seg.nseg, R, seg.min_n, seg.max_n, s2) else "scan"
+
+                def setup(path):
+                    lib.dgcnn_knn_grid(0 if path == "scan" else 2 if path == "grid" else 1)
+                    lib.dgcnn_knn_seg_mix_min_n(int(path[2:]) if path.startswith("T=") else 0)
+                res, t = {}, {p_: [] for p_ in paths}
+                for rd in range(rounds):
+                    for path in paths:
+                        setup(path)
+                        if rd == 0:
+                            res[path] = call().cpu().numpy()
+                        t[path].append(timed(call, reps))
+                for path in paths[1:]:
+                    assert np.array_equal(res["scan"], res[path]), "%s, k=%d: %s != all-pairs scan" % (name, k, path)
+                b = np.array(t[base])
+                for path in paths:
+                    a = np.array(t[path])
+                    v = "+" if a.max() < b.min() else ("-" if b.max() < a.min() else "=")
+                    tag = ""
+                    if path.startswith("T="):
+                        T = int(path[2:])
+                        g = int((sizes >= T).sum())
+                        tag = "[%d/%d]" % (g, len(sizes) - g)
+                        verdicts[T].append(v)
+                    lines.append("%-6s k=%-3d %-8s %-8s %8.3f /%8.3f /%8.3f   vs base %5.2f %s%s" % (
+                        "", k, path, tag, a.min(), np.median(a), a.max(), np.median(b) / np.median(a), v, "   <- base" if path == base else ""))
+    finally:
+        lib.dgcnn_knn_seg_mix_min_n(prev_t)
+        lib.dgcnn_knn_grid(prev)
+    lines.append("per T over all towers and k: faster / within the spread / slower than base")
+    for T in MIX_T:
+        lines.append("  T=%-6d %2d / %2d / %2d" % (T, verdicts[T].count("+"), verdicts[T].count("="), verdicts[T].count("-")))
+    return lines
+
+
 def write(path, lines):
     text = "\n".join(lines)
     print(text)
@@ -147,9 +216,14 @@ def main():
     ap.add_argument("--grid-only", action="store_true", help="only the cell-grid section")
     ap.add_argument("--grid-sweep", default=None, metavar="FILE",
                     help="also time the towers of grid_sweep_towers() (3 rounds) into FILE (profiles/packed/grid_sweep.txt)")
+    ap.add_argument("--mix-out", default=None, metavar="FILE",
+                    help="only the per-cloud mix of grid and scan at every threshold of MIX_T, into FILE (profiles/packed/mix_bench.txt)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "packed_bench measures on the GPU"
     lib = H.load()
+    if args.mix_out:
+        write(args.mix_out, mix_section(lib, args.reps))
+        return
     write(args.grid_out, grid_section(lib, args.reps))
     if args.grid_sweep:
         write(args.grid_sweep, grid_section(lib, args.reps, rounds=3, towers=grid_sweep_towers()))
