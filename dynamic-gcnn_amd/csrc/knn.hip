@@ -550,6 +550,7 @@ __global__ __launch_bounds__(256, (KC <= 20 ? 3 : 2)) void knn_mfma_kernel(const
 //     |p' - P| <= 3.25 * 2^-16 * sum|x_c y_c|   (dropped terms x2y2, x3 y, (x1+x2) y3 and the fp32 accumulation)
 //     |p  - P| <= C * 2^-24 * sum|x_c y_c|      (the oracle's fmaf chain p; P = exact inner product)
 //  => |d' - d| <= 2 |p' - p| + 2^-22 t  <  2^-14 t,   t = fl(s_i + s_j)   (sum|xy| <= (S_i + S_j)/2; d, d' share t)
+// (reached: 1.86 * 2^-16 t on the true neighbours of the `rounddown` clouds of tests/knn_adversarial.py, float64 model of the products)
 // A candidate can enter the list only if d < thr, hence only if d' < thr + eps with eps = 2^-13 t (2x margin).  For those
 // (and only those) the NORMATIVE distance is recomputed on the VALU -- fmaf chain over c ascending from +0, x_i and x_j from
 // fp32 LDS copies of the block's query rows and of the current candidate tile (a first version read x_j from global memory:
@@ -921,11 +922,11 @@ __device__ __forceinline__ unsigned long long wave_lowest64(const unsigned long 
 // LX: the candidates' fp32 rows are kept in LDS next to the tile and a wave's survivors are re-checked tile by tile (N < 8192: ~10
 // pairs per wave and tile, LDS is the cheaper source); !LX: pairs wait in the queue across tiles until 64 are there and read the
 // candidate row from global memory (L2) -- at N = 65536 a wave meets a survivor every other tile.
-// NPR = products of the filter's inner product: 3 = a1 q1 + a1 q2 + a2 q1 (two bf16 terms per operand; |d' - d| <= 2^-14 t), 1 = a1 q1
-// only (plain bf16 operands, unit roundoff 2^-8: |p' - p| <= sum |a q| (2^-7 + 2^-16) <= (t / 2) 2^-7 (1 + 2^-9), fp32 accumulation of
-// exact products on top: |d' - d| <= 2^-7 t (1 + 2^-8); tested with 2^-6 t): a third of the MFMAs, a quarter of the staging
-// arithmetic, one plane in LDS -- for a wider margin, i.e. more pairs re-checked exactly.  The result is the same bit for bit (the
-// re-check decides).
+// NPR = products of the filter's inner product: 3 = a1 q1 + a1 q2 + a2 q1 (two bf16 terms per operand; |d' - d| <= 2^-14 t; reached:
+// 1.86 * 2^-16 t, as above), 1 = a1 q1 only (plain bf16 operands, unit roundoff 2^-8: |p' - p| <= sum |a q| (2^-7 + 2^-16) <=
+// (t / 2) 2^-7 (1 + 2^-9), fp32 accumulation of exact products on top: |d' - d| <= 2^-7 t (1 + 2^-8); reached: 0.96 * 2^-7 t on the
+// same clouds; tested with 2^-6 t): a third of the MFMAs, a quarter of the staging arithmetic, one plane in LDS -- for a wider
+// margin, i.e. more pairs re-checked exactly.  The result is the same bit for bit (the re-check decides).
 template <bool LX, int NPR = 3, class Clouds = DenseClouds>
 // N >= 8192 with the one-product filter: 4 workgroups per CU (128 VGPRs; the re-check's candidate ring 8 -> 4 deep keeps it out of
 // scratch): (8,16384,64,40) 2048 workgroups = 2 rounds of 1024 instead of 2.67 of 768, 1.71 -> 1.54 ms (profiles/r06/knn_occ.txt)
@@ -1190,8 +1191,12 @@ __global__ __launch_bounds__(256, ((LX || NPR != 1) ? 3 : 4)) void knn_bf16a_ker
       // (t = s_i + s_j; bound on |d' - d| above), i.e.  a > (1 - 2^-14) t / 2 - thr / 2.  Tested with 2^-13 for 2^-14 and the right
       // side as  c1 s_j + (c1 s_i - thr / 2),  c1 = (1 - 2^-13) / 2: the roundings of that sum (< 2^-20 t) sit far inside the
       // 2^-15 t of slack; one add and one compare per candidate.  thr = +inf: everything passes; rows past N: nothing does.
+      // A positive thr below 2 FLT_MIN must not halve to zero: all-zero rows seeded with all-zero rows have tau0 = 0 and thr =
+      // next_up(0), the smallest denormal, and with s_i = s_j = a = 0 the test would read 0 < 0 and drop the very pairs at d = 0 that
+      // thr admits.  FLT_MIN for the half instead: a larger half-threshold only sends more pairs to the exact re-check.
       const float thr = (row < N) ? thr_s[rslot] : -INFINITY;
-      const float gi = si * C1 - 0.5f * thr;
+      const float hthr = (thr > 0.f) ? fmaxf(0.5f * thr, 1.17549435e-38f) : 0.5f * thr;
+      const float gi = si * C1 - hthr;
       const float* sj = sjs + cbase + 4 * h;
       unsigned mask = 0u;
 #pragma unroll
