@@ -1399,64 +1399,6 @@ bool launch_seed_bound(const float* x, const float* sq, int64_t rows, Clouds cl,
   return true;
 }
 
-template <int CP, int KC>
-void launch_knn(const float* x, const float* sq, int B, int N, int C, int64_t ldx, int k, int vec_ok,
-                int32_t* idx, const float* tau0, hipStream_t st) {
-  dim3 grid((unsigned)dg::cdiv(N, ROWS), (unsigned)B);
-  if constexpr (CP == 64) {                      // large feature-space graphs: bf16 matrix pipe + exact re-check of the survivors
-    const int m = knn_bf16f_mode();
-    if (!knn_force_valu() && vec_ok && C % 4 == 0 && C > 16 && (m == 1 || (m == 2 && (N >= 8192 || tau0)))) {
-      dg::launch((knn_bf16f_kernel<KC>), grid, dim3(256), 0, st, x, sq, N, C, ldx, k, idx, tau0);
-      return;
-    }
-  }
-  if constexpr (CP >= 16 && CP <= 64) {
-    if (!knn_force_valu()) {
-      if (vec_ok && C % 4 == 0) dg::launch((knn_mfma_kernel<CP, KC, true>), grid, dim3(256), 0, st, x, sq, N, C, ldx, k, idx, tau0);
-      else dg::launch((knn_mfma_kernel<CP, KC, false>), grid, dim3(256), 0, st, x, sq, N, C, ldx, k, idx, tau0);
-      return;
-    }
-  }
-  dg::launch((knn_kernel<CP, KC>), grid, dim3(256), 0, st, x, sq, N, C, ldx, k, vec_ok, idx, (CP <= 4) ? tau0 : (const float*)nullptr);
-}
-
-// packed tower: the list-keeping VALU scan for every C (the bound tau0 only for C <= 4: knn_hist_bound_kernel)
-template <int CP>
-int dispatch_k_packed(const float* x, const float* sq, PackedClouds cl, int max_n, int C, int64_t ldx, int k, int vec_ok,
-                      int32_t* idx, const float* tau0, hipStream_t st) {
-  const dim3 grid((unsigned)dg::cdiv(max_n, ROWS), (unsigned)cl.nseg);
-  const float* t0 = (CP <= 4) ? tau0 : (const float*)nullptr;
-#define DG_KP(KCV) dg::launch((knn_kernel<CP, KCV, PackedClouds>), grid, dim3(256), 0, st, x, sq, cl, C, ldx, k, vec_ok, idx, t0)
-  if (k <= 8) DG_KP(8);
-  else if (k <= 20) DG_KP(20);
-  else if (k <= 40) DG_KP(40);
-  else DG_KP(64);
-#undef DG_KP
-  return dg::check_launch("dgcnn_knn_seg_f32");
-}
-
-// the listed clouds of a packed tower (raw coordinates, k <= 40: dgcnn_knn_seg_mix_f32), at most max_n points each
-int dispatch_k_listed(const char* what, const float* x, const float* sq, ListedClouds cl, int max_n, int C, int64_t ldx, int k, int vec_ok,
-                      int32_t* idx, const float* tau0, hipStream_t st) {
-  const dim3 grid((unsigned)dg::cdiv(max_n, ROWS), (unsigned)cl.nlist);
-#define DG_KL(KCV) dg::launch((knn_kernel<4, KCV, ListedClouds>), grid, dim3(256), 0, st, x, sq, cl, C, ldx, k, vec_ok, idx, tau0)
-  if (k <= 8) DG_KL(8);
-  else if (k <= 20) DG_KL(20);
-  else DG_KL(40);
-#undef DG_KL
-  return dg::check_launch(what);
-}
-
-template <int CP>
-int dispatch_k(const float* x, const float* sq, int B, int N, int C, int64_t ldx, int k, int vec_ok,
-               int32_t* idx, const float* tau0, hipStream_t st) {
-  if (k <= 8) launch_knn<CP, 8>(x, sq, B, N, C, ldx, k, vec_ok, idx, tau0, st);
-  else if (k <= 20) launch_knn<CP, 20>(x, sq, B, N, C, ldx, k, vec_ok, idx, tau0, st);
-  else if (k <= 40) launch_knn<CP, 40>(x, sq, B, N, C, ldx, k, vec_ok, idx, tau0, st);
-  else launch_knn<CP, 64>(x, sq, B, N, C, ldx, k, vec_ok, idx, tau0, st);
-  return dg::check_launch("dgcnn_knn_f32");
-}
-
 }  // namespace
 
 extern "C" int dgcnn_knn_force_valu(int on) {   // A/B switch (tests): 1 = VALU fmaf distances for every C, 0 = MFMA for C > 4
@@ -1483,19 +1425,12 @@ int launch_knn_grid_listed(const char* what, const float* x, const float* sq, co
                            int rows, int max_n, int C, int64_t ldx, int k, int32_t* idx, void* ws, hipStream_t st);
 }  // namespace dg
 
-// workspace = [s_i of every row (B*N floats, padded to 256 bytes) | seed bounds (same size) | scratch of the cell-grid search (C <= 4,
-//              k <= 40) or of the append-form scan (16 < C <= 64: one count and knn_append_cap(k, N) 8-byte entries per row)]
-static size_t knn_sq_bytes(int B, int N) { return (((size_t)B * (size_t)N * sizeof(float)) + 255) & ~(size_t)255; }
 static bool knn_append_lx(int N) { return N < 8192; }     // which form of the append scan (knn_bf16a_kernel<LX>)
 static int knn_append_cap(int k, int N) {    // entries per row buffer: >= k + slack of the form, <= 64 KA_MAXE
   if (knn_append_lx(N)) return k <= 20 ? 256 : (k <= 40 ? 384 : 512);
   return k <= 20 ? 320 : (k <= 40 ? 448 : 512);
 }
 static bool knn_append_shape(int C, int k) { return C > 16 && C <= 64 && C % 4 == 0 && k <= 64; }
-static size_t knn_append_rows_bytes(size_t rows, int cap) {
-  return ((rows * sizeof(int) + 255) & ~(size_t)255) + rows * (size_t)cap * sizeof(unsigned long long);
-}
-static size_t knn_append_bytes(int B, int N, int k) { return knn_append_rows_bytes((size_t)B * (size_t)N, knn_append_cap(k, N)); }
 static int knn_append_tighten_mask(bool lx) {
   static int tight = -1;                     // DGCNN_KNN_TIGHTEN_EVERY (power of two; A/B switch): bound tightening every n-th tile
   if (tight < 0) { const char* e = getenv("DGCNN_KNN_TIGHTEN_EVERY"); tight = e ? atoi(e) : 0; if (tight < 0 || (tight & (tight - 1))) tight = 1; }
@@ -1503,12 +1438,42 @@ static int knn_append_tighten_mask(bool lx) {
   return (tight ? tight : (lx ? 4 : 8)) - 1;
 }
 
-extern "C" int64_t dgcnn_knn_workspace_bytes(int B, int N, int C, int k) {
-  if (B <= 0 || N <= 0) return 0;
-  size_t n = 2 * knn_sq_bytes(B, N);                 // s_i, and the seed bounds of dgcnn_knn_seeded_f32
-  if (dg::knn_grid_applicable(C, k)) n += dg::knn_grid_workspace_bytes(B, N);
-  else if (knn_append_shape(C, k)) n += knn_append_bytes(B, N, k);       // counts + candidate buffers of the append-form scan
-  return (int64_t)n;
+// ---- the workspace of every k-NN entry ---------------------------------------------------------------------------------------------
+// [s_i of every row | bounds of every row: the seeds' or the histogram's (not in the cell-grid-only entry) | scratch: the cell grid's
+// (knn_grid.hip), or the append-form scan's -- one count and `cap` 8-byte entries per row], every region but the last padded to 256
+// bytes.  An entry and its *_workspace_bytes query build the layout with the same function below: the query answers `end`.
+struct KnnWorkspace {
+  char* base;                                // the caller's buffer and its size (null, 0: a size query)
+  size_t bytes;
+  size_t bound, scratch, ent, end;           // byte offsets of the regions (s_i at 0); ent: the append form's entries, after its counts
+  int cap;                                   // entries per row of the append form; 0: the scratch is not the append form's
+  static size_t pad(size_t n) { return (n + 255) & ~(size_t)255; }
+  KnnWorkspace(void* ws, size_t ws_bytes, size_t rows, bool bounds, size_t grid_bytes, int append_cap)
+      : base(static_cast<char*>(ws)), bytes(ws_bytes), bound(pad(rows * sizeof(float))), scratch(bounds ? 2 * bound : bound),
+        ent(scratch + pad(rows * sizeof(int))),
+        end(append_cap ? ent + rows * (size_t)append_cap * sizeof(unsigned long long) : scratch + grid_bytes), cap(append_cap) {}
+  bool aligned() const { return (reinterpret_cast<uintptr_t>(base) & 15) == 0; }
+  bool holds(size_t upto) const { return bytes >= upto; }
+  float* s_i() const { return reinterpret_cast<float*>(base); }
+  float* bounds() const { return holds(scratch) ? reinterpret_cast<float*>(base + bound) : nullptr; }   // null: no room for them
+  void* grid() const { return base + scratch; }
+  int* cnt() const { return reinterpret_cast<int*>(base + scratch); }
+  unsigned long long* entries() const { return reinterpret_cast<unsigned long long*>(base + ent); }
+};
+// dense: the cell grid's scratch for raw coordinates (C <= 4, k <= 40), the append form's for 16 < C <= 64
+static KnnWorkspace knn_ws_dense(void* ws, size_t n, int B, int N, int C, int k) {
+  const bool grid = dg::knn_grid_applicable(C, k);
+  return KnnWorkspace(ws, n, (size_t)B * (size_t)N, true, grid ? dg::knn_grid_workspace_bytes(B, N) : 0,
+                      !grid && knn_append_shape(C, k) ? knn_append_cap(k, N) : 0);
+}
+static KnnWorkspace knn_ws_seg(void* ws, size_t n, int rows, int max_n, int C, int k) {
+  return KnnWorkspace(ws, n, (size_t)rows, true, 0, knn_append_shape(C, k) ? knn_append_cap(k, max_n) : 0);
+}
+static KnnWorkspace knn_ws_seg_grid(void* ws, size_t n, int rows, int nseg) {              // no bounds: the grid uses none
+  return KnnWorkspace(ws, n, (size_t)rows, false, dg::knn_grid_seg_workspace_bytes(rows, nseg), 0);
+}
+static KnnWorkspace knn_ws_seg_mix(void* ws, size_t n, int rows, int n_grid) {             // cell tables for the GRID clouds only
+  return KnnWorkspace(ws, n, (size_t)rows, true, dg::knn_grid_seg_workspace_bytes(rows, n_grid), 0);
 }
 
 // Seeds are used (a) whenever the append-form scan takes the shape (C in {32, 64}: the bound is what makes it possible) and (b) by
@@ -1578,69 +1543,192 @@ extern "C" int dgcnn_knn_hist(int stride) {              // tools / tests: 0 off
   return prev;
 }
 
-static int knn_impl(const char* what, const float* x, int B, int N, int C, int64_t ldx, int k, const int32_t* seed, int64_t ldseed,
-                    int kseed, int32_t* idx, void* ws, size_t ws_bytes, void* stream) {
+
+// ---- one dispatch for dense, packed and listed clouds ------------------------------------------------------------------------------
+namespace {
+
+// What the host knows of the clouds a call searches: the device-side map, how many there are (grid y), the smallest, the largest and
+// the sum of their sizes.  Every size rule is written once in these terms: a kernel's PRECONDITION must hold for the smallest cloud
+// (min_n); grids and the form of a kernel go by the largest (max_n).  Dense (B clouds of N points): min_n = max_n = N.
+template <class Clouds>
+struct CloudSet {
+  Clouds cl;
+  int ny, min_n, max_n;
+  int64_t rows;
+  static constexpr bool kDense = std::is_same<Clouds, DenseClouds>::value;
+  // ListedClouds exist for the raw-coordinate scan of dgcnn_knn_seg_mix_f32 only (C <= 4, k <= 40, no seeds): nothing else is built
+  static constexpr bool kRawOnly = std::is_same<Clouds, ListedClouds>::value;
+  dim3 grid(int rows_per_block) const { return dim3((unsigned)dg::cdiv(max_n, rows_per_block), (unsigned)ny); }
+};
+
+// what every stage of one call passes on unchanged
+struct KnnCall {
+  const char* what;                          // the entry's name
+  const float* x;
+  int C;
+  int64_t ldx;
+  int k, vec_ok;                             // vec_ok: rows are float4-loadable
+  int32_t* idx;
+  KnnWorkspace w;
+  hipStream_t st;
+  const float* sq() const { return w.s_i(); }
+};
+int knn_vec_ok(const float* x, int64_t ldx) { return (ldx % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0); }
+
+void launch_sqnorm(const KnnCall& a, int64_t rows) {
+  dg::launch(sqnorm_kernel, dim3((unsigned)dg::cdiv(rows, SQ_ROWS)), dim3(256), sizeof(float) * SQ_ROWS * (a.C + 1), a.st, a.x, a.ldx, rows,
+             a.C, a.w.s_i());
+}
+
+// Raw coordinates (C <= 4): the histogram bound of every row.  Null (no bound) when it is switched off (stride 0, or a cloud under 256
+// points), VALU distances are forced, the kernel's precondition N >= 4 k stride fails for the smallest cloud, or there is no room.
+template <class Clouds>
+const float* launch_hist_bound(const CloudSet<Clouds>& s, const KnnCall& a) {
+  const int hs = knn_hist_stride(s.min_n);
+  float* tb = a.w.bounds();
+  if (hs == 0 || knn_force_valu() || s.min_n < 4 * a.k * hs || !tb) return nullptr;
+#define DG_HB(HSV) dg::launch((knn_hist_bound_kernel<HSV, Clouds>), s.grid(64), dim3(256), 0, a.st, a.x, a.sq(), s.cl, a.C, a.ldx, a.k, tb)
+  if (hs == 1) DG_HB(1); else if (hs == 2) DG_HB(2); else DG_HB(4);
+#undef DG_HB
+  return tb;
+}
+
+// Bound known in advance (tau0: launch_seed_bound): the append-form scan, then one selection per row
+template <class Clouds>
+void launch_append_scan(const CloudSet<Clouds>& s, const KnnCall& a, const float* tau0) {
+  const bool lx = knn_append_lx(s.max_n);
+  const int npr = knn_append_products(lx), tmask = knn_append_tighten_mask(lx);
+  const KnnWorkspace& w = a.w;
+#define DG_KA(LXV, NPRV) dg::launch((knn_bf16a_kernel<LXV, NPRV, Clouds>), s.grid(ROWS), dim3(256), 0, a.st, a.x, a.sq(), s.cl, a.C, a.ldx, a.k, tau0, w.cap, w.entries(), w.cnt(), tmask)
+  if (lx) { if (npr == 1) DG_KA(true, 1); else DG_KA(true, 3); }
+  else { if (npr == 1) DG_KA(false, 1); else DG_KA(false, 3); }
+#undef DG_KA
+  dg::launch(knn_select_kernel, dim3((unsigned)dg::cdiv(s.rows, 4)), dim3(256), 0, a.st, w.entries(), w.cnt(), s.rows, w.cap, a.k, a.idx);
+}
+
+// The scan that keeps its lists.  Dense, 16 < C <= 64: the bf16 matrix pipe + exact re-check of the survivors (large graphs, or a seed
+// bound); dense, 4 < C <= 64: fp32 distances on the matrix pipe; everything else, and every packed or listed tower: the VALU scan,
+// which takes a bound for C <= 4 only (the histogram's).
+template <int CP, int KC, class Clouds>
+void launch_scan(const CloudSet<Clouds>& s, const KnnCall& a, const float* tau0) {
+  if constexpr (CloudSet<Clouds>::kDense && CP >= 16 && CP <= 64) {
+    const int N = s.max_n, m = knn_bf16f_mode();
+    const bool vec = a.vec_ok && a.C % 4 == 0;
+    if constexpr (CP == 64) {
+      if (!knn_force_valu() && vec && a.C > 16 && (m == 1 || (m == 2 && (N >= 8192 || tau0)))) {
+        dg::launch((knn_bf16f_kernel<KC>), s.grid(ROWS), dim3(256), 0, a.st, a.x, a.sq(), N, a.C, a.ldx, a.k, a.idx, tau0);
+        return;
+      }
+    }
+    if (!knn_force_valu()) {
+      if (vec) dg::launch((knn_mfma_kernel<CP, KC, true>), s.grid(ROWS), dim3(256), 0, a.st, a.x, a.sq(), N, a.C, a.ldx, a.k, a.idx, tau0);
+      else dg::launch((knn_mfma_kernel<CP, KC, false>), s.grid(ROWS), dim3(256), 0, a.st, a.x, a.sq(), N, a.C, a.ldx, a.k, a.idx, tau0);
+      return;
+    }
+  }
+  dg::launch((knn_kernel<CP, KC, Clouds>), s.grid(ROWS), dim3(256), 0, a.st, a.x, a.sq(), s.cl, a.C, a.ldx, a.k, a.vec_ok, a.idx,
+             (CP <= 4) ? tau0 : (const float*)nullptr);
+}
+
+template <int CP, class Clouds>
+void launch_scan_k(const CloudSet<Clouds>& s, const KnnCall& a, const float* tau0) {
+  if (a.k <= 8) launch_scan<CP, 8>(s, a, tau0);
+  else if (a.k <= 20) launch_scan<CP, 20>(s, a, tau0);
+  else if (a.k <= 40 || CloudSet<Clouds>::kRawOnly) launch_scan<CP, 40>(s, a, tau0);
+  else if constexpr (!CloudSet<Clouds>::kRawOnly) launch_scan<CP, 64>(s, a, tau0);
+}
+
+// The all-pairs search of one set of clouds, s_i already in the workspace.  seed: null, or the graph that the entry's seeding rule
+// admitted; append: the append-form scan may take the shape (knn_append_usable, and the workspace holds its scratch).
+template <class Clouds>
+int knn_scan(const CloudSet<Clouds>& s, const KnnCall& a, const int32_t* seed, int64_t ldseed, bool append) {
+  const float* tau0 = nullptr;
+  if constexpr (!CloudSet<Clouds>::kRawOnly) {
+    // the bound of the first k seeds of every row (C in {16, 32, 64}; otherwise none)
+    if (seed && launch_seed_bound(a.x, a.sq(), s.rows, s.cl, a.C, a.ldx, seed, ldseed, a.k, a.w.bounds(), a.st)) tau0 = a.w.bounds();
+  }
+  if constexpr (CloudSet<Clouds>::kRawOnly) launch_scan_k<4>(s, a, launch_hist_bound(s, a));
+  else if (tau0 && append) launch_append_scan(s, a, tau0);
+  else if (a.C <= 4) launch_scan_k<4>(s, a, launch_hist_bound(s, a));
+  else if (a.C <= 16) launch_scan_k<16>(s, a, tau0);
+  else if (a.C <= 64) launch_scan_k<64>(s, a, tau0);
+  else launch_scan_k<128>(s, a, tau0);
+  return dg::check_launch(a.what);
+}
+
+// the append-form scan takes 16 < C <= 64 on float4-loadable rows, unless a switch turns it or the bf16 matrix pipe off
+bool knn_append_usable(const KnnCall& a) {
+  return knn_append_on() && knn_append_shape(a.C, a.k) && a.vec_ok && !knn_force_valu() && knn_bf16f_mode() != 0 && a.w.holds(a.w.end);
+}
+// The two seeding rules.  Both need kseed >= k seeds per row and 32-bit element offsets within a cloud; dgcnn_knn_seed_min_n overrides
+// the cloud size from which either applies.
+// Dense: seeds are used by the list-keeping and matrix-pipe scans (4 < C <= 64, float4-loadable rows) from N >= 4096 without the append
+// form, and from any N with it (the measurements: at g_knn_seed_min_n).
+bool knn_seeds_used_dense(const KnnCall& a, const int32_t* seed, int kseed, int N, bool append) {
+  const int min_n = knn_seed_min_n() >= 0 ? knn_seed_min_n() : (append ? 0 : 4096);
+  return seed && kseed >= a.k && kseed <= 64 && a.C > 4 && a.C <= 64 && a.C % 4 == 0 && a.vec_ok && !knn_force_valu() && N >= min_n &&
+         (int64_t)N * a.ldx < ((int64_t)1 << 31) && a.w.bounds();
+}
+// Packed: seeds are used only together with the append form (the packed list-keeping scan takes no seed bound).
+bool knn_seeds_used_packed(const KnnCall& a, const int32_t* seed, int kseed, int min_n, int max_n, bool append) {
+  const int seed_min = knn_seed_min_n() >= 0 ? knn_seed_min_n() : 0;
+  return append && seed && kseed >= a.k && kseed <= 64 && min_n >= seed_min && (int64_t)max_n * a.ldx < ((int64_t)1 << 31);
+}
+
+int knn_impl(const char* what, const float* x, int B, int N, int C, int64_t ldx, int k, const int32_t* seed, int64_t ldseed, int kseed,
+             int32_t* idx, void* ws, size_t ws_bytes, void* stream) {
   DG_REQUIRE(x && idx && ws, DGCNN_EINVAL, "%s: null pointer", what);
   DG_REQUIRE(B > 0 && N > 0 && C > 0 && ldx >= C, DGCNN_EINVAL, "%s: bad shape B=%d N=%d C=%d", what, B, N, C);
   DG_REQUIRE(k > 0 && k <= N, DGCNN_EINVAL, "%s: k=%d must be in [1, N=%d] (tf.nn.top_k raises otherwise)", what, k, N);
   DG_REQUIRE(k <= 64, DGCNN_EUNSUP, "%s: k=%d > 64 unsupported", what, k);
   DG_REQUIRE(C <= 128, DGCNN_EUNSUP, "%s: C=%d > 128 unsupported", what, C);
-  DG_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0 && ws_bytes >= knn_sq_bytes(B, N), DGCNN_EINVAL,
+  const KnnCall a{what, x, C, ldx, k, knn_vec_ok(x, ldx), idx, knn_ws_dense(ws, ws_bytes, B, N, C, k), (hipStream_t)stream};
+  DG_REQUIRE(a.w.aligned() && a.w.holds(a.w.bound), DGCNN_EINVAL,
              "%s: workspace must be 16-byte aligned and hold dgcnn_knn_workspace_bytes(B, N, C, k) bytes (got %zu)", what, ws_bytes);
-  hipStream_t st = (hipStream_t)stream;
-  float* sq_ws = reinterpret_cast<float*>(ws);
-  const int64_t rows = (int64_t)B * N;
-  const int vec_ok = (ldx % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
-  // the seed bound is used by the matrix-pipe scan kernels (4 < C <= 64) on float4-loadable rows; needs >= k seeds per row
-  const size_t grid_off = 2 * knn_sq_bytes(B, N);
-  const bool append = knn_append_on() && knn_append_shape(C, k) && vec_ok && !knn_force_valu() && knn_bf16f_mode() != 0 &&
-                      ws_bytes >= grid_off + knn_append_bytes(B, N, k);
-  const int min_n = knn_seed_min_n() >= 0 ? knn_seed_min_n() : (append ? 0 : 4096);
-  const bool seeded = seed && kseed >= k && kseed <= 64 && C > 4 && C <= 64 && C % 4 == 0 && vec_ok && !knn_force_valu() &&
-                      N >= min_n && (int64_t)N * ldx < ((int64_t)1 << 31) && ws_bytes >= 2 * knn_sq_bytes(B, N);
+  const CloudSet<DenseClouds> s{DenseClouds(N), B, N, N, (int64_t)B * N};
+  const bool append = knn_append_usable(a);
+  const bool seeded = knn_seeds_used_dense(a, seed, kseed, N, append);
+  launch_sqnorm(a, s.rows);
   // raw coordinates (C <= 4) when the caller provided the scratch: exact search over a uniform cell grid (knn_grid.hip)
-  const bool grid_ws = dg::knn_grid_applicable(C, k) && !knn_force_valu() && ws_bytes >= grid_off + dg::knn_grid_workspace_bytes(B, N);
-  dg::launch(sqnorm_kernel, dim3((unsigned)dg::cdiv(rows, SQ_ROWS)), dim3(256), sizeof(float) * SQ_ROWS * (C + 1), st, x,
-                     ldx, rows, C, sq_ws);
-  if (grid_ws && N >= dg::knn_grid_min_n())
-    return dg::launch_knn_grid(x, sq_ws, B, N, C, ldx, k, idx, reinterpret_cast<char*>(ws) + grid_off, st);
-  float* tau0 = nullptr;
-  if (seeded) {
-    tau0 = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + knn_sq_bytes(B, N));
-    if (!launch_seed_bound(x, sq_ws, rows, DenseClouds(N), C, ldx, seed, ldseed, k, tau0, st)) tau0 = nullptr;      // (the first k seeds of every row)
+  if (dg::knn_grid_applicable(C, k) && !knn_force_valu() && a.w.holds(a.w.end) && N >= dg::knn_grid_min_n())
+    return dg::launch_knn_grid(x, a.sq(), B, N, C, ldx, k, idx, a.w.grid(), a.st);
+  return knn_scan(s, a, seeded ? seed : nullptr, ldseed, append);
+}
+
+// The argument rules that the three packed-tower entries share, in the order they report them.  grid: the entry searches (some of) the
+// clouds with the cell grid.  mix: null, or the grid class of dgcnn_knn_seg_mix_f32 -- min_n / max_n then describe its scan class.
+struct GridClass { int n, max_n; };
+int knn_check_tower(const char* what, bool pointers, int nseg, int rows, int C, int64_t ldx, int k, bool grid, int min_n, int max_n,
+                    const GridClass* mix = nullptr) {
+  DG_REQUIRE(pointers, DGCNN_EINVAL, "%s: null pointer", what);
+  DG_REQUIRE(nseg > 0 && nseg <= 65535 && rows > 0 && C > 0 && ldx >= C, DGCNN_EINVAL, "%s: bad shape nseg=%d rows=%d C=%d", what,
+             nseg, rows, C);
+  DG_REQUIRE(!grid || (C <= 4 && k <= 40), DGCNN_EINVAL, "%s: C=%d k=%d: the cell grid searches raw coordinates (C <= 4) for k <= 40",
+             what, C, k);
+  int smallest = min_n;
+  if (mix) {
+    const int nscan = nseg - mix->n;
+    DG_REQUIRE(mix->n > 0 && mix->n < nseg, DGCNN_EINVAL,
+               "%s: n_grid=%d must be in [1, nseg=%d): a tower of one class goes to dgcnn_knn_seg_f32 or dgcnn_knn_seg_grid_f32", what,
+               mix->n, nseg);
+    DG_REQUIRE(mix->max_n > 0 && min_n > 0 && min_n <= max_n && (int64_t)mix->max_n + (int64_t)min_n * nscan <= rows &&
+                   (int64_t)mix->max_n * mix->n + (int64_t)max_n * nscan >= rows,
+               DGCNN_EINVAL, "%s: cloud sizes grid_max_n=%d scan_min_n=%d scan_max_n=%d do not fit %d rows in %d + %d clouds", what,
+               mix->max_n, min_n, max_n, rows, mix->n, nscan);
+    if (mix->max_n < smallest) smallest = mix->max_n;
+  } else {
+    DG_REQUIRE(min_n > 0 && min_n <= max_n && max_n <= rows && (int64_t)min_n * nseg <= rows && (int64_t)max_n * nseg >= rows,
+               DGCNN_EINVAL, "%s: cloud sizes min_n=%d max_n=%d do not fit %d rows in %d clouds", what, min_n, max_n, rows, nseg);
   }
-  if (tau0 && append) {                          // bound known in advance: append-form scan + one selection per row
-    char* base = reinterpret_cast<char*>(ws) + grid_off;
-    int* cnt = reinterpret_cast<int*>(base);
-    unsigned long long* ent = reinterpret_cast<unsigned long long*>(base + (((size_t)rows * sizeof(int) + 255) & ~(size_t)255));
-    const int cap = knn_append_cap(k, N);
-    const dim3 grid((unsigned)dg::cdiv(N, ROWS), (unsigned)B);
-    const int npr = knn_append_products(knn_append_lx(N));
-    const int tmask = knn_append_tighten_mask(knn_append_lx(N));
-#define DG_KA(LXV, NPRV) dg::launch((knn_bf16a_kernel<LXV, NPRV>), grid, dim3(256), 0, st, x, (const float*)sq_ws, N, C, ldx, k, (const float*)tau0, cap, ent, cnt, tmask)
-    if (knn_append_lx(N)) { if (npr == 1) DG_KA(true, 1); else DG_KA(true, 3); }
-    else { if (npr == 1) DG_KA(false, 1); else DG_KA(false, 3); }
-#undef DG_KA
-    dg::launch(knn_select_kernel, dim3((unsigned)dg::cdiv(rows, 4)), dim3(256), 0, st, (const unsigned long long*)ent, (const int*)cnt, rows,
-               cap, k, idx);
-    return dg::check_launch(what);
-  }
-  if (C <= 4) {
-    // raw coordinates below the cell grid's range: a histogram bound first (the workspace's second s_i-sized region holds it)
-    const int hs = knn_hist_stride(N);
-    if (hs > 0 && !knn_force_valu() && k <= 64 && N >= 4 * k * hs && ws_bytes >= 2 * knn_sq_bytes(B, N)) {
-      float* tb = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + knn_sq_bytes(B, N));
-      const dim3 hg((unsigned)dg::cdiv(N, 64), (unsigned)B);
-      if (hs == 1) dg::launch(knn_hist_bound_kernel<1>, hg, dim3(256), 0, st, x, (const float*)sq_ws, N, C, ldx, k, tb);
-      else if (hs == 2) dg::launch(knn_hist_bound_kernel<2>, hg, dim3(256), 0, st, x, (const float*)sq_ws, N, C, ldx, k, tb);
-      else dg::launch(knn_hist_bound_kernel<4>, hg, dim3(256), 0, st, x, (const float*)sq_ws, N, C, ldx, k, tb);
-      tau0 = tb;
-    }
-    return dispatch_k<4>(x, sq_ws, B, N, C, ldx, k, vec_ok, idx, tau0, st);
-  }
-  if (C <= 16) return dispatch_k<16>(x, sq_ws, B, N, C, ldx, k, vec_ok, idx, tau0, st);
-  if (C <= 64) return dispatch_k<64>(x, sq_ws, B, N, C, ldx, k, vec_ok, idx, tau0, st);
-  return dispatch_k<128>(x, sq_ws, B, N, C, ldx, k, vec_ok, idx, tau0, st);
+  DG_REQUIRE(k > 0 && k <= smallest, DGCNN_EINVAL, "%s: k=%d must be in [1, smallest cloud=%d] (tf.nn.top_k raises otherwise)", what, k,
+             smallest);
+  return DGCNN_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t dgcnn_knn_workspace_bytes(int B, int N, int C, int k) {
+  return (B <= 0 || N <= 0) ? 0 : (int64_t)knn_ws_dense(nullptr, 0, B, N, C, k).end;
 }
 
 extern "C" int dgcnn_knn_f32(const float* x, int B, int N, int C, int64_t ldx, int k, int32_t* idx,
@@ -1660,109 +1748,46 @@ extern "C" int dgcnn_knn_seeded_f32(const float* x, int B, int N, int C, int64_t
 }
 
 // ---- packed towers: clouds of different sizes concatenated row-wise, cloud b = rows [seg_off[b], seg_off[b + 1]) -----------------
-// Every form below is the dense kernel instantiated with PackedClouds (a block maps to its cloud's base and size instead of b N and
-// N); the host-known smallest / largest cloud (min_n, max_n) takes every decision the dense search takes from N.
+// The dense dispatch over PackedClouds (a block maps to its cloud's base and size instead of b N and N).
 extern "C" int64_t dgcnn_knn_seg_workspace_bytes(int rows, int max_n, int C, int k) {
-  if (rows <= 0 || max_n <= 0) return 0;
-  size_t n = 2 * knn_sq_bytes(1, rows);              // s_i, and the seed bounds (or the histogram bounds of C <= 4)
-  if (knn_append_shape(C, k)) n += knn_append_rows_bytes((size_t)rows, knn_append_cap(k, max_n));
-  return (int64_t)n;
+  return (rows <= 0 || max_n <= 0) ? 0 : (int64_t)knn_ws_seg(nullptr, 0, rows, max_n, C, k).end;
 }
 
 extern "C" int dgcnn_knn_seg_f32(const float* x, int64_t ldx, int C, int k, int nseg, const int32_t* seg_off, int rows, int min_n,
                                  int max_n, const int32_t* seed, int64_t ldseed, int kseed, int32_t* idx, void* ws, size_t ws_bytes,
                                  void* stream) {
   const char* what = "dgcnn_knn_seg_f32";
-  DG_REQUIRE(x && idx && ws && seg_off, DGCNN_EINVAL, "%s: null pointer", what);
-  DG_REQUIRE(nseg > 0 && nseg <= 65535 && rows > 0 && C > 0 && ldx >= C, DGCNN_EINVAL, "%s: bad shape nseg=%d rows=%d C=%d", what,
-             nseg, rows, C);
-  DG_REQUIRE(min_n > 0 && min_n <= max_n && max_n <= rows && (int64_t)min_n * nseg <= rows && (int64_t)max_n * nseg >= rows,
-             DGCNN_EINVAL, "%s: cloud sizes min_n=%d max_n=%d do not fit %d rows in %d clouds", what, min_n, max_n, rows, nseg);
-  DG_REQUIRE(k > 0 && k <= min_n, DGCNN_EINVAL, "%s: k=%d must be in [1, smallest cloud=%d] (tf.nn.top_k raises otherwise)", what, k,
-             min_n);
+  if (const int rc = knn_check_tower(what, x && idx && ws && seg_off, nseg, rows, C, ldx, k, false, min_n, max_n)) return rc;
   DG_REQUIRE(k <= 64, DGCNN_EUNSUP, "%s: k=%d > 64 unsupported", what, k);
   DG_REQUIRE(C <= 128, DGCNN_EUNSUP, "%s: C=%d > 128 unsupported", what, C);
   DG_REQUIRE(!seed || (ldseed >= kseed && kseed > 0), DGCNN_EINVAL, "%s: bad seed shape", what);
-  DG_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0 && ws_bytes >= knn_sq_bytes(1, rows), DGCNN_EINVAL,
+  const KnnCall a{what, x, C, ldx, k, knn_vec_ok(x, ldx), idx, knn_ws_seg(ws, ws_bytes, rows, max_n, C, k), (hipStream_t)stream};
+  DG_REQUIRE(a.w.aligned() && a.w.holds(a.w.bound), DGCNN_EINVAL,
              "%s: workspace must be 16-byte aligned and hold dgcnn_knn_seg_workspace_bytes(rows, max_n, C, k) bytes (got %zu)", what,
              ws_bytes);
-  hipStream_t st = (hipStream_t)stream;
-  float* sq_ws = reinterpret_cast<float*>(ws);
-  float* tb = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + knn_sq_bytes(1, rows));
-  const bool tb_ok = ws_bytes >= 2 * knn_sq_bytes(1, rows);
-  const PackedClouds cl{seg_off, nseg};
-  const int vec_ok = (ldx % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
-  const size_t aux = 2 * knn_sq_bytes(1, rows);
-  const bool lx = knn_append_lx(max_n);
-  const int cap = knn_append_cap(k, max_n);
-  const bool append = knn_append_on() && knn_append_shape(C, k) && vec_ok && !knn_force_valu() && knn_bf16f_mode() != 0 &&
-                      ws_bytes >= aux + knn_append_rows_bytes((size_t)rows, cap);
-  const int seed_min = knn_seed_min_n() >= 0 ? knn_seed_min_n() : 0;
-  const bool seeded = append && seed && kseed >= k && kseed <= 64 && min_n >= seed_min && (int64_t)max_n * ldx < ((int64_t)1 << 31);
-  dg::launch(sqnorm_kernel, dim3((unsigned)dg::cdiv(rows, SQ_ROWS)), dim3(256), sizeof(float) * SQ_ROWS * (C + 1), st, x, ldx,
-             (int64_t)rows, C, sq_ws);
-  if (seeded && launch_seed_bound(x, sq_ws, (int64_t)rows, cl, C, ldx, seed, ldseed, k, tb, st)) {
-    char* base = reinterpret_cast<char*>(ws) + aux;
-    int* cnt = reinterpret_cast<int*>(base);
-    unsigned long long* ent = reinterpret_cast<unsigned long long*>(base + (((size_t)rows * sizeof(int) + 255) & ~(size_t)255));
-    const dim3 grid((unsigned)dg::cdiv(max_n, ROWS), (unsigned)nseg);
-    const int npr = knn_append_products(lx);
-    const int tmask = knn_append_tighten_mask(lx);
-#define DG_KA(LXV, NPRV) dg::launch((knn_bf16a_kernel<LXV, NPRV, PackedClouds>), grid, dim3(256), 0, st, x, (const float*)sq_ws, cl, C, ldx, k, (const float*)tb, cap, ent, cnt, tmask)
-    if (lx) { if (npr == 1) DG_KA(true, 1); else DG_KA(true, 3); }
-    else { if (npr == 1) DG_KA(false, 1); else DG_KA(false, 3); }
-#undef DG_KA
-    dg::launch(knn_select_kernel, dim3((unsigned)dg::cdiv(rows, 4)), dim3(256), 0, st, (const unsigned long long*)ent, (const int*)cnt,
-               (int64_t)rows, cap, k, idx);
-    return dg::check_launch(what);
-  }
-  if (C <= 4) {
-    // the histogram bound's precondition N >= 4 k stride must hold for the smallest cloud
-    const int hs = knn_hist_stride(min_n);
-    const float* tau0 = nullptr;
-    if (hs > 0 && !knn_force_valu() && min_n >= 4 * k * hs && tb_ok) {
-      const dim3 hg((unsigned)dg::cdiv(max_n, 64), (unsigned)nseg);
-      if (hs == 1) dg::launch(knn_hist_bound_kernel<1, PackedClouds>, hg, dim3(256), 0, st, x, (const float*)sq_ws, cl, C, ldx, k, tb);
-      else if (hs == 2) dg::launch(knn_hist_bound_kernel<2, PackedClouds>, hg, dim3(256), 0, st, x, (const float*)sq_ws, cl, C, ldx, k, tb);
-      else dg::launch(knn_hist_bound_kernel<4, PackedClouds>, hg, dim3(256), 0, st, x, (const float*)sq_ws, cl, C, ldx, k, tb);
-      tau0 = tb;
-    }
-    return dispatch_k_packed<4>(x, sq_ws, cl, max_n, C, ldx, k, vec_ok, idx, tau0, st);
-  }
-  if (C <= 16) return dispatch_k_packed<16>(x, sq_ws, cl, max_n, C, ldx, k, vec_ok, idx, nullptr, st);
-  if (C <= 64) return dispatch_k_packed<64>(x, sq_ws, cl, max_n, C, ldx, k, vec_ok, idx, nullptr, st);
-  return dispatch_k_packed<128>(x, sq_ws, cl, max_n, C, ldx, k, vec_ok, idx, nullptr, st);
+  const CloudSet<PackedClouds> s{PackedClouds{seg_off, nseg}, nseg, min_n, max_n, (int64_t)rows};
+  const bool append = knn_append_usable(a);
+  const bool seeded = knn_seeds_used_packed(a, seed, kseed, min_n, max_n, append);
+  launch_sqnorm(a, s.rows);
+  return knn_scan(s, a, seeded ? seed : nullptr, ldseed, append);
 }
 
 // ---- packed towers, raw coordinates (C <= 4, k <= 40): the exact cell-grid search of knn_grid.hip with one grid per cloud ---------
-// workspace = [s_i of every tower row (padded to 256 bytes) | sorted records, s_j and original indices of every row, one GridInfo and
-//              one cell table per cloud].  No seed: the grid never used one.  dgcnn_knn_seg_grid_use (knn_grid.hip) is the rule by
-// which a caller chooses between this entry and dgcnn_knn_seg_f32; the indices are the same either way.
+// No seed: the grid never used one.  dgcnn_knn_seg_grid_use (knn_grid.hip) is the rule by which a caller chooses between this entry
+// and dgcnn_knn_seg_f32; the indices are the same either way.
 extern "C" int64_t dgcnn_knn_seg_grid_workspace_bytes(int rows, int nseg) {
-  if (rows <= 0 || nseg <= 0) return 0;
-  return (int64_t)(knn_sq_bytes(1, rows) + dg::knn_grid_seg_workspace_bytes(rows, nseg));
+  return (rows <= 0 || nseg <= 0) ? 0 : (int64_t)knn_ws_seg_grid(nullptr, 0, rows, nseg).end;
 }
 
 extern "C" int dgcnn_knn_seg_grid_f32(const float* x, int64_t ldx, int C, int k, int nseg, const int32_t* seg_off, int rows, int min_n,
                                       int max_n, int32_t* idx, void* ws, size_t ws_bytes, void* stream) {
   const char* what = "dgcnn_knn_seg_grid_f32";
-  DG_REQUIRE(x && idx && ws && seg_off, DGCNN_EINVAL, "%s: null pointer", what);
-  DG_REQUIRE(nseg > 0 && nseg <= 65535 && rows > 0 && C > 0 && ldx >= C, DGCNN_EINVAL, "%s: bad shape nseg=%d rows=%d C=%d", what,
-             nseg, rows, C);
-  DG_REQUIRE(C <= 4 && k <= 40, DGCNN_EINVAL, "%s: C=%d k=%d: the cell grid searches raw coordinates (C <= 4) for k <= 40", what, C, k);
-  DG_REQUIRE(min_n > 0 && min_n <= max_n && max_n <= rows && (int64_t)min_n * nseg <= rows && (int64_t)max_n * nseg >= rows,
-             DGCNN_EINVAL, "%s: cloud sizes min_n=%d max_n=%d do not fit %d rows in %d clouds", what, min_n, max_n, rows, nseg);
-  DG_REQUIRE(k > 0 && k <= min_n, DGCNN_EINVAL, "%s: k=%d must be in [1, smallest cloud=%d] (tf.nn.top_k raises otherwise)", what, k,
-             min_n);
-  DG_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0 && ws_bytes >= (size_t)dgcnn_knn_seg_grid_workspace_bytes(rows, nseg),
-             DGCNN_EINVAL, "%s: workspace must be 16-byte aligned and hold dgcnn_knn_seg_grid_workspace_bytes(rows, nseg) bytes (got %zu)",
-             what, ws_bytes);
-  hipStream_t st = (hipStream_t)stream;
-  float* sq_ws = reinterpret_cast<float*>(ws);
-  dg::launch(sqnorm_kernel, dim3((unsigned)dg::cdiv(rows, SQ_ROWS)), dim3(256), sizeof(float) * SQ_ROWS * (C + 1), st, x, ldx,
-             (int64_t)rows, C, sq_ws);
-  return dg::launch_knn_grid_seg(x, sq_ws, nseg, seg_off, rows, max_n, C, ldx, k, idx, reinterpret_cast<char*>(ws) + knn_sq_bytes(1, rows),
-                                 st);
+  if (const int rc = knn_check_tower(what, x && idx && ws && seg_off, nseg, rows, C, ldx, k, true, min_n, max_n)) return rc;
+  const KnnCall a{what, x, C, ldx, k, knn_vec_ok(x, ldx), idx, knn_ws_seg_grid(ws, ws_bytes, rows, nseg), (hipStream_t)stream};
+  DG_REQUIRE(a.w.aligned() && a.w.holds(a.w.end), DGCNN_EINVAL,
+             "%s: workspace must be 16-byte aligned and hold dgcnn_knn_seg_grid_workspace_bytes(rows, nseg) bytes (got %zu)", what, ws_bytes);
+  launch_sqnorm(a, rows);
+  return dg::launch_knn_grid_seg(x, a.sq(), nseg, seg_off, rows, max_n, C, ldx, k, idx, a.w.grid(), a.st);
 }
 
 // ---- packed towers, raw coordinates: every cloud through the search that suits its own size, in one call ----------------------------
@@ -1770,56 +1795,26 @@ extern "C" int dgcnn_knn_seg_grid_f32(const float* x, int64_t ldx, int C, int k,
 // the all-pairs scan with the histogram bound; both sub-searches are the kernels of the two entries above instantiated with
 // ListedClouds (knn_common.h), launched over their own class only -- grids cdiv(grid_max_n, 256) x n_grid and cdiv(scan_max_n, 64) x
 // (nseg - n_grid), so a small cloud launches no row of blocks for the large ones and owns no cell table.  A pair's D has the same bits
-// in either kernel and both select by (D, j): idx is dgcnn_knn_seg_f32's and dgcnn_knn_seg_grid_f32's, bit for bit.
-// workspace = [s_i of every tower row (padded to 256 bytes) | the scan rows' histogram bounds (same size) | sorted records, s_j and
-//              original indices of every row (24 bytes per row, indexed by tower row), one GridInfo and one cell table per GRID cloud]
+// in either kernel and both select by (D, j): idx is dgcnn_knn_seg_f32's and dgcnn_knn_seg_grid_f32's, bit for bit.  The histogram
+// bounds are those of the scan rows; the grid's records, s_j and original indices (24 bytes per row) are indexed by tower row.
 extern "C" int64_t dgcnn_knn_seg_mix_workspace_bytes(int rows, int n_grid) {
-  if (rows <= 0 || n_grid <= 0) return 0;
-  return (int64_t)(2 * knn_sq_bytes(1, rows) + dg::knn_grid_seg_workspace_bytes(rows, n_grid));
+  return (rows <= 0 || n_grid <= 0) ? 0 : (int64_t)knn_ws_seg_mix(nullptr, 0, rows, n_grid).end;
 }
 
 extern "C" int dgcnn_knn_seg_mix_f32(const float* x, int64_t ldx, int C, int k, int nseg, const int32_t* seg_off, int rows,
                                      const int32_t* cloud_list, int n_grid, int grid_max_n, int scan_min_n, int scan_max_n,
                                      int32_t* idx, void* ws, size_t ws_bytes, void* stream) {
   const char* what = "dgcnn_knn_seg_mix_f32";
-  DG_REQUIRE(x && idx && ws && seg_off && cloud_list, DGCNN_EINVAL, "%s: null pointer", what);
-  DG_REQUIRE(nseg > 0 && nseg <= 65535 && rows > 0 && C > 0 && ldx >= C, DGCNN_EINVAL, "%s: bad shape nseg=%d rows=%d C=%d", what,
-             nseg, rows, C);
-  DG_REQUIRE(C <= 4 && k <= 40, DGCNN_EINVAL, "%s: C=%d k=%d: the cell grid searches raw coordinates (C <= 4) for k <= 40", what, C, k);
-  DG_REQUIRE(n_grid > 0 && n_grid < nseg, DGCNN_EINVAL,
-             "%s: n_grid=%d must be in [1, nseg=%d): a tower of one class goes to dgcnn_knn_seg_f32 or dgcnn_knn_seg_grid_f32", what,
-             n_grid, nseg);
-  DG_REQUIRE(grid_max_n > 0 && scan_min_n > 0 && scan_min_n <= scan_max_n &&
-                 (int64_t)grid_max_n + (int64_t)scan_min_n * (nseg - n_grid) <= rows &&
-                 (int64_t)grid_max_n * n_grid + (int64_t)scan_max_n * (nseg - n_grid) >= rows,
-             DGCNN_EINVAL, "%s: cloud sizes grid_max_n=%d scan_min_n=%d scan_max_n=%d do not fit %d rows in %d + %d clouds", what,
-             grid_max_n, scan_min_n, scan_max_n, rows, n_grid, nseg - n_grid);
-  DG_REQUIRE(k > 0 && k <= scan_min_n && k <= grid_max_n, DGCNN_EINVAL,
-             "%s: k=%d must be in [1, smallest cloud=%d] (tf.nn.top_k raises otherwise)", what, k,
-             scan_min_n < grid_max_n ? scan_min_n : grid_max_n);
-  DG_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0 && ws_bytes >= (size_t)dgcnn_knn_seg_mix_workspace_bytes(rows, n_grid),
-             DGCNN_EINVAL, "%s: workspace must be 16-byte aligned and hold dgcnn_knn_seg_mix_workspace_bytes(rows, n_grid) bytes (got %zu)",
-             what, ws_bytes);
-  hipStream_t st = (hipStream_t)stream;
-  float* sq_ws = reinterpret_cast<float*>(ws);
-  float* tb = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + knn_sq_bytes(1, rows));
-  void* grid_ws = reinterpret_cast<char*>(ws) + 2 * knn_sq_bytes(1, rows);
-  dg::launch(sqnorm_kernel, dim3((unsigned)dg::cdiv(rows, SQ_ROWS)), dim3(256), sizeof(float) * SQ_ROWS * (C + 1), st, x, ldx,
-             (int64_t)rows, C, sq_ws);
-  const int rc = dg::launch_knn_grid_listed(what, x, sq_ws, seg_off, cloud_list, n_grid, rows, grid_max_n, C, ldx, k, idx, grid_ws, st);
+  const GridClass g{n_grid, grid_max_n};
+  if (const int rc = knn_check_tower(what, x && idx && ws && seg_off && cloud_list, nseg, rows, C, ldx, k, true, scan_min_n, scan_max_n, &g))
+    return rc;
+  const KnnCall a{what, x, C, ldx, k, knn_vec_ok(x, ldx), idx, knn_ws_seg_mix(ws, ws_bytes, rows, n_grid), (hipStream_t)stream};
+  DG_REQUIRE(a.w.aligned() && a.w.holds(a.w.end), DGCNN_EINVAL,
+             "%s: workspace must be 16-byte aligned and hold dgcnn_knn_seg_mix_workspace_bytes(rows, n_grid) bytes (got %zu)", what, ws_bytes);
+  launch_sqnorm(a, rows);
+  const int rc = dg::launch_knn_grid_listed(what, x, a.sq(), seg_off, cloud_list, n_grid, rows, grid_max_n, C, ldx, k, idx, a.w.grid(), a.st);
   if (rc != 0) return rc;
   const int nscan = nseg - n_grid;
-  const ListedClouds cl{seg_off, cloud_list + n_grid, nscan};
-  const int vec_ok = (ldx % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
-  // the histogram bound's precondition N >= 4 k stride must hold for the smallest cloud of the SCAN class
-  const int hs = knn_hist_stride(scan_min_n);
-  const float* tau0 = nullptr;
-  if (hs > 0 && !knn_force_valu() && scan_min_n >= 4 * k * hs) {
-    const dim3 hg((unsigned)dg::cdiv(scan_max_n, 64), (unsigned)nscan);
-    if (hs == 1) dg::launch(knn_hist_bound_kernel<1, ListedClouds>, hg, dim3(256), 0, st, x, (const float*)sq_ws, cl, C, ldx, k, tb);
-    else if (hs == 2) dg::launch(knn_hist_bound_kernel<2, ListedClouds>, hg, dim3(256), 0, st, x, (const float*)sq_ws, cl, C, ldx, k, tb);
-    else dg::launch(knn_hist_bound_kernel<4, ListedClouds>, hg, dim3(256), 0, st, x, (const float*)sq_ws, cl, C, ldx, k, tb);
-    tau0 = tb;
-  }
-  return dispatch_k_listed(what, x, sq_ws, cl, scan_max_n, C, ldx, k, vec_ok, idx, tau0, st);
+  return knn_scan(CloudSet<ListedClouds>{ListedClouds{seg_off, cloud_list + n_grid, nscan}, nscan, scan_min_n, scan_max_n, (int64_t)rows},
+                  a, nullptr, 0, false);
 }

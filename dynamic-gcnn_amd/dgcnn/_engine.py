@@ -585,26 +585,40 @@ def knn(x2d, B, N, k, seed=None, seg=None):
         return knn_packed(x2d, k, seg, seed=seed)
     C = x2d.shape[1]
     idx = torch.empty((B, N, k), dtype=torch.int32, device=x2d.device)
-    nws = int(H.load().dgcnn_knn_workspace_bytes(B, N, C, k))           # s_i, seed bounds (+ the cell grid's scratch for raw coordinates)
-    ws = torch.empty((nws,), dtype=torch.uint8, device=x2d.device)
-    Cp, kc = (4 if C <= 4 else 16 if C <= 16 else 64 if C <= 64 else 128), (8 if k <= 8 else 20 if k <= 20 else 40 if k <= 40 else 64)
-    seeded = (KNN_SEED and seed is not None and seed.dim() == 3 and seed.shape[0] == B and seed.shape[1] == N and seed.shape[2] >= k
-              and seed.dtype == torch.int32 and seed.is_contiguous())
-    # bench.py's tag of the CALL: the kernels it launches (the library picks the form: knn.hip:knn_dispatch)
+    ws, nws = _knn_workspace(x2d, "dgcnn_knn_workspace_bytes", B, N, C, k)   # knn.hip:KnnWorkspace
+    Cp, kc = _knn_instance(C, k)
+    seeded = _knn_seed_ok(seed, B, N, k)
+    # bench.py's tag of the CALL: the kernels it launches (the library picks the form: knn.hip:knn_impl, knn_scan)
     if seeded and 16 < C <= 64:
         tag = "knn_call<C%d,k%d>[sqnorm_kernel+knn_seed_bound_kernel+knn_bf16a_kernel+knn_select_kernel]" % (Cp, kc)
     elif C <= 4:
         tag = "knn_call<C%d,k%d>[%s]" % (Cp, kc, "knn_grid_*" if N >= 4096 else "sqnorm_kernel+knn_hist_bound_kernel+knn_kernel")
     else:
         tag = "knn_call<C%d,k%d>[sqnorm_kernel+%s]" % (Cp, kc, "knn_bf16f_kernel" if N >= 8192 else "knn_mfma_kernel")
-    if (KNN_SEED and seed is not None and seed.dim() == 3 and seed.shape[0] == B and seed.shape[1] == N and seed.shape[2] >= k and
-            seed.dtype == torch.int32 and seed.is_contiguous()):
+    if seeded:
         H.call("dgcnn_knn_seeded_f32", x2d.data_ptr(), B, N, C, H.ld2(x2d), k, seed.data_ptr(), int(seed.shape[2]), int(seed.shape[2]),
                idx.data_ptr(), ws.data_ptr(), nws, tag=tag, work=2.0 * B * N * N * C)
     else:
         H.call("dgcnn_knn_f32", x2d.data_ptr(), B, N, C, H.ld2(x2d), k, idx.data_ptr(), ws.data_ptr(), nws, tag=tag,
                work=2.0 * B * N * N * C)
     return idx
+
+
+def _knn_instance(C, k):
+    """(CP, KC) of the scan kernel a shape instantiates (knn.hip:knn_scan, launch_scan_k), for bench.py's tags"""
+    return (4 if C <= 4 else 16 if C <= 16 else 64 if C <= 64 else 128), (8 if k <= 8 else 20 if k <= 20 else 40 if k <= 40 else 64)
+
+
+def _knn_workspace(x2d, query, *shape):
+    """(uint8 tensor, its size): the workspace whose size the library's `query`(*shape) asks for"""
+    nws = int(getattr(H.load(), query)(*shape))
+    return torch.empty((nws,), dtype=torch.uint8, device=x2d.device), nws
+
+
+def _knn_seed_ok(seed, B, N, k):
+    """seed is a usable earlier graph of these clouds: (B, N, >= k) contiguous int32, and seeding is switched on"""
+    return (KNN_SEED and seed is not None and seed.dim() == 3 and seed.shape[0] == B and seed.shape[1] == N and seed.shape[2] >= k
+            and seed.dtype == torch.int32 and seed.is_contiguous())
 
 
 def _knn_grid_mode(lib, C, k):
@@ -624,7 +638,7 @@ def knn_packed(x2d, k, seg, seed=None):
     off = seg.device(x2d.device)
     idx = torch.empty((1, R, k), dtype=torch.int32, device=x2d.device)
     n = seg.host[1:] - seg.host[:-1]
-    Cp, kc = (4 if C <= 4 else 16 if C <= 16 else 64 if C <= 64 else 128), (8 if k <= 8 else 20 if k <= 20 else 40 if k <= 40 else 64)
+    Cp, kc = _knn_instance(C, k)
     # raw coordinates: the cell grid, one per cloud, where the library's rule picks it (the same indices; a seed is not needed).  Mode 1
     # with a per-cloud threshold T > 0: the clouds of at least T points through the grid, the others through the scan, in one call
     lib = H.load()
@@ -633,8 +647,7 @@ def knn_packed(x2d, k, seg, seed=None):
         lst, n_grid, grid_max, scan_min, scan_max = seg.mix(T, x2d.device)
         use_grid = n_grid == seg.nseg
         if 0 < n_grid < seg.nseg:
-            nws = int(lib.dgcnn_knn_seg_mix_workspace_bytes(R, n_grid))
-            ws = torch.empty((nws,), dtype=torch.uint8, device=x2d.device)
+            ws, nws = _knn_workspace(x2d, "dgcnn_knn_seg_mix_workspace_bytes", R, n_grid)
             H.call("dgcnn_knn_seg_mix_f32", x2d.data_ptr(), H.ld2(x2d), C, k, seg.nseg, off.data_ptr(), R, lst.data_ptr(), n_grid, grid_max,
                    scan_min, scan_max, idx.data_ptr(), ws.data_ptr(), nws,
                    tag="knn_seg_call<C4,k%d>[sqnorm_kernel+knn_grid_*+knn_hist_bound_kernel+knn_kernel]" % kc,
@@ -643,16 +656,13 @@ def knn_packed(x2d, k, seg, seed=None):
     else:
         use_grid = C <= 4 and lib.dgcnn_knn_seg_grid_use(C, k, seg.nseg, R, seg.min_n, seg.max_n, int((n * n).sum()))
     if use_grid:
-        nws = int(H.load().dgcnn_knn_seg_grid_workspace_bytes(R, seg.nseg))
-        ws = torch.empty((nws,), dtype=torch.uint8, device=x2d.device)
+        ws, nws = _knn_workspace(x2d, "dgcnn_knn_seg_grid_workspace_bytes", R, seg.nseg)
         H.call("dgcnn_knn_seg_grid_f32", x2d.data_ptr(), H.ld2(x2d), C, k, seg.nseg, off.data_ptr(), R, seg.min_n, seg.max_n,
                idx.data_ptr(), ws.data_ptr(), nws, tag="knn_seg_call<C4,k%d>[sqnorm_kernel+knn_grid_*]" % kc,
                work=2.0 * float((n * n).sum()) * C)
         return idx
-    nws = int(H.load().dgcnn_knn_seg_workspace_bytes(R, seg.max_n, C, k))
-    ws = torch.empty((nws,), dtype=torch.uint8, device=x2d.device)
-    seeded = (KNN_SEED and seed is not None and seed.dim() == 3 and seed.shape[0] == 1 and seed.shape[1] == R and seed.shape[2] >= k
-              and seed.dtype == torch.int32 and seed.is_contiguous())
+    ws, nws = _knn_workspace(x2d, "dgcnn_knn_seg_workspace_bytes", R, seg.max_n, C, k)
+    seeded = _knn_seed_ok(seed, 1, R, k)
     if seeded and 16 < C <= 64:
         tag = "knn_seg_call<C%d,k%d>[sqnorm_kernel+knn_seed_bound_kernel+knn_bf16a_kernel+knn_select_kernel]" % (Cp, kc)
     else:
