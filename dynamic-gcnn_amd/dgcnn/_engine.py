@@ -1781,17 +1781,38 @@ def mark_head_gradients_complete():
     c.tape.append(bwd)
 
 
-def softmax_loss(logits2d, labels, weight, want_grad):
-    """-> (softmax (R,ncls), scal tensor [loss, accuracy] on device).  Seeds d(logits) if want_grad."""
+def softmax_loss(logits2d, labels, weight, want_grad, seg=None, per_cloud=False):
+    """-> (softmax (R,ncls), scal tensor [loss, accuracy] on device).  Seeds d(logits) if want_grad.
+    per_cloud with a Segments `seg`: loss, accuracy and the seed are taken cloud by cloud (csrc/seg_loss.hip) -- scal is the mean
+    over the clouds of the per-cloud means, d(logits) the sum of their gradients, what nseg micro-steps of -mbs 1 add up to -- and
+    the (nseg, 2) device tensor [loss, accuracy] of every cloud is returned as a third value (None without labels)."""
     c = ctx()
     R, ncls = logits2d.shape
     assert logits2d.is_contiguous()
-    sm = torch.empty((R, ncls), dtype=torch.float32, device=logits2d.device)
-    scal = H.zeros(2, torch.float32, logits2d.device)      # (its own tensor: the caller reads it after later towers' begin_step)
+    dev = logits2d.device
+    sm = torch.empty((R, ncls), dtype=torch.float32, device=dev)
     dl = None
     if want_grad:
         dl, _ = c.grad_w(logits2d)          # (written, not accumulated: a first touch of a whole root needs no zero fill)
         assert dl is not None and dl.is_contiguous()
+    if per_cloud and seg is not None:
+        if seg.rows != R:
+            raise ValueError("softmax_loss: the offsets end at %d, the logits have %d rows" % (seg.rows, R))
+        cs = None
+        scal = torch.empty(2, dtype=torch.float32, device=dev)      # (written by the call, as cloud_scal is)
+        ws = None
+        if labels is not None:
+            cs = torch.empty((seg.nseg, 2), dtype=torch.float32, device=dev)
+            need = int(H.load().dgcnn_seg_softmax_xent_workspace_bytes(R, seg.nseg))
+            ws = c.workspace()
+            if ws.numel() < need:
+                ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        else:
+            H.memset(scal)                  # (no labels: nothing writes the scalars; keep the dense call's zeros)
+        H.call("dgcnn_seg_softmax_xent_f32", logits2d.data_ptr(), H._p(labels), H._p(weight), R, ncls, seg.device(dev).data_ptr(),
+               seg.nseg, sm.data_ptr(), H._p(dl), H._p(cs), scal.data_ptr(), H._p(ws), 0 if ws is None else ws.numel())
+        return sm, scal, cs
+    scal = H.zeros(2, torch.float32, dev)      # (its own tensor: the caller reads it after later towers' begin_step)
     H.call("dgcnn_softmax_xent_f32", logits2d.data_ptr(), H._p(labels), H._p(weight), R, ncls, sm.data_ptr(),
            H._p(dl), scal.data_ptr())
     return sm, scal

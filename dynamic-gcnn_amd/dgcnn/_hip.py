@@ -138,6 +138,8 @@ PROTOTYPES = {
     "dgcnn_pad_copy_f32": [c_vp, c_i64, c_int, c_vp, c_int, c_i64, c_vp],
     "dgcnn_copy2d_f32": [c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_int, c_vp],
     "dgcnn_softmax_xent_f32": [c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp],
+    "dgcnn_seg_softmax_xent_workspace_bytes": [c_int, c_int],
+    "dgcnn_seg_softmax_xent_f32": [c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp],
     "dgcnn_axpby_f32": [c_vp, c_f32, c_vp, c_f32, c_i64, c_vp],
     "dgcnn_adam_f32": [c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_vp],
     "dgcnn_edge_mlp_bf16_supported": [c_int, c_int, c_int],
@@ -174,7 +176,7 @@ PROTOTYPES = {
 
 INT64_RESULTS = ("dgcnn_knn_workspace_bytes", "dgcnn_knn_seg_workspace_bytes", "dgcnn_knn_seg_grid_workspace_bytes",
                  "dgcnn_knn_seg_mix_workspace_bytes", "dgcnn_edge_mlp_bf16_bwd_workspace_bytes", "dgcnn_seg_colsum_workspace_bytes",
-                 "dgcnn_seg_stats_workspace_bytes")      # byte counts; every other entry point returns an int status
+                 "dgcnn_seg_stats_workspace_bytes", "dgcnn_seg_softmax_xent_workspace_bytes")      # byte counts; every other entry point returns an int status
 
 _lib = None
 

@@ -61,6 +61,11 @@ _OPTIONS = [
                                                 "the predictions of -mbs 1, whatever shares the micro-batch (inference only)"),
     ("BN_PER_CLOUD_TRAIN", "-bpct", _BOOL, False, "t", "per-cloud BatchNorm (BN_PER_CLOUD) with its backward: a tower of several clouds "
                                                        "trains -- and validates -- cloud by cloud, as -mbs 1 does"),
+    ("LOSS_PER_CLOUD", "-lpc", _BOOL, False, "ti", "loss, accuracy and the seed of the backward of a tower of several clouds are taken cloud by "
+                                                   "cloud: the gradient is the sum, the logged loss / accuracy the mean, of the per-cloud "
+                                                   "means, as -mbs 1 accumulates and logs them (equal to -mbs 1 only together with per-cloud "
+                                                   "BatchNorm: --bn_per_cloud_train / --bn_per_cloud); inference also writes one "
+                                                   "loss / accuracy row per entry"),
 ]
 
 

@@ -33,6 +33,7 @@ from .trainval import trainval
 TRAIN_COLUMNS = ("iter,epoch,titer,ttrain,tio,tsave,tsummary,"
                  "tsumiter,tsumtrain,tsumio,tsumsave,tsumsummary,loss,accuracy")
 INFERENCE_COLUMNS = "iter,epoch,titer,tinference,tio,tsumiter,tsuminference,tsumio,loss,accuracy"
+ENTRY_COLUMNS = "entry,points,loss,accuracy"      # LOSS_PER_CLOUD: inference_entries-%07d.csv, one row per entry
 
 
 def round_decimals(val, digits):
@@ -91,6 +92,7 @@ class Handlers(object):
     csv_logger = None
     weight_io = None
     train_logger = None
+    entry_logger = None
     trainer = None
     iteration = 0
     rank = 0
@@ -164,6 +166,8 @@ def prepare(flags):
         if flags.TRAIN:
             h.train_logger = open("%s/summary-%07d.csv" % (flags.LOG_DIR, loaded), "w")
             h.train_logger.write("iter,accuracy,loss\n")
+        elif getattr(flags, "LOSS_PER_CLOUD", False) and getattr(flags, "LABEL_KEY", ""):
+            h.entry_logger = open("%s/inference_entries-%07d.csv" % (flags.LOG_DIR, loaded), "w")
     return h
 
 
@@ -384,9 +388,40 @@ def train_loop(flags, h):
     h.data_io.finalize()
 
 
+def _entry_rows(h, per_cloud, points, idx):
+    """LOSS_PER_CLOUD: (points, loss, accuracy) of every entry of the batch on rank 0, in batch order ([] on the other ranks).
+    per_cloud: this replica's (nseg, 2) [loss, accuracy] tensors, tower by tower; points: the point count of each of their clouds.
+    One device -> host copy.  Replicas gather to rank 0 on the torch.distributed control-plane group, as the softmax rows do
+    (_gather_rows: the entry indices must be rank 0's); the rows travel as host objects, so shards need not hold equally many
+    clouds."""
+    local = torch.cat([t.reshape(-1, 2) for t in per_cloud]).to(torch.float64).cpu().numpy()
+    if local.shape[0] != len(points):
+        raise RuntimeError("inference_loop: %d per-cloud results for %d clouds" % (local.shape[0], len(points)))
+    rows = [np.array([float(n), l, a]) for n, (l, a) in zip(points, local)]
+    if h.world == 1:
+        return rows
+    dist = parallel.dist_state()[0]
+    if dist is None:
+        raise RuntimeError("LOSS_PER_CLOUD with more than one replica needs torch.distributed for the control plane "
+                           "(bin/dgcnn.py initialises a gloo group next to the RCCL communicator)")
+    box = [np.asarray(idx, dtype=np.int64).tolist()]
+    dist.broadcast_object_list(box, src=0)
+    same = [None] * h.world
+    dist.all_gather_object(same, box[0] == np.asarray(idx, dtype=np.int64).tolist())
+    if not all(same):                                   # (every rank learns it: nobody is left waiting in the gather below)
+        raise RuntimeError("inference_loop: rank(s) %s drew different entry indices than rank 0 (data sources must be seeded "
+                           "identically on every replica)" % ", ".join(str(r) for r, ok in enumerate(same) if not ok))
+    parts = [None] * h.world if h.rank == 0 else None
+    dist.gather_object(rows, parts, dst=0)
+    return [r for part in parts for r in part] if h.rank == 0 else []
+
+
 def inference_loop(flags, h):
     if h.csv_logger:
         h.csv_logger.write(INFERENCE_COLUMNS + "\n")
+    if h.entry_logger:
+        h.entry_logger.write(ENTRY_COLUMNS + "\n")
+    per_entry = bool(getattr(flags, "LOSS_PER_CLOUD", False))
     tsum = dict(iter=0.0, inference=0.0, io=0.0)
     has_label = bool(getattr(flags, "LABEL_KEY", ""))
     lo, _ = parallel.shard_bounds(int(flags.BATCH_SIZE), h.rank, h.world)
@@ -403,7 +438,7 @@ def inference_loop(flags, h):
         t_io = time.time() - t0
 
         t0 = time.time()
-        softmax, losses, accs = [], [], []
+        softmax, losses, accs, clouds, points = [], [], [], [], []
         for step in _micro_batches(flags, h, data, label, weight):
             dv, lv, wv = step[:3]
             ov = step[3] if len(step) > 3 else [None] * len(dv)          # (PACK_TOWERS: packed towers carry their offsets)
@@ -418,6 +453,10 @@ def inference_loop(flags, h):
             if has_label:
                 accs.append(res[-2])
                 losses.append(res[-1])
+                if per_entry:
+                    clouds += h.trainer.per_cloud_scalars()
+                    for d, o in zip(dv, ov):
+                        points += [int(d.shape[1])] * int(d.shape[0]) if o is None else [int(n) for n in np.diff(np.asarray(o))]
         loss, acc = _replica_mean(h, losses), _replica_mean(h, accs)
         if not has_label:
             torch.cuda.synchronize()
@@ -430,6 +469,12 @@ def inference_loop(flags, h):
             if h.rank == 0:
                 for at, row in enumerate(rows):
                     h.data_io.store(idx[at], row)
+
+        if per_entry and has_label:
+            rows = _entry_rows(h, clouds, points, idx)
+            if h.entry_logger:
+                for at, row in enumerate(rows):
+                    h.entry_logger.write("%d,%d,%.9g,%.9g\n" % (int(idx[at]), int(row[0]), row[1], row[2]))
 
         epoch = it * float(flags.BATCH_SIZE) / h.data_io.num_entries()
         t_spent = time.time() - t_iter
@@ -446,10 +491,13 @@ def inference_loop(flags, h):
             sys.stdout.flush()
             if h.csv_logger:
                 h.csv_logger.flush()
+            if h.entry_logger:
+                h.entry_logger.flush()
         h.iteration += 1
 
-    if h.csv_logger:
-        h.csv_logger.close()
+    for f in (h.csv_logger, h.entry_logger):
+        if f:
+            f.close()
     h.data_io.finalize()
 
 

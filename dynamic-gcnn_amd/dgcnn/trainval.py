@@ -143,6 +143,8 @@ class trainval(object):
         ug = str(getattr(f, "USE_GRAPH", "0")).lower()
         self._use_graph = ug if ug in ("auto", "plan") else ug in ("1", "true", "yes", "on", "graph")
         self._static_inputs = bool(getattr(f, "STATIC_INPUTS", False))
+        self._dense_segs = {}          # LOSS_PER_CLOUD: (B, N) -> Segments with the offsets b * N of a dense tower (device copy cached)
+        self._per_cloud = []           # ... one per tower of the last inference / accum_gradient call
         return self
 
     def _split_reduce(self):
@@ -176,6 +178,25 @@ class trainval(object):
                 raise ValueError("feed_dict: %d data towers but %d %s towers" % (n, len(res[key]), key))
         return res
 
+    def _loss_per_cloud(self):
+        return bool(getattr(self._flags, "LOSS_PER_CLOUD", False))
+
+    def _dense_seg(self, B, N):
+        """LOSS_PER_CLOUD on a dense (B, N, C) tower with B > 1: its clouds as a Segments with the offsets b * N.  Made (and copied
+        to the device) OUTSIDE any recording: a replayed step reads the cached device offsets."""
+        seg = self._dense_segs.get((B, N))
+        if seg is None:
+            if len(self._dense_segs) >= GRAPH_SEEN_MAX:
+                self._dense_segs.clear()
+            seg = self._dense_segs[(B, N)] = E.Segments(np.arange(B + 1, dtype=np.int64) * N)
+        seg.device(self._ctx.device)
+        return seg
+
+    def per_cloud_scalars(self):
+        """LOSS_PER_CLOUD: one (nseg, 2) device tensor [loss, accuracy] per tower of the last inference / accum_gradient call that
+        had labels, cloud by cloud in tower order -- the values -mbs 1 would have logged per micro-step."""
+        return list(self._per_cloud)
+
     def _to_dev(self, a, dtype):
         if a is None:
             return None
@@ -183,7 +204,8 @@ class trainval(object):
         return t.to(device=self._ctx.device, dtype=dtype, non_blocking=True).contiguous()
 
     def _tower(self, data, label, weight, train, offsets=None):
-        """forward (+ backward when train) of one tower; returns (softmax (MBS,N,ncls), scal[loss, acc]).
+        """forward (+ backward when train) of one tower; returns (softmax (MBS,N,ncls), scal[loss, acc], cloud) -- cloud: the
+        (nseg, 2) per-cloud [loss, accuracy] tensor under LOSS_PER_CLOUD with labels, else None.
         offsets: a packed tower -- softmax (1,R,ncls), loss / accuracy the mean over its R rows (the reduce_mean of
         trainval.py:52 on a (1, R) tower: the dense value when the clouds are equal-sized)."""
         if offsets is not None:
@@ -193,6 +215,8 @@ class trainval(object):
         wgt = self._to_dev(weight, torch.float32)
         if pts.dim() != 3:
             raise ValueError("points must be (MINIBATCH_SIZE, N, NUM_CHANNEL), got %s" % (tuple(pts.shape),))
+        if self._loss_per_cloud() and pts.shape[0] > 1:
+            self._dense_seg(int(pts.shape[0]), int(pts.shape[1]))      # (made before a recording can start)
         if (getattr(self._flags, "BN_PER_CLOUD", False) or getattr(self._flags, "BN_PER_CLOUD_TRAIN", False)) and pts.shape[0] > 1:
             return self._tower_eager(pts, lab, wgt, train)          # (model.build runs it as a packed tower: always eager)
         kind = self._wants_graph(pts.shape[0] * pts.shape[1])
@@ -245,12 +269,25 @@ class trainval(object):
         else:
             logits = model.build(pts, self._flags)                   # trainval.py:38
         B, N, ncls = logits.shape
-        sm, scal = E.softmax_loss(logits.view(B * N, ncls), None if lab is None else lab.view(-1),
-                                  None if wgt is None else wgt.view(-1), want_grad=bool(train))
+        lpc_seg = None
+        if self._loss_per_cloud():
+            # cloud by cloud: a packed tower through its Segments, a dense one with B > 1 through the offsets b * N; one cloud
+            # (B = 1, or a packed tower of one) is what the dense call computes already
+            lpc_seg = seg if seg is not None else (self._dense_seg(B, N) if B > 1 else None)
+            if lpc_seg is not None and lpc_seg.nseg == 1:
+                lpc_seg = None
+        if lpc_seg is not None:
+            sm, scal, cloud = E.softmax_loss(logits.view(B * N, ncls), None if lab is None else lab.view(-1),
+                                             None if wgt is None else wgt.view(-1), want_grad=bool(train), seg=lpc_seg,
+                                             per_cloud=True)
+        else:
+            sm, scal = E.softmax_loss(logits.view(B * N, ncls), None if lab is None else lab.view(-1),
+                                      None if wgt is None else wgt.view(-1), want_grad=bool(train))
+            cloud = scal.view(1, 2) if (self._loss_per_cloud() and lab is not None) else None
         if train:
             c.backward()                                             # compute_gradients, trainval.py:54
         c.recording = False
-        return sm.view(B, N, ncls), scal
+        return sm.view(B, N, ncls), scal, cloud
 
     def _tower_eager(self, pts, lab, wgt, train):
         return self._tower_body(pts, lab, wgt, train)
@@ -274,7 +311,7 @@ class trainval(object):
         c = self._ctx
         hooked = c.head_grads_hook is not None
         key = (kind, tuple(pts.shape), bool(train), lab is not None, wgt is not None, float(E.DROPOUT_KEEP), H.gemm_arith(),
-               E.WGRAD_SIDE_STREAM, E.HEAD_PLANES, E.DETERMINISTIC, E.EDGE_MLP_DTYPE, hooked,
+               E.WGRAD_SIDE_STREAM, E.HEAD_PLANES, E.DETERMINISTIC, E.EDGE_MLP_DTYPE, hooked, self._loss_per_cloud(),
                int(torch.cuda.current_stream().cuda_stream))     # (a plan bakes in the streams that were current at record time)
         ent = self._graphs.get(key)
         if ent is not None:
@@ -302,7 +339,7 @@ class trainval(object):
             if ent is None:
                 return None
             if kind == "plan":                          # recording a plan RUNS the step: this call is done
-                return ent["sm"].clone(), ent["scal"].clone()
+                return self._entry_outputs(ent)
         else:
             self._graphs.move_to_end(key)
         # the recorded step reads its OWN input buffers: stage the caller's tensors into them -- unless this very tensor OBJECT (kept
@@ -334,11 +371,19 @@ class trainval(object):
         c.stat_off = max(c.stat_off, ent["stat_used"])       # (the next eager step re-zeroes what this replay dirtied)
         # the replay's output buffers are overwritten by the next replay of this key: hand out copies (stream ordered),
         # so that several towers / micro-steps of one shape each keep their own softmax and [loss, accuracy]
-        return ent["sm"].clone(), ent["scal"].clone()
+        return self._entry_outputs(ent)
+
+    @staticmethod
+    def _entry_outputs(ent):
+        return ent["sm"].clone(), ent["scal"].clone(), None if ent.get("cloud") is None else ent["cloud"].clone()
 
     def _capture(self, key, pts, lab, wgt, train, kind):
         c = self._ctx
         ent = {"pts": pts.clone(), "lab": None if lab is None else lab.clone(), "wgt": None if wgt is None else wgt.clone()}
+        if self._loss_per_cloud() and pts.shape[0] > 1:
+            # the recorded launches hold the address of this Segments' device offsets: the entry keeps it alive, whatever
+            # happens to the cache it came from
+            ent["seg"] = self._dense_seg(int(pts.shape[0]), int(pts.shape[1]))
         hook = c.head_grads_hook
         try:
             c.ensure_arena(int(pts.shape[0]) * int(pts.shape[1]))
@@ -359,14 +404,14 @@ class trainval(object):
                 c.advance_seed()
                 with torch.cuda.use_mem_pool(pool):
                     with H.Plan.record() as plan:
-                        ent["sm"], ent["scal"] = self._tower_body(ent["pts"], ent["lab"], ent["wgt"], train)
+                        ent["sm"], ent["scal"], ent["cloud"] = self._tower_body(ent["pts"], ent["lab"], ent["wgt"], train)
                 ent["plan"], ent["pool"], ent["head_reduced"] = plan, pool, self._head_reduced
                 ent["info"] = plan.info()
             else:
                 c.head_grads_hook = None                 # (a captured HIP graph cannot carry the RCCL call)
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
-                    ent["sm"], ent["scal"] = self._tower_body(ent["pts"], ent["lab"], ent["wgt"], train)
+                    ent["sm"], ent["scal"], ent["cloud"] = self._tower_body(ent["pts"], ent["lab"], ent["wgt"], train)
                 ent["graph"] = g
             if c.capture_extent is not None and c.stat_off > c.capture_extent:
                 # the recorded memset covers less than the step writes (the slot count or the arena changed between the sighting and
@@ -398,7 +443,8 @@ class trainval(object):
             self._graphs[key] = ent
             if ent.pop("discard", False):                        # results stand, the recording does not (see above)
                 self._graph_seen[key] = 0
-                out = {"sm": ent["sm"].clone(), "scal": ent["scal"].clone()}
+                out = {"sm": ent["sm"].clone(), "scal": ent["scal"].clone(),
+                       "cloud": None if ent.get("cloud") is None else ent["cloud"].clone()}
                 self._drop_graph(key)
                 return out if kind == "plan" else None
             if ent["arena"] != c.arena_key():                    # (cannot happen after ensure_arena; never replay such a graph)
@@ -441,12 +487,15 @@ class trainval(object):
         """trainval.py:103-108: [softmax_tower0, ..., (accuracy, loss)].  offsets: feed_dict (packed towers: softmax (1,R,ncls))."""
         fd = self.feed_dict(data, label, weight, offsets)
         outs, scals = [], []
+        self._per_cloud = []
         for i in range(len(fd["data"])):
-            sm, scal = self._tower(fd["data"][i], fd["label"][i] if label is not None else None,
-                                   fd["weight"][i] if weight is not None else None, train=False,
-                                   **({} if fd["offsets"][i] is None else {"offsets": fd["offsets"][i]}))
+            sm, scal, cloud = self._tower(fd["data"][i], fd["label"][i] if label is not None else None,
+                                          fd["weight"][i] if weight is not None else None, train=False,
+                                          **({} if fd["offsets"][i] is None else {"offsets": fd["offsets"][i]}))
             outs.append(sm)
             scals.append(scal)
+            if cloud is not None:
+                self._per_cloud.append(cloud)
         if label is not None:
             s = torch.stack(scals).mean(0)                           # trainval.py:59-60
             outs += [s[1], s[0]]
@@ -484,10 +533,13 @@ class trainval(object):
             saved = c.flat_grad.clone()
             H.memset(c.flat_grad)
         scals = []
+        self._per_cloud = []
         for i in range(T):
-            _, scal = self._tower(fd["data"][i], fd["label"][i], fd["weight"][i] if weight is not None else None,
-                                  train=True, **({} if fd["offsets"][i] is None else {"offsets": fd["offsets"][i]}))
+            _, scal, cloud = self._tower(fd["data"][i], fd["label"][i], fd["weight"][i] if weight is not None else None,
+                                         train=True, **({} if fd["offsets"][i] is None else {"offsets": fd["offsets"][i]}))
             scals.append(scal)
+            if cloud is not None:
+                self._per_cloud.append(cloud)
         if T > 1:                                                     # mean over towers, trainval.py:64-73
             H.call("dgcnn_axpby_f32", saved.data_ptr(), 1.0, c.flat_grad.data_ptr(), 1.0 / T, c.flat_grad.numel())
         s = scals[0] if T == 1 else torch.stack(scals).mean(0)

@@ -588,6 +588,28 @@ int dgcnn_softmax_xent_f32(const float* logits, const int32_t* labels, const flo
                            int64_t rows, int ncls, float* softmax, float* dlogits, float* scal,
                            void* stream);
 
+/* ---- the same CLOUD BY CLOUD for a packed tower (csrc/seg_loss.hip): what M micro-steps of `-mbs 1` compute.  Cloud b = rows
+ * [seg_off[b], seg_off[b + 1]) (seg_off = int32[nseg + 1] on the device, STRICTLY increasing from 0 to rows: no empty cloud -- device
+ * memory cannot be checked on the host, and an empty cloud would divide by n_b = 0 and leave a partial slot unwritten), n_b rows:
+ *   l_b = (1 / n_b) sum_{r in b} w_r (log sum_c e^{z_rc} - z_{r, lab_r}),   a_b = #{r in b : FIRST arg-max of z_r == lab_r} / n_b
+ *   (a negative label adds nothing to either sum but counts in n_b; w_r = 1 when weight == NULL),
+ *   dlogits_r = (softmax_r - onehot_r) * w_r / n_b: the SUM over the clouds of the per-cloud means (micro-steps add up),
+ *   cloud_scal = float[nseg][2] = {l_b, a_b},  scal = float[2] = {(1 / nseg) sum_b l_b, (1 / nseg) sum_b a_b}.
+ * cloud_scal and scal are WRITTEN, not accumulated (no zeroing by the caller).  The per-row arithmetic is dgcnn_softmax_xent_f32's
+ * operation for operation with 1.0f / n_b for its 1.0f / rows: a one-cloud tower gives its softmax and dlogits bit for bit.  The
+ * sums are taken in ONE fixed order in every dgcnn_set_stat_slots setting (no atomics; two calls are bit-identical), by the two
+ * stages of dgcnn_seg_colstats_f32: 64-row chunks cut at the cloud boundaries (grids over chunks, never one workgroup per cloud),
+ * per (chunk, cloud) piece fp32 per wave over its <= 16 rows, the four waves in double; then a cloud's pieces first chunk to
+ * last in double, l_b = float(sum * (1.0 / n_b)), a_b = float(count / n_b), and the clouds b-ascending in double for scal.
+ * labels == NULL: the softmax only (cloud_scal / scal / ws untouched and may be NULL).  softmax or dlogits may be NULL; dlogits
+ * needs labels.  ws: dgcnn_seg_softmax_xent_workspace_bytes(rows, nseg) bytes (host only; 0 for an empty tower), 8-byte aligned.
+ * DGCNN_EINVAL -- before anything is launched or written -- for a null logits / seg_off (with labels: cloud_scal / scal / ws),
+ * non-positive sizes, nseg > rows, nseg > 65535, a workspace that is too small or misaligned. */
+int64_t dgcnn_seg_softmax_xent_workspace_bytes(int rows, int nseg);
+int dgcnn_seg_softmax_xent_f32(const float* logits, const int32_t* labels, const float* weight, int rows, int ncls,
+                               const int32_t* seg_off, int nseg, float* softmax, float* dlogits, float* cloud_scal, float* scal,
+                               void* ws, size_t ws_bytes, void* stream);
+
 /* ---- dgcnn/trainval.py:17,75-80: accumulators + tf.train.AdamOptimizer ---------------------- */
 /* y = a*x + b*y over n elements */
 int dgcnn_axpby_f32(const float* x, float a, float* y, float b, int64_t n, void* stream);
