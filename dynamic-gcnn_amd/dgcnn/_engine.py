@@ -1335,7 +1335,10 @@ def edge_conv_block(x, B, N, k, num_filters, relu1=True, outs=None, net2=None, s
 
     def bf16_operands():
         """The literal edge tensor in fp32 (the difference x_j - x_i BEFORE any rounding; channels padded to a multiple of 4 so
-        that the products take the float4 path) and the matching weight rows -- the operands the bf16 products round."""
+        that the products take the float4 path) and the matching weight rows -- the operands the bf16 products round.
+        dgcnn_gemm_f32 rounds its operands (arith = 1) only on its float4 path with N > 4 (include/dgcnn_hip.h); where the products
+        E W0 and E^T dY (both N = F) will not take it, E and the weight are rounded here instead: rounded values are bf16 values, so
+        the fp32 product of them is the mode's arithmetic.  (Rounding is idempotent: the other shapes see the same bits as before.)"""
         xg, Wp = x, W0
         if Cp != C:
             xg = H.zeros((R, Cp), torch.float32, x.device)
@@ -1345,6 +1348,12 @@ def edge_conv_block(x, B, N, k, num_filters, relu1=True, outs=None, net2=None, s
             H.call("dgcnn_copy2d_f32", W0[C:].data_ptr(), F, Wp[Cp:Cp + C].data_ptr(), F, C, F, 0)
         E_ = torch.empty((R * k, 2 * Cp), dtype=torch.float32, device=x.device)
         H.call("dgcnn_edge_gather_f32", xg.data_ptr(), H.ld2(xg), idx.data_ptr(), B, N, Cp, k, E_.data_ptr())   # ops.py:21-40
+        if not (F % 4 == 0 and F > 4 and H.ld2(Wp) % 4 == 0 and Wp.data_ptr() % 16 == 0):
+            H.call("dgcnn_round_bf16_f32", E_.data_ptr(), E_.data_ptr(), E_.numel())
+            Wr = torch.empty((Wp.shape[0], F), dtype=torch.float32, device=x.device)      # (never W0 itself: a variable)
+            Wc = Wp.contiguous()
+            H.call("dgcnn_round_bf16_f32", Wc.data_ptr(), Wr.data_ptr(), Wr.numel())
+            Wp = Wr
         return E_, Wp
 
     if bf16:

@@ -308,6 +308,8 @@ int dgcnn_edge_bn_bwd_apply_wgrad_f32(const float* V, int64_t ldv, const float* 
  * or all 9 partial products run on the bf16 matrix pipe with fp32 accumulation (fp32-class results, see
  * gemm_x3.hip).  1 = only the leading bf16 term of each operand: plain bf16 operands with fp32 accumulation (NOT fp32
  * class: the bf16 edge-MLP mode of BASELINE configs[2]; the host selects it around the EdgeConv conv0 / conv1 products).
+ * Operands that are not float4-loadable run the fp32 kernel unrounded in every mode, and the streaming kernels for N <= 4
+ * and for K <= 4 never round either: a caller that needs mode 1 there rounds its operands itself (dgcnn_round_bf16_f32).
  * Default 6, or $DGCNN_GEMM_ARITH = f32 | bf16x6 | bf16x9 | bf16x1.  Process-wide.                     */
 int dgcnn_gemm_set_arith(int mode);
 int dgcnn_gemm_get_arith(void);

@@ -23,17 +23,25 @@ def dg():
     dgcnn.reset()
     yield dgcnn
     E.EDGE_MLP_DTYPE = "f32"
+    E.DETERMINISTIC = E.DETERMINISTIC_ENV_DEFAULT
     dgcnn.reset()
 
 
 @pytest.mark.parametrize("B,N,C,k,F", [(2, 64, 3, 5, 8), (2, 128, 64, 20, 64), (1, 96, 4, 7, 128), (2, 64, 64, 10, 32),
-                                       (1, 96, 4, 10, 128), (2, 64, 3, 8, 64), (1, 50, 64, 40, 128), (1, 70, 64, 10, 128), (1, 60, 64, 8, 128)])
+                                       (1, 96, 4, 10, 128), (2, 64, 3, 8, 64), (1, 50, 64, 40, 128), (1, 70, 64, 10, 128), (1, 60, 64, 8, 128),
+                                       # conv0 widths whose products E W0 and E^T dY leave dgcnn_gemm_f32's rounding path (F = 4: the
+                                       # streaming kernels; F % 4 != 0: the scalar fp32 kernel, legal without DETERMINISTIC) -- the
+                                       # engine rounds E and W0 itself there -- and F = 12, the smallest width that stays on it
+                                       (2, 64, 3, 5, 4), (2, 64, 64, 10, 4), (2, 64, 3, 5, 6), (1, 96, 4, 7, 10), (2, 64, 3, 5, 12)])
 def test_edge_conv_bf16_forward_backward(dg, B, N, C, k, F):
     """One edge_conv block in bf16 mode against the oracle in bf16 mode (same graph): [max, mean, net] within 1e-4 and the
     gradients w.r.t. X (C % 4 == 0), W0, beta0, W1, beta1 within 2e-3 -- the bars of the fp32 block test
-    (test_gpu_parity.py::test_edge_conv_forward_backward)."""
+    (test_gpu_parity.py::test_edge_conv_forward_backward).  F % 4 != 0 runs with DETERMINISTIC off (the fixed-order column sums
+    take float4 columns) and without d(X): the mode refuses the input gradient at such widths."""
     from dgcnn import _engine as E
     E.EDGE_MLP_DTYPE = "bf16"
+    if F % 4:
+        E.DETERMINISTIC = False
     rng = np.random.default_rng(C * 10 + F)
     pts = rng.random((B, N, C), dtype=np.float32)
     P = {"conv0/weights": rng.normal(0, 0.5, (2 * C, F)).astype(np.float32),
@@ -43,7 +51,7 @@ def test_edge_conv_bf16_forward_backward(dg, B, N, C, k, F):
     c = dg.ctx()
     c.begin_step()
     c.recording = True
-    want_dx = C % 4 == 0
+    want_dx = C % 4 == 0 and F % 4 == 0
     if want_dx:
         x = c.new_buffer(B * N, C)
     else:
