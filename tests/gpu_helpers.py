@@ -46,6 +46,52 @@ class capture_layers(object):
         return False
 
 
+class capture_convs(object):
+    """Context manager: records every E.conv_bn_act call the HIP path makes (the head's layers and conv1 / shortcut of the EdgeConv
+    stack), keyed by the layer's variable scope ('MergedEdgeConv', 'FC0', 'EdgeConv1/conv1', ...):
+      x    the (R, Cin) input the layer read, on the host in float64 -- decoded from its operand planes where the producer
+           registered some (plane mode: the fp32 slice may never have been written), else the fp32 view;
+      out  the (R, Cout) tensor the call returned (behind the dropout, when the layer carries one), from the planes where the
+           call wrote no fp32 copy (f32_out=False);
+      g    the per-cloud maximum returned with it (gmax=...), or None;
+      planes_in / planes_out   whether x / out were read from planes;  kw   the call's keyword arguments."""
+
+    def __init__(self):
+        self.calls = {}
+
+    def __enter__(self):
+        from dgcnn import _engine as E
+        self._E = E
+        self._orig = orig = E.conv_bn_act
+        cap = self
+
+        def hook(x, leaf_scope, num_outputs, **kw):
+            c = E.ctx()
+            ps = c.planes.get(c.plane_key(x))
+            xin = planes_to_host(ps) if ps is not None else host(x).astype(np.float64)
+            ret = orig(x, leaf_scope, num_outputs, **kw)
+            out, g = ret if isinstance(ret, tuple) else (ret, None)
+            po = c.planes.get(c.plane_key(out)) if not kw.get("f32_out", True) else None
+            cap.calls["/".join(c.scope + [leaf_scope])] = dict(
+                x=xin, out=planes_to_host(po) if po is not None else host(out).astype(np.float64),
+                g=None if g is None else host(g).astype(np.float64), planes_in=ps is not None, planes_out=po is not None, kw=dict(kw))
+            return ret
+        E.conv_bn_act = hook
+        return self
+
+    def __exit__(self, *exc):
+        self._E.conv_bn_act = self._orig
+        return False
+
+
+# Bars other GPU modules share with the tests that set them (one definition, so that a mode's bar cannot drift between modules)
+BF16_BLOCK_OUT_TOL = 1e-4      # test_gpu_bf16_edge_mlp.py::test_edge_conv_bf16_forward_backward: [max, mean, net], rtol = atol
+BF16_BLOCK_GRAD_TOL = 2e-3     # ... its gradients: rtol, and atol = this times max(1, max |reference|)
+BF16_MODEL_LOSS_TOL = 1e-4     # test_gpu_bf16_edge_mlp.py::test_model_gradients_bf16_small: loss against the oracle in bf16 mode
+BF16_MODEL_GRAD_TOL = 4e-2     # ... every gradient tensor, relative Frobenius
+LAYER_ATOL = 1e-4              # test_gpu_bf16_edge_mlp.py::test_config2_architecture_logits_n2048_bf16: a layer on its own input
+
+
 def run_model(dg, flags, pts, params, train, labels=None):
     """trainval on `pts` with the given parameter values; -> (trainval, result list, {scope: (x_in, idx)})."""
     tv = dg.trainval(flags)

@@ -37,7 +37,8 @@ def model_forward(points, offsets, flags, params, idx_list, dropout_mask=None):
     if name not in ("dgcnn", "residual-dgcnn", "residual-dgcnn-nofc"):
         raise NotImplementedError("Unsupported MODEL_NAME: %s" % name)
     residual = name != "dgcnn"
-    tensors, layers = O.repeat_edge_conv(pts, L, int(flags.KVALUE), flags.EDGE_CONV_FILTERS, P, residual=residual, idx_list=idx_list)
+    tensors, layers = O.repeat_edge_conv(pts, L, int(flags.KVALUE), flags.EDGE_CONV_FILTERS, P, residual=residual, idx_list=idx_list,
+                                         edge_mlp_dtype=str(getattr(flags, "EDGE_MLP_DTYPE", "f32") or "f32"))
     cache = dict(layers=layers, L=L, residual=residual, off=off)
     if name == "residual-dgcnn-nofc":
         fin, cf = O.conv_bn_act(tensors[-1], P["Final/weights"], P["Final/BatchNorm/beta"], relu=True)
