@@ -13,9 +13,10 @@ namespace {
 // GEMMs of the side stream, whose workgroups hold 154 KB of LDS on every CU (A/B in the step: no measurable difference, 4.75 vs
 // 4.74 ms -- kept because it asks for less).
 constexpr int FIN_COLS = 4, FIN_LANES = 64;
-__device__ __forceinline__ bool slot_sums(const double* __restrict__ acc, int F, int nslots, int& f, double& s, double& q) {
+__device__ __forceinline__ bool slot_sums(const double* __restrict__ acc, int F, int nslots, int& f, double& s, double& q,
+                                          int colblock) {
   const int c = threadIdx.x / FIN_LANES, z = threadIdx.x % FIN_LANES;
-  f = blockIdx.x * FIN_COLS + c;
+  f = colblock * FIN_COLS + c;
   if (f >= F) return false;                    // wave-uniform
   double a = 0.0, b = 0.0;
   // four slots in flight per lane (slots z, z + 64, z + 128, z + 192 of every group of 256), added in that order
@@ -49,7 +50,7 @@ __global__ __launch_bounds__(FIN_COLS * FIN_LANES) void bn_finalize_kernel(const
                                                                            float* __restrict__ rstd) {
   int f;
   double s, q;
-  if (!slot_sums(stats, F, nslots, f, s, q)) return;
+  if (!slot_sums(stats, F, nslots, f, s, q, blockIdx.x)) return;
   const double mu = s / count;
   double var = q / count - mu * mu;   // biased variance, in double: no fp32 cancellation
   if (var < 0.0) var = 0.0;
@@ -62,7 +63,7 @@ __global__ __launch_bounds__(FIN_COLS * FIN_LANES) void bn_bwd_finalize_kernel(d
                                                                                float* __restrict__ dbeta, float dbeta_beta) {
   int f;
   double s, q;
-  if (!slot_sums(red, F, nslots, f, s, q)) return;
+  if (!slot_sums(red, F, nslots, f, s, q, blockIdx.x)) return;
   red[f] = s;
   red[F + f] = q;
   if (dbeta) dbeta[f] = (dbeta_beta != 0.f) ? (float)s + dbeta_beta * dbeta[f] : (float)s;
@@ -684,6 +685,239 @@ __global__ __launch_bounds__(256) void bn1_bwd_kernel(const float* T, int64_t R,
   if (!APPLY) k1_block_sums(lred, m, F, FVB, RP, s0, s1, red, nslots);
 }
 
+// ---- the class-dimension tail (model.py:88-101, trainval.py:39-54): last FC layer (F = 256, dropout behind it) -> Final
+// (NUM_CLASS <= 4 columns) -> softmax / loss, and the way back.  At F = 256 the k = 1 map gives one wave per row, lane l on
+// columns 4l .. 4l+3 -- the operand mapping of skinny_nn_kernel / skinny_nt_kernel (gemm.hip) -- so the Final layer's products
+// are formed in registers beside the BatchNorm passes instead of re-reading the (R, 256) tensors from HBM.  Every kernel here
+// performs, per output element and per partial sum, the operations of the launches it replaces in their order (the shared
+// helpers of common.h, bn_z, slot_sums): results are bit-identical to the separate launches.
+
+// F1 = bn1_act_kernel (dropout form) + skinny_nn_kernel<N> with statistics (+ the zero fill of [loss, accuracy]).  Launched
+// on the grid of the streaming product: rows r = 4 blockIdx.x + wave, stride 4 gridDim.x, in both.
+template <int N>
+__global__ __launch_bounds__(256) void bn1_act_class_kernel(const float* __restrict__ T, int64_t R,
+                                                            const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                            const float* __restrict__ beta, int relu,
+                                                            float* __restrict__ out, int64_t ldo,
+                                                            const uint64_t* __restrict__ drop_seed, float drop_keep,
+                                                            const float* __restrict__ W, int64_t ldw,
+                                                            float* __restrict__ C, int64_t ldc, double* __restrict__ stats,
+                                                            int nslots, float* __restrict__ scal) {
+  constexpr int F = 256;
+  __shared__ float bs[F * N + 8 * N];            // [F][N] weight, then [4 waves][2][N] for the statistics
+  float* red = bs + F * N;
+  for (int e = threadIdx.x; e < F * N; e += 256) bs[e] = W[(int64_t)(e / N) * ldw + (e % N)];
+  if (scal && blockIdx.x == 0 && threadIdx.x < 2) scal[threadIdx.x] = 0.f;
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int f = lane * 4;
+  const int64_t rstep = (int64_t)gridDim.x * 4;
+  const uint64_t dseed = *drop_seed;
+  const uint32_t dthr = dropout_threshold(drop_keep);
+  const float dscale = 1.0f / drop_keep;
+  float mu[4], rs[4], be[4];
+  Vec<4>::ld(mean + f, mu); Vec<4>::ld(rstd + f, rs); Vec<4>::ld(beta + f, be);
+  float cs[N], cq[N];
+#pragma unroll
+  for (int n = 0; n < N; ++n) { cs[n] = 0.f; cq[n] = 0.f; }
+  for (int64_t r = (int64_t)blockIdx.x * 4 + wv; r < R; r += 4 * rstep) {
+    float y[4][4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int64_t rr = r + b * rstep;
+      if (rr < R) Vec<4>::ld(T + rr * F + f, y[b]);
+    }
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int64_t rr = r + b * rstep;             // (wave-uniform: the whole wave takes the tree below)
+      if (rr < R) {
+        float z[4];
+#pragma unroll
+        for (int v = 0; v < 4; ++v) { float xh; z[v] = bn_z(y[b][v], mu[v], rs[v], be[v], relu, xh); }
+#pragma unroll
+        for (int v = 0; v < 4; ++v) z[v] = dropout_keeps(dseed, (uint64_t)(rr * F + f + v), dthr) ? z[v] * dscale : 0.f;
+        Vec<4>::st(out + rr * ldo + f, z);
+        float acc[N];
+#pragma unroll
+        for (int n = 0; n < N; ++n) acc[n] = 0.f;
+        skinny_nn_chunk<N>(acc, make_float4(z[0], z[1], z[2], z[3]), bs + f * N);
+        skinny_nn_tree<N>(acc);
+        if (lane == 0) {
+#pragma unroll
+          for (int n = 0; n < N; ++n) {
+            const float v = acc[n];
+            C[rr * ldc + n] = v;
+            cs[n] += v;
+            cq[n] += v * v;
+          }
+        }
+      }
+    }
+  }
+  if (lane == 0) {                               // the four waves' partial sums, added below in wave order (fixed)
+#pragma unroll
+    for (int n = 0; n < N; ++n) { red[wv * 2 * N + n] = cs[n]; red[wv * 2 * N + N + n] = cq[n]; }
+  }
+  __syncthreads();
+  if (threadIdx.x < 2 * N) {
+    const int which = threadIdx.x / N, n = threadIdx.x % N;
+    const float a = ((red[threadIdx.x] + red[2 * N + threadIdx.x]) + red[4 * N + threadIdx.x]) + red[6 * N + threadIdx.x];
+    atomicAdd(stats + ((int64_t)(blockIdx.x % nslots) * 2 + which) * N + n, (double)a);
+  }
+}
+
+// F2 = bn_finalize_kernel + bn_act_kreduce_kernel<1, false> (k = 1) + softmax_xent_kernel on the (rows, ncls <= 4) logits:
+// every workgroup folds the statistics slots itself (wave c = column c, slot_sums' order), workgroup 0 stores mean / rstd for
+// the backward; then row by row z = bn_z(...) -> fin, and softmax / seed / loss / accuracy from fin as softmax_xent_kernel.
+__global__ __launch_bounds__(256) void bn_softmax_xent_kernel(const float* __restrict__ Y, const double* __restrict__ stats,
+                                                              int nslots, double count, float eps,
+                                                              const float* __restrict__ beta, int relu, int64_t rows, int ncls,
+                                                              float* __restrict__ mean, float* __restrict__ rstd, float* fin,
+                                                              const int32_t* __restrict__ labels,
+                                                              const float* __restrict__ weight, float* __restrict__ softmax,
+                                                              float* __restrict__ dlogits, float* __restrict__ scal) {
+  __shared__ float sl[256], sc[256];
+  __shared__ float smu[FIN_COLS], srs[FIN_COLS];
+  {
+    int f;
+    double s, q;
+    if (slot_sums(stats, ncls, nslots, f, s, q, 0)) {
+      const double mu = s / count;
+      double var = q / count - mu * mu;
+      if (var < 0.0) var = 0.0;
+      smu[f] = (float)mu;
+      srs[f] = (float)(1.0 / sqrt(var + (double)eps));
+      if (blockIdx.x == 0) { mean[f] = smu[f]; rstd[f] = srs[f]; }
+    }
+  }
+  __syncthreads();
+  float loss = 0.f, corr = 0.f;
+  const float inv_rows = 1.0f / (float)rows;
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += (int64_t)gridDim.x * blockDim.x) {
+    float* z = fin + r * ncls;
+    for (int c = 0; c < ncls; ++c) { float xh; z[c] = bn_z(Y[r * ncls + c], smu[c], srs[c], beta[c], relu, xh); }
+    const int lab = labels ? labels[r] : -1;
+    const float w = weight ? weight[r] : 1.f;
+    softmax_xent_row(z, ncls, lab, w, inv_rows, softmax ? softmax + r * ncls : nullptr,
+                     dlogits ? dlogits + r * ncls : nullptr, loss, corr);
+  }
+  sl[threadIdx.x] = loss;
+  sc[threadIdx.x] = corr;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) { sl[threadIdx.x] += sl[threadIdx.x + s]; sc[threadIdx.x] += sc[threadIdx.x + s]; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && scal) {
+    atomicAdd(scal + 0, sl[0] * inv_rows);
+    atomicAdd(scal + 1, sc[0] * inv_rows);
+  }
+}
+
+// B1 (APPLY = false) / B2 (APPLY = true) = bn1_bwd_kernel<APPLY> of the last FC layer whose incoming gradient
+// d(out) = dT_final W_final^T (skinny_nt_kernel<NC> at beta = 0) is formed in registers instead of loaded.
+// B1 first applies the Final layer's own BatchNorm backward to its row (bn_bwd_finalize_kernel + bn_bwd_apply_kernel<1, false>:
+// every workgroup folds red_f itself, workgroup 0 adds d(beta_final)); lane 0 of the wave that owns the row stores dT_final in
+// place of the Final layer's GEMM output Tf (the weight gradient and B2 read it).  B2 reads the stored dT_final.
+template <bool APPLY, int NC>
+__global__ __launch_bounds__(256) void bn1_bwd_class_kernel(const float* T, int64_t R, const float* __restrict__ mean,
+                                                            const float* __restrict__ rstd, const float* __restrict__ beta,
+                                                            int relu, const uint64_t* __restrict__ drop_seed, float drop_keep,
+                                                            float* Tf, const float* __restrict__ mean_f,
+                                                            const float* __restrict__ rstd_f, const float* __restrict__ beta_f,
+                                                            int relu_f, const float* __restrict__ dfin,
+                                                            const double* __restrict__ red_f, int nslots_f,
+                                                            float* __restrict__ dbeta_f, float dbeta_f_beta,
+                                                            const float* __restrict__ W, int64_t ldw,
+                                                            double* __restrict__ red, float* dT, int nslots) {
+  constexpr int F = 256, FVB = 64, RP = 4;
+  extern __shared__ float lred[];   // reduce only: K1_PARK_FLOATS
+  __shared__ float sc1[FIN_COLS], sc2[FIN_COLS];
+  const uint64_t dseed = *drop_seed;
+  const uint32_t dthr = dropout_threshold(drop_keep);
+  const float dscale = 1.0f / drop_keep;
+  const K1Map m = k1_map(F, FVB, RP);              // (every thread is on: 256 threads = 4 rows x 64 quads)
+  float muf[NC], rsf[NC], bef[NC], c1f[NC], c2f[NC];
+  if (!APPLY) {
+    int f;
+    double s, q;
+    if (slot_sums(red_f, NC, nslots_f, f, s, q, 0)) {
+      const double inv_cnt = 1.0 / ((double)R * (double)1);
+      sc1[f] = (float)(s * inv_cnt);
+      sc2[f] = (float)(q * inv_cnt);
+      if (blockIdx.x == 0 && dbeta_f) dbeta_f[f] = (dbeta_f_beta != 0.f) ? (float)s + dbeta_f_beta * dbeta_f[f] : (float)s;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NC; ++k) { muf[k] = mean_f[k]; rsf[k] = rstd_f[k]; bef[k] = beta_f[k]; c1f[k] = sc1[k]; c2f[k] = sc2[k]; }
+  }
+  float w[4][NC];
+#pragma unroll
+  for (int v = 0; v < 4; ++v)
+#pragma unroll
+    for (int k = 0; k < NC; ++k) w[v][k] = W[(int64_t)(m.f + v) * ldw + k];
+  float mu[4], rs[4], be[4], c1[4] = {0, 0, 0, 0}, c2[4] = {0, 0, 0, 0};
+  float s0[4] = {0, 0, 0, 0}, s1[4] = {0, 0, 0, 0};
+  Vec<4>::ld(mean + m.f, mu); Vec<4>::ld(rstd + m.f, rs); Vec<4>::ld(beta + m.f, be);
+  if (APPLY) {
+    const double inv_cnt = 1.0 / (double)R;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      c1[v] = (float)(red[m.f + v] * inv_cnt);
+      c2[v] = (float)(red[F + m.f + v] * inv_cnt);
+    }
+  }
+  for (int64_t r = m.r0; r < R; r += 4 * m.rstep) {
+    float y[4][4], a[4][NC], g[4][NC];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int64_t rr = r + b * m.rstep;
+      if (rr < R) {
+        Vec<4>::ld(T + rr * F + m.f, y[b]);
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+          a[b][k] = Tf[rr * NC + k];
+          if (!APPLY) g[b][k] = dfin[rr * NC + k];
+        }
+      }
+    }
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int64_t rr = r + b * m.rstep;            // (wave-uniform: one wave per row)
+      if (rr < R) {
+        if (!APPLY) {                                // the Final layer's BatchNorm backward on this row: a <- dT_final[rr]
+#pragma unroll
+          for (int k = 0; k < NC; ++k) {
+            float xh;
+            const float z = bn_z(a[b][k], muf[k], rsf[k], bef[k], relu_f, xh);
+            float dz = g[b][k];
+            if (relu_f && !(z > 0.f)) dz = 0.f;
+            a[b][k] = rsf[k] * (dz - c1f[k] - xh * c2f[k]);
+          }
+          if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+            for (int k = 0; k < NC; ++k) Tf[rr * NC + k] = a[b][k];
+          }
+        }
+        float d[4], o[4];
+        skinny_nt_quad<NC>(a[b], w, d);
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          float xh;
+          const float z = bn_z(y[b][v], mu[v], rs[v], be[v], relu, xh);
+          float dz = d[v];
+          dz = dropout_keeps(dseed, (uint64_t)(rr * F + m.f + v), dthr) ? dz * dscale : 0.f;
+          if (relu && !(z > 0.f)) dz = 0.f;
+          if (APPLY) o[v] = rs[v] * (dz - c1[v] - xh * c2[v]);
+          else { s0[v] += dz; s1[v] += dz * xh; }
+        }
+        if (APPLY) Vec<4>::st(dT + rr * F + m.f, o);
+      }
+    }
+  }
+  if (!APPLY) k1_block_sums(lred, m, F, FVB, RP, s0, s1, red, nslots);
+}
+
 // Backward BN reduction of an EdgeConv conv0 WITHOUT touching the edges.  With relu and dz_e = [z_e = max_i]
 // dmax_i / ties_i + dmean_i / k  (zero where z_e <= 0), summing over the k rows of point i gives
 //   sum_m dz        = [max_i > 0] dmax_i + dmean_i npos_i / k
@@ -1018,6 +1252,82 @@ extern "C" int dgcnn_bn1_bwd_dropout_f32(const float* T, int64_t R, int F, const
   dg::launch((bn1_bwd_kernel<true>), ga.grid, dim3(256), 0, st, T, R, F, ga.FVB, ga.RP, mean, rstd, beta, relu, dout, lddo,
                      (const float*)nullptr, (int64_t)0, red, dT, (float*)nullptr, (int64_t)0, seed_dev, keep, dg::stat_slots());
   return dg::check_launch("dgcnn_bn1_bwd_dropout_f32");
+}
+
+// ---- the class-dimension tail: see bn1_act_class_kernel.  F = 256, NUM_CLASS <= 4, dense (R, F) / (R, ncls) tensors.
+static int check_class_tail(const char* what, int F, int ncls, const float* W, int64_t ldw) {
+  DG_REQUIRE(F == 256, DGCNN_EUNSUP, "%s: the last FC layer must be 256 wide (got %d): one wave per row", what, F);
+  DG_REQUIRE(ncls >= 1 && ncls <= 4, DGCNN_EUNSUP, "%s: 1 .. 4 classes (got %d)", what, ncls);
+  DG_REQUIRE(W && ldw >= ncls, DGCNN_EINVAL, "%s: bad class weight", what);
+  return DGCNN_OK;
+}
+
+extern "C" int dgcnn_bn1_act_class_f32(const float* T, int64_t R, int F, const float* mean, const float* rstd,
+                                       const float* beta, int relu, float keep, const uint64_t* seed_dev, float* out,
+                                       int64_t ldo, const float* W, int64_t ldw, int ncls, float* logits, int64_t ldc,
+                                       double* stats, float* scal, void* stream) {
+  int rc = check_bn1_drop("dgcnn_bn1_act_class_f32", T, R, F, mean, rstd, beta, relu, keep, seed_dev);
+  if (rc) return rc;
+  rc = check_class_tail("dgcnn_bn1_act_class_f32", F, ncls, W, ldw);
+  if (rc) return rc;
+  DG_REQUIRE(out && ldo % 4 == 0 && ldo >= F && a16(out), DGCNN_EINVAL, "dgcnn_bn1_act_class_f32: out must be 16-byte aligned, ld %% 4 == 0");
+  DG_REQUIRE(logits && ldc >= ncls && stats && R < (1ll << 31), DGCNN_EINVAL, "dgcnn_bn1_act_class_f32: bad logits / stats");
+  // the grid of dgcnn_gemm_f32's streaming product for these rows: same rows per wave, same writers per statistics slot
+  const unsigned g = (unsigned)dg::cap_writers(dg::cdiv(R, 4) < 2048 ? dg::cdiv(R, 4) : 2048);
+  hipStream_t st = (hipStream_t)stream;
+#define DG_ACT_CLASS(NN) dg::launch((bn1_act_class_kernel<NN>), dim3(g), dim3(256), 0, st, T, R, mean, rstd, beta, relu, out, ldo, \
+                                    seed_dev, keep, W, ldw, logits, ldc, stats, dg::stat_slots(), scal)
+  if (ncls == 1) DG_ACT_CLASS(1); else if (ncls == 2) DG_ACT_CLASS(2); else if (ncls == 3) DG_ACT_CLASS(3); else DG_ACT_CLASS(4);
+#undef DG_ACT_CLASS
+  return dg::check_launch("dgcnn_bn1_act_class_f32");
+}
+
+extern "C" int dgcnn_bn_softmax_xent_f32(const float* Y, const double* stats, double count, float eps, const float* beta,
+                                         int relu, int64_t rows, int ncls, float* mean, float* rstd, float* fin,
+                                         const int32_t* labels, const float* weight, float* softmax, float* dlogits,
+                                         float* scal, void* stream) {
+  DG_REQUIRE(Y && stats && beta && mean && rstd && fin && rows > 0 && count > 0, DGCNN_EINVAL, "dgcnn_bn_softmax_xent_f32: bad args");
+  DG_REQUIRE(ncls >= 1 && ncls <= FIN_COLS, DGCNN_EUNSUP, "dgcnn_bn_softmax_xent_f32: 1 .. %d classes (got %d)", FIN_COLS, ncls);
+  DG_REQUIRE(relu == 0 || relu == 1, DGCNN_EINVAL, "dgcnn_bn_softmax_xent_f32: relu must be 0 or 1 (got %d)", relu);
+  DG_REQUIRE(!dlogits || labels, DGCNN_EINVAL, "dgcnn_bn_softmax_xent_f32: dlogits needs labels");
+  int64_t g = dg::cdiv(rows, 256);                  // dgcnn_softmax_xent_f32's grid
+  if (g > 1024) g = 1024;
+  dg::launch(bn_softmax_xent_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, Y, stats, dg::stat_slots(), count, eps,
+             beta, relu, rows, ncls, mean, rstd, fin, labels, weight, softmax, dlogits, scal);
+  return dg::check_launch("dgcnn_bn_softmax_xent_f32");
+}
+
+extern "C" int dgcnn_bn1_bwd_class_f32(const float* T, int64_t R, int F, const float* mean, const float* rstd,
+                                       const float* beta, int relu, float keep, const uint64_t* seed_dev, float* Tf, int ncls,
+                                       const float* mean_f, const float* rstd_f, const float* beta_f, int relu_f,
+                                       const float* dfin, double* red_f, float* dbeta_f, float dbeta_f_beta, const float* W,
+                                       int64_t ldw, double* red, float* dT, float* dbeta, float dbeta_beta, int phases, void* stream) {
+  DG_REQUIRE(phases >= 1 && phases <= 3, DGCNN_EINVAL, "dgcnn_bn1_bwd_class_f32: phases must be 1 (sums), 2 (finalize + dT) or 3 (got %d)", phases);
+  int rc = check_bn1_drop("dgcnn_bn1_bwd_class_f32", T, R, F, mean, rstd, beta, relu, keep, seed_dev);
+  if (rc) return rc;
+  rc = check_class_tail("dgcnn_bn1_bwd_class_f32", F, ncls, W, ldw);
+  if (rc) return rc;
+  DG_REQUIRE(Tf && mean_f && rstd_f && beta_f && dfin && red_f && red && dT && a16(dT) && (relu_f == 0 || relu_f == 1), DGCNN_EINVAL,
+             "dgcnn_bn1_bwd_class_f32: bad args");
+  hipStream_t st = (hipStream_t)stream;
+  const K1Grid gr = k1_grid(R, F, 256);
+  const K1Grid ga = k1_grid(R, F, 4096);
+  const size_t sh1 = sizeof(float) * K1_PARK_FLOATS;
+  const int ns = dg::stat_slots();
+#define DG_BWD_CLASS(NC)                                                                                                         \
+  do {                                                                                                                           \
+    if (phases & 1)                                                                                                              \
+      dg::launch((bn1_bwd_class_kernel<false, NC>), gr.grid, dim3(256), sh1, st, T, R, mean, rstd, beta, relu, seed_dev, keep,    \
+                 Tf, mean_f, rstd_f, beta_f, relu_f, dfin, red_f, ns, dbeta_f, dbeta_f_beta, W, ldw, red, (float*)nullptr, ns);   \
+    if (!(phases & 2)) break;                                                                                                    \
+    dg::launch(bn_bwd_finalize_kernel, dim3((unsigned)dg::cdiv(F, FIN_COLS)), dim3(FIN_COLS * FIN_LANES), 0, st, red, F, ns,     \
+               dbeta, dbeta_beta);                                                                                               \
+    dg::launch((bn1_bwd_class_kernel<true, NC>), ga.grid, dim3(256), 0, st, T, R, mean, rstd, beta, relu, seed_dev, keep, Tf,     \
+               mean_f, rstd_f, beta_f, relu_f, dfin, red_f, ns, (float*)nullptr, 0.f, W, ldw, red, dT, ns);                       \
+  } while (0)
+  if (ncls == 1) DG_BWD_CLASS(1); else if (ncls == 2) DG_BWD_CLASS(2); else if (ncls == 3) DG_BWD_CLASS(3); else DG_BWD_CLASS(4);
+#undef DG_BWD_CLASS
+  return dg::check_launch("dgcnn_bn1_bwd_class_f32");
 }
 
 namespace dg {

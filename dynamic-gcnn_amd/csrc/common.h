@@ -106,3 +106,51 @@ __device__ __forceinline__ float round_bf16_rne(float v) {
   const unsigned r = (u + 0x7fffu + ((u >> 16) & 1u)) & 0xffff0000u;
   return __uint_as_float(((u & 0x7fffffffu) > 0x7f800000u) ? ((u | 0x00400000u) & 0xffff0000u) : r);
 }
+
+// ---- the class dimension (Final layer, NUM_CLASS <= 4): the arithmetic of the streaming products of gemm.hip, shared with the
+// BatchNorm kernels of bn.hip that form the same products in registers -- one definition each, so that a fused kernel performs,
+// per output element, the operations of the launches it replaces in their order.
+// NN: one float4 chunk of k of a row's N dots (b = the [K][N] weight in LDS at row k4), then the wave's fixed tree.
+template <int N>
+__device__ __forceinline__ void skinny_nn_chunk(float (&acc)[N], const float4 v, const float* b) {
+#pragma unroll
+  for (int n = 0; n < N; ++n) acc[n] += v.x * b[n] + v.y * b[N + n] + v.z * b[2 * N + n] + v.w * b[3 * N + n];
+}
+template <int N>
+__device__ __forceinline__ void skinny_nn_tree(float (&acc)[N]) {
+#pragma unroll
+  for (int n = 0; n < N; ++n)
+    for (int d = 32; d > 0; d >>= 1) acc[n] += __shfl_down(acc[n], d, 64);
+}
+// NT at beta = 0: o[q] = sum over k (ascending, from 0.f) of a[k] * w[q][k] -- four output columns of one row.
+template <int K>
+__device__ __forceinline__ void skinny_nt_quad(const float (&a)[K], const float (&w)[4][K], float (&o)[4]) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    o[q] = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) o[q] += a[k] * w[q][k];
+  }
+}
+
+// softmax / cross-entropy / accuracy of ONE row of logits z[ncls] (trainval.py:39-52): probabilities, the seed of the backward
+// pass and the row's terms of the two means.  Shared by softmax_xent_kernel (misc.hip) and its BatchNorm-fused form (bn.hip).
+__device__ __forceinline__ void softmax_xent_row(const float* z, int ncls, int lab, float w, float inv_rows, float* softmax,
+                                                 float* dlogits, float& loss, float& corr) {
+  float mx = z[0];
+  int am = 0;
+  for (int c = 1; c < ncls; ++c)
+    if (z[c] > mx) { mx = z[c]; am = c; }
+  float se = 0.f;
+  for (int c = 0; c < ncls; ++c) se += expf(z[c] - mx);
+  const float inv = 1.0f / se;
+  for (int c = 0; c < ncls; ++c) {
+    const float p = expf(z[c] - mx) * inv;
+    if (softmax) softmax[c] = p;
+    if (dlogits) dlogits[c] = (p - (c == lab ? 1.f : 0.f)) * w * inv_rows;
+  }
+  if (lab >= 0) {
+    loss += (logf(se) - (z[lab] - mx)) * w;
+    corr += (am == lab) ? 1.f : 0.f;
+  }
+}

@@ -429,14 +429,9 @@ __global__ __launch_bounds__(256) void skinny_nn_kernel(const float* __restrict_
     for (int n = 0; n < N; ++n) acc[n] = 0.f;
     const float* a = A + (int64_t)r * lda;
     for (int k4 = lane * 4; k4 < K; k4 += 256) {
-      const float4 v = ld4(a + k4);
-      const float* b = bs + k4 * N;
-#pragma unroll
-      for (int n = 0; n < N; ++n) acc[n] += v.x * b[n] + v.y * b[N + n] + v.z * b[2 * N + n] + v.w * b[3 * N + n];
+      skinny_nn_chunk<N>(acc, ld4(a + k4), bs + k4 * N);
     }
-#pragma unroll
-    for (int n = 0; n < N; ++n)
-      for (int d = 32; d > 0; d >>= 1) acc[n] += __shfl_down(acc[n], d, 64);
+    skinny_nn_tree<N>(acc);
     if (lane == 0) {
 #pragma unroll
       for (int n = 0; n < N; ++n) {
@@ -539,11 +534,12 @@ __global__ __launch_bounds__(256) void skinny_nt_kernel(const float* __restrict_
     float a[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) a[k] = A[(int64_t)r * lda + k];
-    float o[4] = {0.f, 0.f, 0.f, 0.f};
+    float w[4][K], o[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q)
 #pragma unroll
-      for (int k = 0; k < K; ++k) o[q] += a[k] * B[(int64_t)(c4 + q) * ldb + k];
+      for (int k = 0; k < K; ++k) w[q][k] = B[(int64_t)(c4 + q) * ldb + k];
+    skinny_nt_quad<K>(a, w, o);
     float4* dst = reinterpret_cast<float4*>(C + (int64_t)r * ldc + c4);
     if (beta != 0.f) {
       const float4 old = *dst;

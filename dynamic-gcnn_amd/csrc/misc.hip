@@ -472,25 +472,10 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const float* __restri
   float loss = 0.f, corr = 0.f;
   const float inv_rows = 1.0f / (float)rows;
   GRID_STRIDE(r, rows) {
-    const float* z = logits + r * ncls;
-    float mx = z[0];
-    int am = 0;
-    for (int c = 1; c < ncls; ++c)
-      if (z[c] > mx) { mx = z[c]; am = c; }
-    float se = 0.f;
-    for (int c = 0; c < ncls; ++c) se += expf(z[c] - mx);
-    const float inv = 1.0f / se;
     const int lab = labels ? labels[r] : -1;
     const float w = weight ? weight[r] : 1.f;
-    for (int c = 0; c < ncls; ++c) {
-      const float p = expf(z[c] - mx) * inv;
-      if (softmax) softmax[r * ncls + c] = p;
-      if (dlogits) dlogits[r * ncls + c] = (p - (c == lab ? 1.f : 0.f)) * w * inv_rows;
-    }
-    if (lab >= 0) {
-      loss += (logf(se) - (z[lab] - mx)) * w;
-      corr += (am == lab) ? 1.f : 0.f;
-    }
+    softmax_xent_row(logits + r * ncls, ncls, lab, w, inv_rows, softmax ? softmax + r * ncls : nullptr,
+                     dlogits ? dlogits + r * ncls : nullptr, loss, corr);
   }
   sl[threadIdx.x] = loss;
   sc[threadIdx.x] = corr;

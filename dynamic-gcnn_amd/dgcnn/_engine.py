@@ -40,6 +40,10 @@ WGRAD_SIDE_STREAM = os.environ.get("DGCNN_SIDE_STREAM", "1") != "0"   # weight-g
 # Fusions with a separate-pass twin that the tests compare them against (module constants, not run-time switches):
 EDGE_BWD_FUSED_L0 = True   # input layer (C <= 4, no input gradient): conv0's whole backward in one pass
 FUSE_DROPOUT = True        # tf.nn.dropout inside the last FC layer's BatchNorm passes
+# the class-dimension tail (last FC layer -> Final -> loss) in 8 launches instead of 15: the Final layer's two class products are
+# formed inside the FC layer's BatchNorm passes, the launches on the (R, NUM_CLASS) logits fold into their neighbours
+# (csrc/bn.hip: bn1_act_class_kernel ...).  Bit-identical to the separate launches; DGCNN_FUSE_CLASS_TAIL=0 selects those.
+FUSE_CLASS_TAIL = os.environ.get("DGCNN_FUSE_CLASS_TAIL", "1") != "0"
 BF16_FUSED_BWD = True      # bf16 edge-MLP: the layer's backward in one pass over the edges (tests switch it off to compare)
 EDGE_BWD_REDUCE_POINTS = True   # BN backward sums of conv0 from per-point data (False: a pass over the edges)
 SIDE_STREAM_MIN_ROWS = 16384   # below this many points the side stream is not used
@@ -111,6 +115,10 @@ class Context(object):
         self.wprep = {}                  # weight-only work of the step, issued ahead on the side stream: key -> tensor / PlaneSet
         self.wprep_event = None          # True while the main stream has not yet been made to wait for it (prepared())
         self.head_grads_hook = None      # called by the backward when every head gradient is final (trainval: bucketed all-reduce)
+        # the class-dimension tail (FUSE_CLASS_TAIL): launches held back until their consumer is known
+        self.dense_loss_follows = False  # set by trainval around model.build: the dense softmax_loss consumes the logits next
+        self.class_tail = None           # last FC layer: its BatchNorm + dropout pass, waiting for the Final layer's weight
+        self.loss_tail = None            # Final layer: its BatchNorm finalize + activation, waiting for softmax_loss
 
     # ---- device / scratch -------------------------------------------------------------
     @property
@@ -315,6 +323,7 @@ class Context(object):
         self.wprep = {}
         self.wprep_event = None
         self._slot_stack = []
+        self.class_tail = self.loss_tail = None
         if not DETERMINISTIC and H.STAT_SLOTS != 32:
             H.set_stat_slots(32)
         elif DETERMINISTIC and H.STAT_SLOTS < 256:
@@ -438,7 +447,15 @@ class Context(object):
                 return slot[0], 0.0
         return self.grad(v), 1.0
 
+    def first_touch(self, v):
+        """True when `v` IS a whole tracked root whose gradient nobody has touched yet (what grad_w answers with beta = 0.0)."""
+        if not self.recording:
+            return False
+        ptr = v.data_ptr()
+        return any(root.data_ptr() == ptr and tuple(root.shape) == tuple(v.shape) and slot[0] is None for root, slot in self.roots)
+
     def backward(self):
+        flush_class_tail(self)
         self.join_side()                 # side work issued during the forward (transposed adjacency)
         for fn in reversed(self.tape):
             fn()
@@ -821,12 +838,44 @@ def bn_finalize(stats, F, count):
     return mr[0], mr[1]
 
 
+def _launch_bn1_act_dropout(h):
+    """The last FC layer's BatchNorm + activation + dropout pass on its own (h: the record conv_bn_act holds it back in)."""
+    H.call("dgcnn_bn1_act_dropout_f32", h["T"].data_ptr(), h["R"], h["F"], h["mean"].data_ptr(), h["rstd"].data_ptr(),
+           h["beta"].data_ptr(), int(h["relu"]), float(h["keep"]), h["seed"].data_ptr(), h["out"].data_ptr(), H.ld2(h["out"]),
+           tag="bn_act_kreduce_kernel<k=1>", work=4.0 * h["R"] * h["F"] * 2)
+
+
+def _launch_loss_tail(lt):
+    """The Final layer's BatchNorm finalize + activation on their own (lt: the record conv_bn_act holds them back in)."""
+    prev = H.STAT_SLOTS
+    if lt["nslots"] != prev:
+        H.set_stat_slots(lt["nslots"])
+    try:
+        H.call("dgcnn_bn_finalize_f32", lt["st"].data_ptr(), lt["F"], float(lt["R"]), BN_EPS, lt["mean"].data_ptr(), lt["rstd"].data_ptr())
+    finally:
+        if H.STAT_SLOTS != prev:
+            H.set_stat_slots(prev)
+    H.call("dgcnn_bn_act_kreduce_f32", lt["T"].data_ptr(), lt["R"], 1, lt["F"], lt["mean"].data_ptr(), lt["rstd"].data_ptr(),
+           lt["beta"].data_ptr(), int(lt["relu"]), lt["out"].data_ptr(), H.ld2(lt["out"]), 0, 0, 0, 0, 0,
+           tag="bn_act_kreduce_kernel<k=1>", work=4.0 * lt["R"] * lt["F"] * 2)
+
+
+def flush_class_tail(c):
+    """Issue whatever the class-dimension tail still holds back (its consumer did not come)."""
+    tail, c.class_tail = c.class_tail, None
+    if tail is not None:
+        _launch_bn1_act_dropout(tail)
+    lt, c.loss_tail = c.loss_tail, None
+    if lt is not None:
+        _launch_loss_tail(lt)
+
+
 # ----------------------------------------------------------------------------------------------
 # slim.conv2d(1x1, no bias) + slim.batch_norm + activation on per-point tensors (k = 1)
 # dgcnn/ops.py:62-70,125-133,153-160 ; dgcnn/model.py:46-53,65-72,94-101
 # ----------------------------------------------------------------------------------------------
 def conv_bn_act(x, leaf_scope, num_outputs, relu=True, out=None, out2=None, gbias=None, rpg=0, w_rows=None, arith=None,
-                plane_out=None, f32_out=True, gmax=None, drop_keep=None, seg=None):
+                plane_out=None, f32_out=True, gmax=None, drop_keep=None, seg=None, class_tail=None):
     """x: (R,Cin) view.  Variables `<scope>/weights` [Cin(+extra), Cout], `<scope>/BatchNorm/beta`.
     w_rows: (lo, hi) row range of the weight that multiplies x (FC0 with the folded global feature).
     Returns the (R,Cout) output (a fresh tracked buffer unless `out` is given).
@@ -841,9 +890,18 @@ def conv_bn_act(x, leaf_scope, num_outputs, relu=True, out=None, out2=None, gbia
     cloud goes through the segmented kernels (csrc/seg.hip): gbias is (nseg, Cout) and is addressed through the row -> cloud map
     (rpg is ignored), its gradient is the per-cloud column sum, gmax (any value but None) is the max-pool over each cloud's own
     rows -- always the separate pass over the GEMM output, never the epilogue.  The plane mode is NOT packed: a packed tower
-    runs the fp32-class GEMMs (bf16-split / fp32 MFMA) even when HEAD_PLANES is set."""
+    runs the fp32-class GEMMs (bf16-split / fp32 MFMA) even when HEAD_PLANES is set.
+    class_tail: NUM_CLASS of the Final layer that consumes this output NEXT (the last FC layer; FUSE_CLASS_TAIL): where the
+    shapes and modes allow, this layer's BatchNorm + dropout pass is held back and runs with the Final layer's product in it."""
     c = ctx()
     R, Cin = x.shape
+    tail, c.class_tail = c.class_tail, None
+    if tail is not None and not (tail["out"].data_ptr() == x.data_ptr() and tuple(tail["out"].shape) == tuple(x.shape) and
+                                 num_outputs == tail["ncls"] and out2 is None and gbias is None and w_rows is None and
+                                 arith is None and gmax is None and drop_keep is None and seg is None and plane_out is None and
+                                 x.is_contiguous() and (out is None or out.is_contiguous())):
+        _launch_bn1_act_dropout(tail)           # somebody else's input: the plain pass
+        tail = None
     if seg is not None and seg.rows != R:
         raise ValueError("offsets end at %d, the tower has %d rows" % (seg.rows, R))
     bpc = per_cloud(seg)
@@ -857,6 +915,10 @@ def conv_bn_act(x, leaf_scope, num_outputs, relu=True, out=None, out2=None, gbia
             Wx = W[w_rows[0]:w_rows[1]]
         bname, beta = c.get_variable("BatchNorm/beta", (num_outputs,))
     F = num_outputs
+    if tail is not None:
+        if H.load().dgcnn_gemm_stat_writers(0, R, F, Cin, x.data_ptr(), H.ld2(x), Wx.data_ptr(), H.ld2(Wx)) != 0 or planes_ok(R, Cin, F):
+            _launch_bn1_act_dropout(tail)       # (not the streaming class product)
+            tail = None
     if bpc:
         return _conv_bn_act_per_cloud(c, x, Wx, beta, F, relu, out, out2, gbias, rgrp, arith, gmax, drop_keep, seg, wname, w_rows, bname)
     T = torch.empty((R, F), dtype=torch.float32, device=x.device)
@@ -877,7 +939,23 @@ def conv_bn_act(x, leaf_scope, num_outputs, relu=True, out=None, out2=None, gbia
             keys = c.stats_raw(seg.nseg * F)                                   # zeroed uint64[nseg][F], filled by the pass below
     elif gmax is not None and gmax[1] % 256 == 0 and gmax[0] * gmax[1] == R and F > 4:
         keys = c.stats_raw(gmax[0] * F)                                    # zeroed uint64[B][F]
-    if use_pl:
+    if tail is not None:
+        # F1: the held-back BatchNorm + dropout pass of the FC layer writes x AND forms T = x W with its column statistics, on the
+        # streaming product's grid; F2 (softmax_loss) folds the statistics, applies this layer's BatchNorm + ReLU and the loss
+        scal = torch.empty(2, dtype=torch.float32, device=x.device)           # [loss, accuracy]: zeroed by F1
+        H.call("dgcnn_bn1_act_class_f32", tail["T"].data_ptr(), R, Cin, tail["mean"].data_ptr(), tail["rstd"].data_ptr(),
+               tail["beta"].data_ptr(), int(tail["relu"]), float(tail["keep"]), tail["seed"].data_ptr(), x.data_ptr(), H.ld2(x),
+               Wx.data_ptr(), H.ld2(Wx), F, T.data_ptr(), F, st.data_ptr(), scal.data_ptr(),
+               tag="bn1_act_class_kernel", work=4.0 * R * Cin * 2)
+        mr = torch.empty((2, F), dtype=torch.float32, device=x.device)
+        mean, rstd = mr[0], mr[1]
+        if out is None:
+            out = c.new_buffer(R, F)
+        c.loss_tail = dict(T=T, st=st, F=F, R=R, beta=beta, relu=relu, mean=mean, rstd=rstd, out=out, scal=scal,
+                           nslots=H.STAT_SLOTS)
+        c.pop_slots()
+        fuse_drop = False
+    elif use_pl:
         c.ensure_plane_scales(R)
         xp = c.planes_of(x)                                                # (R, Cin) activations
         wt = prepared(("wT", Wx.data_ptr()))                               # (F rows, Cin channels) = W^T
@@ -893,18 +971,28 @@ def conv_bn_act(x, leaf_scope, num_outputs, relu=True, out=None, out2=None, gbia
                        keys.data_ptr(), tag="colmax_seg_kernel", work=4.0 * R * F)
         else:
             gemm(x, Wx, T, gbias=gbias, rpg=rpg, stats=st, arith=arith, colmax=keys, colmax_rpg=0 if keys is None else gmax[1])
-    mean, rstd = bn_finalize(st, F, R)
-    c.pop_slots()
-    if out is None:
-        out = c.new_buffer(R, F)
-    fuse_drop = (drop_keep is not None and FUSE_DROPOUT and not use_pl and F % 4 == 0 and out2 is None and
-                 gmax is None and plane_out is None)
-    if fuse_drop:
+    if tail is None:
+        mean, rstd = bn_finalize(st, F, R)
+        c.pop_slots()
+        if out is None:
+            out = c.new_buffer(R, F)
+        fuse_drop = (drop_keep is not None and FUSE_DROPOUT and not use_pl and F % 4 == 0 and out2 is None and
+                     gmax is None and plane_out is None)
+    held = None
+    if tail is not None:
+        pass                                    # (this layer's BatchNorm + ReLU run with the loss: softmax_loss, F2)
+    elif fuse_drop:
         if c.seed_dev is None:
             c.advance_seed()
         seed = c.seed_dev                       # device-resident: the backward regenerates the mask from the same value
-        H.call("dgcnn_bn1_act_dropout_f32", T.data_ptr(), R, F, mean.data_ptr(), rstd.data_ptr(), beta.data_ptr(), int(relu),
-               float(drop_keep), seed.data_ptr(), out.data_ptr(), H.ld2(out), tag="bn_act_kreduce_kernel<k=1>", work=4.0 * R * F * 2)
+        held = dict(T=T, R=R, F=F, mean=mean, rstd=rstd, beta=beta, relu=relu, keep=drop_keep, seed=seed, out=out,
+                    ncls=class_tail, bwd=None)
+        if (class_tail is not None and FUSE_CLASS_TAIL and DETERMINISTIC and c.dense_loss_follows and c.recording and
+                seg is None and gbias is None and w_rows is None and F == 256 and 1 <= int(class_tail) <= 4 and
+                out.is_contiguous()):
+            c.class_tail = held                 # runs inside the Final layer's call (F1), or as the plain pass if that is not next
+        else:
+            _launch_bn1_act_dropout(held)
     elif plane_out is not None:
         H.call("dgcnn_bn_act_planes_f32", T.data_ptr(), F, R, F, mean.data_ptr(), rstd.data_ptr(), beta.data_ptr(), int(relu),
                plane_out.fmt, H._p(plane_out.scale), plane_out.ptr(), plane_out.plane_stride, plane_out.ra,
@@ -925,6 +1013,29 @@ def conv_bn_act(x, leaf_scope, num_outputs, relu=True, out=None, out2=None, gbia
                 c.pop_slots()
 
         def bwd_body():
+            tb = held["bwd"] if held is not None else None
+            if tb is not None:
+                # B1, finalize, B2: d(out) = dT_final W_final^T is formed in registers (never stored); B1 also applies the Final
+                # layer's BatchNorm backward (dT_final in place of its GEMM output, d(beta_final))
+                red = c.stats(F)
+                args = (T.data_ptr(), R, F, mean.data_ptr(), rstd.data_ptr(), beta.data_ptr(), int(relu), float(drop_keep),
+                        seed.data_ptr(), tb["Tf"].data_ptr(), tb["ncls"], tb["mean"].data_ptr(), tb["rstd"].data_ptr(),
+                        tb["beta"].data_ptr(), int(tb["relu"]), tb["dfin"].data_ptr(), tb["red"].data_ptr(), tb["dbeta"].data_ptr(),
+                        1.0, tb["W"].data_ptr(), H.ld2(tb["W"]), red.data_ptr(), T.data_ptr(), c.var_grads[bname].data_ptr(), 1.0)
+                H.call("dgcnn_bn1_bwd_class_f32", *args, 1, tag="bn1_bwd_class_kernel", work=4.0 * R * F)
+                # the Final layer's weight gradient starts as soon as B1 has left dT_final: on the side stream, under the two
+                # bandwidth-bound launches below -- not next to this layer's data-gradient GEMM
+                with c.off_critical_path(rows=R):
+                    gemm(out, tb["Tf"], tb["dWx"], transA=True, beta=1.0)
+                H.call("dgcnn_bn1_bwd_class_f32", *args, 2, tag="bn1_bwd_class_kernel", work=4.0 * R * F * 2)
+                held["bwd"] = None
+                dx, bx = c.grad_w(x)
+                if dx is not None:
+                    gemm(T, Wx, dx, transB=True, beta=bx, arith=arith)
+                with c.off_critical_path(rows=R):
+                    gemm(x, T, c.var_grads[wname] if w_rows is None else c.var_grads[wname][w_rows[0]:w_rows[1]], transA=True,
+                         beta=1.0, arith=arith)
+                return
             dout = c.grad(out)
             if dout is None:
                 return
@@ -995,6 +1106,11 @@ def conv_bn_act(x, leaf_scope, num_outputs, relu=True, out=None, out2=None, gbia
             nsrc = 1 if d2 is None else 2                                  # k = 1: dz = dout + d2 (the kernels' dmax + dmean / k)
             bn_bwd_reduce(T, R, 1, F, mean, rstd, beta, relu, dout, d2, None, None, red,
                           tag="bn_bwd_reduce_kernel<k=1>", work=4.0 * R * F * (1 + nsrc))
+            if tail is not None and FUSE_CLASS_TAIL and d2 is None and dgb is None and dout.is_contiguous() and c.first_touch(x):
+                # the rest of this layer's backward runs inside the FC layer's passes (B1 / B2 above)
+                tail["bwd"] = dict(Tf=T, ncls=F, mean=mean, rstd=rstd, beta=beta, relu=relu, dfin=dout, red=red,
+                                   dbeta=c.var_grads[bname], W=Wx, dWx=dWx)
+                return
             H.call("dgcnn_bn_bwd_apply_f32", T.data_ptr(), R, 1, F, mean.data_ptr(), rstd.data_ptr(), beta.data_ptr(),
                    int(relu), dout.data_ptr(), H.ld2(dout), H._p(d2), 0 if d2 is None else H.ld2(d2), 0, 0, 0, red.data_ptr(),
                    T.data_ptr(), 0, 0, c.var_grads[bname].data_ptr(), 1.0, tag="bn_bwd_apply_kernel<k=1>", work=4.0 * R * F * (2 + nsrc))
@@ -1799,6 +1915,14 @@ def softmax_loss(logits2d, labels, weight, want_grad, seg=None, per_cloud=False)
     R, ncls = logits2d.shape
     assert logits2d.is_contiguous()
     dev = logits2d.device
+    lt = c.loss_tail
+    if lt is not None and not (lt["out"].data_ptr() == logits2d.data_ptr() and tuple(lt["out"].shape) == (R, ncls) and
+                               not (per_cloud and seg is not None)):
+        lt = None
+    if lt is None:
+        flush_class_tail(c)                     # (not the held-back logits: whatever is pending runs on its own)
+    else:
+        c.loss_tail = None
     sm = torch.empty((R, ncls), dtype=torch.float32, device=dev)
     dl = None
     if want_grad:
@@ -1821,6 +1945,20 @@ def softmax_loss(logits2d, labels, weight, want_grad, seg=None, per_cloud=False)
         H.call("dgcnn_seg_softmax_xent_f32", logits2d.data_ptr(), H._p(labels), H._p(weight), R, ncls, seg.device(dev).data_ptr(),
                seg.nseg, sm.data_ptr(), H._p(dl), H._p(cs), scal.data_ptr(), H._p(ws), 0 if ws is None else ws.numel())
         return sm, scal, cs
+    if lt is not None:
+        # F2: folds the Final layer's statistics slots (mean / rstd for the backward), applies its BatchNorm + ReLU -> logits2d,
+        # then softmax / seed / loss / accuracy as below; [loss, accuracy] were zeroed by F1
+        prev = H.STAT_SLOTS
+        if lt["nslots"] != prev:
+            H.set_stat_slots(lt["nslots"])
+        try:
+            H.call("dgcnn_bn_softmax_xent_f32", lt["T"].data_ptr(), lt["st"].data_ptr(), float(R), BN_EPS, lt["beta"].data_ptr(),
+                   int(lt["relu"]), R, ncls, lt["mean"].data_ptr(), lt["rstd"].data_ptr(), logits2d.data_ptr(), H._p(labels),
+                   H._p(weight), sm.data_ptr(), H._p(dl), lt["scal"].data_ptr(), tag="bn_softmax_xent_kernel", work=4.0 * R * ncls * 4)
+        finally:
+            if H.STAT_SLOTS != prev:
+                H.set_stat_slots(prev)
+        return sm, lt["scal"]
     scal = H.zeros(2, torch.float32, dev)      # (its own tensor: the caller reads it after later towers' begin_step)
     H.call("dgcnn_softmax_xent_f32", logits2d.data_ptr(), H._p(labels), H._p(weight), R, ncls, sm.data_ptr(),
            H._p(dl), scal.data_ptr())

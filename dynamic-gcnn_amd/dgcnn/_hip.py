@@ -69,6 +69,12 @@ PROTOTYPES = {
                                           c_vp, c_sz, c_vp],
     "dgcnn_bn1_act_dropout_f32": [c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_int, c_f32, c_vp, c_vp, c_i64, c_vp],
     "dgcnn_bn1_bwd_dropout_f32": [c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_int, c_f32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_f32, c_vp],
+    "dgcnn_bn1_act_class_f32": [c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_int, c_f32, c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_i64,
+                                c_vp, c_vp, c_vp],
+    "dgcnn_bn_softmax_xent_f32": [c_vp, c_vp, c_f64, c_f32, c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                  c_vp],
+    "dgcnn_bn1_bwd_class_f32": [c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_int, c_f32, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_vp,
+                                c_vp, c_vp, c_f32, c_vp, c_i64, c_vp, c_vp, c_vp, c_f32, c_int, c_vp],
     "dgcnn_set_stat_slots": [c_int],
     "dgcnn_get_stat_slots": [],
     "dgcnn_gemm_set_arith": [c_int],

@@ -168,8 +168,9 @@ def build(point_cloud, flags, offsets=None):
                             plane_out=c.new_planes(R, fcf[0], "act"), f32_out=False)
     else:
         net = E.conv_bn_act(big, "FC0", fcf[0], relu=True, gbias=gb, rpg=N, w_rows=(1024, 1024 + ctot, 1024 + ctot),
-                            drop_keep=keep if num_fc == 1 else None, seg=seg)
+                            drop_keep=keep if num_fc == 1 else None, seg=seg, class_tail=num_class if num_fc == 1 else None)
     for i in range(1, num_fc):                                     # ops.py:151-160
-        net = E.conv_bn_act(net, "FC%d" % i, fcf[i], relu=True, drop_keep=keep if i == num_fc - 1 else None, seg=seg)
+        net = E.conv_bn_act(net, "FC%d" % i, fcf[i], relu=True, drop_keep=keep if i == num_fc - 1 else None, seg=seg,
+                            class_tail=num_class if i == num_fc - 1 else None)      # (the Final layer below consumes it next)
     fin = E.conv_bn_act(net, "Final", num_class, relu=True, seg=seg)        # model.py:94-101 (BN + ReLU on the logits)
     return fin.view(B, N, num_class)                                # model.py:104 squeeze

@@ -267,7 +267,12 @@ class trainval(object):
         if seg is not None:
             logits = model.build(pts, self._flags, offsets=seg)      # (1, R, ncls)
         else:
-            logits = model.build(pts, self._flags)                   # trainval.py:38
+            # (the dense softmax_loss below consumes the logits next: the class-dimension tail may hold launches back for it)
+            c.dense_loss_follows = bool(train) and not self._loss_per_cloud()
+            try:
+                logits = model.build(pts, self._flags)               # trainval.py:38
+            finally:
+                c.dense_loss_follows = False
         B, N, ncls = logits.shape
         lpc_seg = None
         if self._loss_per_cloud():
@@ -312,7 +317,7 @@ class trainval(object):
         hooked = c.head_grads_hook is not None
         key = (kind, tuple(pts.shape), bool(train), lab is not None, wgt is not None, float(E.DROPOUT_KEEP), H.gemm_arith(),
                E.WGRAD_SIDE_STREAM, E.HEAD_PLANES, E.DETERMINISTIC, E.EDGE_MLP_DTYPE, hooked, self._loss_per_cloud(),
-               int(torch.cuda.current_stream().cuda_stream))     # (a plan bakes in the streams that were current at record time)
+               E.FUSE_CLASS_TAIL, int(torch.cuda.current_stream().cuda_stream))     # (a plan bakes in the streams that were current at record time)
         ent = self._graphs.get(key)
         if ent is not None:
             # DETERMINISTIC mode grows the slot count (and with it the statistics arena) when a larger cloud arrives: a graph

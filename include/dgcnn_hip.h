@@ -284,6 +284,30 @@ int dgcnn_bn1_bwd_dropout_f32(const float* T, int64_t R, int F, const float* mea
                               int relu, float keep, const uint64_t* seed_dev, const float* dout, int64_t lddo, double* red,
                               float* dT, float* dbeta, float dbeta_beta, void* stream);
 
+/* The class-dimension tail (model.py:88-101, trainval.py:39-54): last FC layer (F = 256, dropout behind it) -> Final layer
+ * (ncls <= 4 columns, W: its [F][ncls] weight, leading dim ldw) -> softmax / loss, with the Final layer's two class products
+ * formed in registers beside the BatchNorm passes.  Each call computes, bit for bit, what the sequence it replaces computes:
+ *   dgcnn_bn1_act_class_f32   = dgcnn_bn1_act_dropout_f32 + dgcnn_gemm_f32 (logits = out W, beta 0, with column statistics, on
+ *                               that product's grid) + the zero fill of scal = [loss, accuracy] (may be NULL);
+ *   dgcnn_bn_softmax_xent_f32 = dgcnn_bn_finalize_f32 (mean, rstd are still written) + dgcnn_bn_act_kreduce_f32 (k = 1, -> fin)
+ *                               + dgcnn_softmax_xent_f32 on fin; scal must already be zero;
+ *   dgcnn_bn1_bwd_class_f32   = dgcnn_bn_bwd_apply_f32 (k = 1) on the Final layer (red_f: slot 0 filled by
+ *                               dgcnn_bn_bwd_reduce_det_f32; dT_final replaces Tf, dbeta_f as there) + dgcnn_gemm_f32
+ *                               (d(out) = dT_final W^T, beta 0 -- never stored) + dgcnn_bn1_bwd_dropout_f32 on the FC layer;
+ *                               phases: 1 = the sums pass (leaves dT_final in Tf: the Final layer's weight gradient can start),
+ *                               2 = finalize + dT, 3 = both. */
+int dgcnn_bn1_act_class_f32(const float* T, int64_t R, int F, const float* mean, const float* rstd, const float* beta,
+                            int relu, float keep, const uint64_t* seed_dev, float* out, int64_t ldo, const float* W,
+                            int64_t ldw, int ncls, float* logits, int64_t ldc, double* stats, float* scal, void* stream);
+int dgcnn_bn_softmax_xent_f32(const float* Y, const double* stats, double count, float eps, const float* beta, int relu,
+                              int64_t rows, int ncls, float* mean, float* rstd, float* fin, const int32_t* labels,
+                              const float* weight, float* softmax, float* dlogits, float* scal, void* stream);
+int dgcnn_bn1_bwd_class_f32(const float* T, int64_t R, int F, const float* mean, const float* rstd, const float* beta,
+                            int relu, float keep, const uint64_t* seed_dev, float* Tf, int ncls, const float* mean_f,
+                            const float* rstd_f, const float* beta_f, int relu_f, const float* dfin, double* red_f,
+                            float* dbeta_f, float dbeta_f_beta, const float* W, int64_t ldw, double* red, float* dT,
+                            float* dbeta, float dbeta_beta, int phases, void* stream);
+
 /* conv0 backward of a layer whose input needs no gradient and has C <= 4 channels (the first EdgeConv layer: raw coordinates),
  * in ONE pass: dY is formed per edge exactly as in dgcnn_edge_bn_bwd_apply_f32 and consumed on the spot,
  * dW0[2C][F] += [x_i, x_j - x_i]^T dY (ops.py:39-52) -- no dY tensor, no transposed adjacency, no point-level GEMMs.
