@@ -60,7 +60,8 @@ __global__ __launch_bounds__(256) void sqnorm_kernel(const float* __restrict__ x
 // bin at which the count reaches k.  The scan then drops every candidate at or above that edge before it reaches the sorted lists:
 // ~1.3 k candidates pass per row instead of ~k (1 + ln(N / k)) per LIST (four lists per row), and the sorted inserts were three
 // quarters of the scan's instructions (r05_pmc_sq.txt).  Rigorous for any input: a candidate dropped has k candidates strictly below it;
-// a coarse bin (many equal distances) only makes the bound looser.  Per candidate: one LDS broadcast read, the 6-operation distance,
+// a coarse bin (many equal distances) only makes the bound looser; a NaN distance (+inf in the selection's order) and +inf are counted
+// in the top bin, under no edge.  Per candidate: one LDS broadcast read, the 6-operation distance,
 // clamp, shift, one ds_add_u32 into the thread's own column of the histogram ([bin][thread]: bank = thread, conflict free).
 constexpr int HB_NB = 48;
 template <int STRIDE, class Clouds = DenseClouds>
@@ -124,9 +125,12 @@ __global__ __launch_bounds__(256) void knn_hist_bound_kernel(const float* __rest
       p = fmaf(xi[3], v.w, p);
       const float tt = si + sj;
       const float tp = 2.0f * p;
-      const float d = fmaxf(tt - tp, 0.0f);
+      const float dn = tt - tp;
+      const float d = fmaxf(dn, 0.0f);
       const int bin = (int)(__float_as_uint(d) >> 22) - bin0;
-      return bin < 0 ? 0 : (bin > HB_NB - 1 ? HB_NB - 1 : bin);
+      // a NaN distance counts as +inf (fmaxf has made it 0): the top bin, which has no edge -- below an edge it would be counted as
+      // one of the k that the edge's bound rests on, and the scan never lists it
+      return (dn != dn) ? HB_NB - 1 : (bin < 0 ? 0 : (bin > HB_NB - 1 ? HB_NB - 1 : bin));
     };
     int t = lo;
     // groups of 8: all LDS reads of a group first, then the arithmetic, then the 8 adds (hipcc will not move a read across a
@@ -317,6 +321,7 @@ __global__ __launch_bounds__(256, (knn_min_waves<CP, KC>())) void knn_kernel(con
 #pragma unroll
     for (int t = 0; t < KC; ++t)
       if (t < k) out[t] = Clouds::kPacked ? (int)cb + jl[t] : jl[t];
+    fill_short_list<KC>(jl, k, N, Clouds::kPacked ? (int)cb : 0, out);      // fewer than k candidates below +inf (knn_common.h)
   }
 }
 
@@ -537,6 +542,7 @@ __global__ __launch_bounds__(256, (KC <= 20 ? 3 : 2)) void knn_mfma_kernel(const
 #pragma unroll
     for (int t = 0; t < KC; ++t)
       if (t < k) out[t] = jl[t];
+    fill_short_list<KC>(jl, k, N, 0, out);                                  // fewer than k candidates below +inf (knn_common.h)
   }
 }
 
@@ -810,6 +816,7 @@ __global__ __launch_bounds__(256, (Bf16fCfg<KC>::OCC)) void knn_bf16f_kernel(con
 #pragma unroll
     for (int t = 0; t < KC; ++t)
       if (t < k) out[t] = jl[t];
+    fill_short_list<KC>(jl, k, N, 0, out);                                  // fewer than k candidates below +inf (knn_common.h)
   }
 }
 
@@ -1240,11 +1247,16 @@ __global__ __launch_bounds__(256, ((LX || NPR != 1) ? 3 : 4)) void knn_bf16a_ker
   if (tid < ROWS && row0 + tid < N) cnt[grow0 + tid] = cnt_s[tid];
 }
 
-// the k smallest keys of every row's buffer, ascending: one wave per row
+// the k smallest keys of every row's buffer, ascending: one wave per row.
+// S < k (non-finite input only: the scan appends d < thr <= +inf, so a buffer holds every candidate below +inf until k of them have
+// been seen -- the seed bound is finite only if k seeds are at finite distance, every later bound is the k-th of a buffer): the row's
+// other k - S entries are the candidates at D~ = +inf by ascending j, i.e. the lowest j of the cloud that the buffer does not hold.
+// They are among 0 .. 2 k - 1 < 128: two 64-bit presence masks built from the S sorted entries, every lane ranks its own two values.
+template <class Clouds>
 __global__ __launch_bounds__(256) void knn_select_kernel(const unsigned long long* __restrict__ ent, const int* __restrict__ cnt,
-                                                         int64_t rows, int cap, int k, int32_t* __restrict__ idx) {
+                                                         Clouds cl, int64_t rows, int cap, int k, int32_t* __restrict__ idx) {
   const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t row = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));       // (one row per wave)
   if (row >= rows) return;
   const int S = cnt[row];
   const unsigned long long* buf = ent + row * cap;
@@ -1252,7 +1264,32 @@ __global__ __launch_bounds__(256) void knn_select_kernel(const unsigned long lon
   if (S <= 64) {
     unsigned long long key = (lane < S) ? buf[lane] : ~0ull;
     key = wave_sort64(key, lane);
-    if (lane < k) out[lane] = (int32_t)(unsigned)key;
+    if (lane < (S < k ? S : k)) out[lane] = (int32_t)(unsigned)key;
+    if (S < k) {                             // wave-uniform
+      int base = 0, N = 0;
+      if constexpr (Clouds::kPacked) {
+        const int cloud = cl.cloud_of(row);
+        base = (int)cl.base(cloud);
+        N = cl.size(cloud);
+      } else {
+        N = cl.N;
+      }
+      const int jloc = (lane < S) ? (int)(unsigned)key - base : -1;
+      unsigned long long held0 = 0ull, held1 = 0ull;
+      for (int t = 0; t < S; ++t) {
+        const unsigned st = (unsigned)__builtin_amdgcn_readlane(jloc, t);
+        if (st < 64u) held0 |= 1ull << st;
+        else if (st < 128u) held1 |= 1ull << (st - 64u);
+      }
+      // values v < N only (k <= N: there are at least k - S of them)
+      const unsigned long long in0 = N >= 64 ? ~0ull : ((1ull << N) - 1ull);
+      const unsigned long long in1 = N >= 128 ? ~0ull : (N > 64 ? ((1ull << (N - 64)) - 1ull) : 0ull);
+      const unsigned long long free0 = ~held0 & in0, free1 = ~held1 & in1;
+      const unsigned long long below = (1ull << lane) - 1ull;
+      const int p0 = S + __popcll(free0 & below), p1 = S + __popcll(free0) + __popcll(free1 & below);
+      if (((free0 >> lane) & 1ull) && p0 < k) out[p0] = base + lane;
+      if (((free1 >> lane) & 1ull) && p1 < k) out[p1] = base + 64 + lane;
+    }
     return;
   }
   unsigned long long key[KA_MAXE];
@@ -1288,7 +1325,7 @@ bool knn_force_valu() { return g_knn_valu == 1; }
 // product; adding 2^-16 (s_i + s_j) (> 4x the worst case, and far below anything that matters to the filter) makes
 //     tau0 = max_m [ (s_i + s_j) - 2 p~ + 2^-16 (s_i + s_j) ]
 // an upper bound of the normative distances -- all the proof needs (k distinct candidates at distance <= tau0).
-// Seeds that are not k DISTINCT in-range indices give +inf (no bound).
+// Seeds that are not k DISTINCT in-range indices give +inf (no bound), and so does a seed at a NaN distance.
 // Packed towers: seeds are tower rows, and only rows of the query row's own cloud count (a row of a neighbouring cloud can be nearer
 // than every true candidate: its distance would be no bound).
 template <int LP, int MAXSTEPS, class Clouds = DenseClouds>
@@ -1363,9 +1400,14 @@ __global__ __launch_bounds__(256) void knn_seed_bound_kernel(const float* __rest
     }
     anybad[w] = b;
   }
+  // The maximum is taken on the distances' BIT PATTERNS as unsigned integers.  Every d here is +0 or positive, +inf or NaN (the slack
+  // 2^-16 tt outweighs the rounding of tt - 2 p~, and finite s_i, s_j leave no way to an infinite p~), and on those the unsigned order is
+  // the float order with every NaN, of either sign, above +inf -- fmaxf would DROP a NaN and leave a bound that rests on fewer than k
+  // candidates.  A NaN distance is +inf in the selection's order: anything above +inf's pattern means no bound.  (One v_max_u32 per pair
+  // where fmaxf was one v_max_f32; a pattern with the sign bit set, should one ever occur, also reads as no bound.)
 #pragma unroll
   for (int w = 0; w < RW; ++w) {
-    float best = -INFINITY;
+    unsigned best = 0u;
 #pragma unroll
     for (int s = 0; s < MAXSTEPS; ++s) {
       if (s < steps) {
@@ -1374,13 +1416,16 @@ __global__ __launch_bounds__(256) void knn_seed_bound_kernel(const float* __rest
 #pragma unroll
         for (int o = 1; o < LP; o <<= 1) p += __shfl_xor(p, o, 64);
         const float tt = si[w] + sj[w][s];
-        const float d = fmaf(-2.0f, p, tt) + tt * (1.0f / 65536.0f);
-        best = (s * PPS + slot < k) ? fmaxf(best, d) : best;
+        const unsigned d = __float_as_uint(fmaf(-2.0f, p, tt) + tt * (1.0f / 65536.0f));
+        best = (s * PPS + slot < k) ? (d > best ? d : best) : best;
       }
     }
 #pragma unroll
-    for (int o = LP; o < 64; o <<= 1) best = fmaxf(best, __shfl_xor(best, o, 64));
-    if (lane == 0 && g0 + w < rows) tau0[g0 + w] = anybad[w] ? INFINITY : best;
+    for (int o = LP; o < 64; o <<= 1) {
+      const unsigned ob = __shfl_xor(best, o, 64);
+      best = ob > best ? ob : best;
+    }
+    if (lane == 0 && g0 + w < rows) tau0[g0 + w] = (anybad[w] || best > 0x7f800000u) ? INFINITY : __uint_as_float(best);
   }
 }
 
@@ -1603,7 +1648,8 @@ void launch_append_scan(const CloudSet<Clouds>& s, const KnnCall& a, const float
   if (lx) { if (npr == 1) DG_KA(true, 1); else DG_KA(true, 3); }
   else { if (npr == 1) DG_KA(false, 1); else DG_KA(false, 3); }
 #undef DG_KA
-  dg::launch(knn_select_kernel, dim3((unsigned)dg::cdiv(s.rows, 4)), dim3(256), 0, a.st, w.entries(), w.cnt(), s.rows, w.cap, a.k, a.idx);
+  dg::launch(knn_select_kernel<Clouds>, dim3((unsigned)dg::cdiv(s.rows, 4)), dim3(256), 0, a.st, w.entries(), w.cnt(), s.cl, s.rows, w.cap, a.k,
+             a.idx);
 }
 
 // The scan that keeps its lists.  Dense, 16 < C <= 64: the bf16 matrix pipe + exact re-check of the survivors (large graphs, or a seed

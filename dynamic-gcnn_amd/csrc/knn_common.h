@@ -100,4 +100,32 @@ __device__ __forceinline__ void list_insert(float (&dl)[KC], int (&jl)[KC], floa
   jl[0] = sel_i(ct, j, jl[0]);
 }
 
+// ---- rows with fewer than k candidates below +inf (non-finite input; include/dgcnn_hip.h, K1) ---------------------------------------
+// The selection is by (D~, j), D~ = +inf where D is NaN: the candidates no form ever lists (d < thr fails for NaN and +inf) all have
+// D~ = +inf and follow the listed ones by ascending j.  Every filter in front of a list (its own k-th entry, the shared bound, a seed
+// or histogram bound, a bf16 margin on a finite threshold) is finite only once k candidates at finite distance exist, so a row that
+// ends with F < k entries has dropped no candidate with D < +inf: its other k - F entries are the lowest j of the cloud that are not
+// among the F.  One lane per row, after the scan (a finite cloud never takes the branch): `jat(t)` = the t-th listed cloud-local j,
+// t < F; the fill is written to out[F .. k) with `base` added (the cloud's first tower row, 0 for dense clouds).  k <= N: the loop
+// ends by v < N whatever the list holds, and stores to out[c], c < k, only.
+template <int KC, class JAt>
+__device__ __forceinline__ void fill_short_row(JAt jat, int F, int k, int N, int base, int32_t* out) {
+  int c = F;
+#pragma unroll 1
+  for (int v = 0; v < N && c < k; ++v) {
+    bool in = false;
+#pragma unroll
+    for (int t = 0; t < KC; ++t) in = in || (t < F && jat(t) == v);
+    if (!in) out[c++] = base + v;
+  }
+}
+// the sentinel form: a list of the scan kernels, ascending, open slots = 0x7fffffff at its end
+template <int KC>
+__device__ __forceinline__ void fill_short_list(const int (&jl)[KC], int k, int N, int base, int32_t* out) {
+  int F = 0;
+#pragma unroll
+  for (int t = 0; t < KC; ++t) F += (t < k && jl[t] != 0x7fffffff) ? 1 : 0;
+  if (F < k) fill_short_row<KC>([&](int t) { return jl[t]; }, F, k, N, base, out);
+}
+
 }  // namespace

@@ -391,6 +391,13 @@ __global__ __launch_bounds__(64 * QW) void knn_grid_query_kernel(const float4* _
 #pragma unroll
     for (int t = 0; t < KC; ++t)
       if (t < k) out[t] = Clouds::kPacked ? (int32_t)cb + (int32_t)(unsigned)kl[t] : (int32_t)(unsigned)kl[t];
+    // Fewer than k candidates below +inf (non-finite input: knn_common.h).  A NaN distance fails d <= thr and leaves KEY_NONE; a +inf
+    // one is listed, but both are D~ = +inf and sort together by j: everything from the first key at +inf on is refilled.  The lane
+    // has seen every point (its k-th key is at +inf, so no stop test held before the ring covered the grid).
+    int F = 0;
+#pragma unroll
+    for (int t = 0; t < KC; ++t) F += (t < k && (unsigned)(kl[t] >> 32) < 0xff800000u) ? 1 : 0;
+    if (F < k) fill_short_row<KC>([&](int t) { return (int)(unsigned)kl[t]; }, F, k, N, Clouds::kPacked ? (int)cb : 0, out);
   }
 }
 

@@ -11,6 +11,7 @@ in the reference.  `sess` arguments are accepted and ignored.
 """
 from __future__ import annotations
 
+import gc
 import math
 import os
 import sys
@@ -390,6 +391,15 @@ class trainval(object):
             # happens to the cache it came from
             ent["seg"] = self._dense_seg(int(pts.shape[0]), int(pts.shape[1]))
         hook = c.head_grads_hook
+        # No cyclic garbage collection while the step is recorded.  A collection that runs in the middle of it can free what an EARLIER
+        # recording left behind in a dead cycle -- a trainval whose tower was wrapped, with its entries' private memory pools and
+        # captured graphs -- and the caching allocator refuses to release a pool's blocks while another pool (or a capture) is in use:
+        # the refusal is raised inside a destructor and ends the process.  torch.cuda.graph collects once on entry for the same reason;
+        # the launch-plan branch did not, and neither is safe from the collector's own schedule, which depends on every allocation the
+        # process has made so far.  So: collect now, outside the recording, and keep the collector off until the recording is over.
+        gc.collect()
+        gc_was_on = gc.isenabled()
+        gc.disable()
         try:
             c.ensure_arena(int(pts.shape[0]) * int(pts.shape[1]))
             ent["arena"] = c.arena_key()
@@ -442,6 +452,8 @@ class trainval(object):
             c.side_busy = False
             c.side_hold = []
             c.head_grads_hook = hook if ent is None else None
+            if gc_was_on:
+                gc.enable()
         if ent is not None:
             ent["stat_used"] = c.stat_off                        # doubles of the statistics arena the captured step writes
             ent["pool_bytes"] = _pool_bytes(ent.get("pool"))

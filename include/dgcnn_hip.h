@@ -51,6 +51,12 @@ const char* dgcnn_last_error(void);
  * idx[b][i][0..k) = the k smallest D_ij = (s_i + s_j) - 2 <x_i,x_j> of row i (self included),
  * ascending, ties -> lower j.  Arithmetic order is normative (oracle/knn_oracle.c): bit-exact.
  * x: (B,N,C) with row stride ldx.  No (B,N,N) matrix is ever written to HBM.
+ * Non-finite input (NaN or infinite coordinates, or finite ones whose s_i, s_i + s_j or 2 <x_i,x_j> overflow): the key of candidate
+ *   j for row i is (D~_ij, j), D~ = +inf where D_ij is NaN and D_ij otherwise (-inf sorts first); idx[i] = the k smallest keys,
+ *   ascending, ties -> lower j, in every kernel form and entry (dense, seeded, packed).  So every row of every cloud holds k DISTINCT
+ *   indices of its own cloud whatever x holds: a row with a NaN coordinate holds 0 .. k-1, and a finite row lists candidates at
+ *   infinite or NaN distance only when fewer than k are at a finite one, lowest j first, after the finite ones.  What reads idx
+ *   (edge gathers, scatters) may index with it unchecked.
  * ws: caller scratch (16-byte aligned) of dgcnn_knn_workspace_bytes(B,N,C,k) bytes: the s_i of ops.py:14 and, for raw
  *   coordinates (C <= 4, k <= 40), the sorted copy / cell table of the exact cell-grid search (csrc/knn_grid.hip: the points of
  *   a cloud are bucketed into a uniform grid and a row only meets the candidates of the cells around its own until its k-th

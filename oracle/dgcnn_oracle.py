@@ -109,7 +109,8 @@ def dist_matrix_f32(x: np.ndarray) -> np.ndarray:
 # dgcnn/ops.py:8-19  k_nn
 # ----------------------------------------------------------------------------------------
 def k_nn(points: np.ndarray, k: int) -> np.ndarray:
-    """idx (B,N,k) int32: k smallest D_ij per row incl. self, ascending, ties -> lower index.
+    """idx (B,N,k) int32: k smallest D_ij per row incl. self, ascending, ties -> lower index.  A NaN distance counts as +inf
+    (oracle/knn_oracle.c, NON-FINITE INPUT): one total order (D~_ij, j) whatever the input.
 
     float32 input -> exact C restatement (bit-defined).  Any other dtype -> numpy in that dtype
     with a stable sort (same tie rule; used by the float64 twin)."""
@@ -127,6 +128,7 @@ def k_nn(points: np.ndarray, k: int) -> np.ndarray:
     inner = np.matmul(M, np.transpose(M, (0, 2, 1)))                    # ops.py:12-13
     squared = np.sum(np.square(M), axis=-1, keepdims=True)              # ops.py:14
     nn_dist = squared + np.transpose(squared, (0, 2, 1)) - 2 * inner    # ops.py:15-16
+    nn_dist = np.where(np.isnan(nn_dist), np.inf, nn_dist)              # the selection's D~ (argsort alone puts NaN AFTER +inf)
     order = np.argsort(nn_dist, axis=-1, kind="stable")                 # ops.py:18 (top_k of -D)
     return order[..., :k].astype(np.int32)
 

@@ -17,6 +17,13 @@
  *           p_ij  = fmaf chain over c ascending starting from +0 (an FMA GEMM micro-kernel)
  *           D_ij  = fl( fl(s_i + s_j) - fl(2 p_ij) )
  * Build with -ffp-contract=off so the compiler never fuses or reassociates.
+ *
+ * NON-FINITE INPUT (NaN or infinite coordinates, or finite ones whose s_i, s_i + s_j or 2 p_ij overflow): the selection is by ONE
+ * total order whatever the input.  The key of candidate j for row i is (D~_ij, j) with D~ = +inf where D_ij is NaN and D~ = D_ij
+ * otherwise (-inf stays -inf and sorts first); idx[i] = the k smallest keys, ascending, ties to the lower j.  So every row holds
+ * k distinct indices of [0, N); a row with a NaN coordinate holds 0 .. k-1; a finite row lists a candidate at infinite or NaN
+ * distance only when fewer than k are at a finite one, lowest j first, after the finite ones.  On finite input nothing changes.
+ * (D itself, as oracle_dist_f32 / oracle_dist_pairs_f32 report it, keeps its NaNs: only the selection maps them.)
  */
 #include <math.h>
 #include <stdint.h>
@@ -72,6 +79,8 @@ static void knn_row(const float *xb, const float *s, int N, int C, long ldx, int
     float t = s[i] + s[j];
     float tp = 2.0f * p;
     float d = t - tp;
+    if (d != d) d = INFINITY;   /* the selection's D~: NaN counts as +inf (a raw NaN fails every '<' below and would keep whatever
+                                   slot it was first given) */
     /* sorted insert, strict '<' so that an equal distance with larger j goes after */
     if (filled < k) {
       int t2 = filled++;
