@@ -23,6 +23,7 @@ from __future__ import annotations
 import contextlib
 import os
 from collections import OrderedDict
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -45,7 +46,6 @@ FUSE_DROPOUT = True        # tf.nn.dropout inside the last FC layer's BatchNorm 
 # (csrc/bn.hip: bn1_act_class_kernel ...).  Bit-identical to the separate launches; DGCNN_FUSE_CLASS_TAIL=0 selects those.
 FUSE_CLASS_TAIL = os.environ.get("DGCNN_FUSE_CLASS_TAIL", "1") != "0"
 BF16_FUSED_BWD = True      # bf16 edge-MLP: the layer's backward in one pass over the edges (tests switch it off to compare)
-EDGE_BWD_REDUCE_POINTS = True   # BN backward sums of conv0 from per-point data (False: a pass over the edges)
 SIDE_STREAM_MIN_ROWS = 16384   # below this many points the side stream is not used
 # the side stream's work is off the critical path: least priority / a CU mask that leaves some compute units to the main stream alone
 # (csrc/plan.cc:dgcnn_stream_create; A/B switches -- neither helps, the mask costs 40 %: profiles/r06/side_stream.txt)
@@ -57,7 +57,6 @@ SIDE_STREAM_RESERVE_CUS = int(os.environ.get("DGCNN_SIDE_RESERVE_CUS", "0"))
 # trainval.initialize() sets it per instance from flags.EDGE_MLP_DTYPE.
 EDGE_MLP_DTYPE = "f32"
 EDGE_MLP_NBR_GEMM = False  # True: factored conv0 with an edge-level neighbour GEMM instead of point-level GEMM + gather-add
-SCATTER_ATOMICS = False  # True: dx_j += dY W^T by fp32 atomics in the GEMM epilogue (A/B switch)
 # Deterministic mode (the DEFAULT since round 5): run-to-run bit-reproducible results.  Every statistics / reduction slot has ONE
 # writer (dgcnn_set_stat_slots raises the slot count to the widest producer's workgroup count), the finalize kernels add the slots
 # in a fixed order, the transposed adjacency's buckets are sorted.  Same kernels as the atomics mode otherwise: +3-4 % at
@@ -237,18 +236,11 @@ class Context(object):
         dgcnn_gemm_stat_writers; 0 for the reduction kernels, whose grids follow the slot count), at least 256 -- instead of the
         step-wide maximum: the head's GEMMs run 192 row tiles where conv1's run 768, and every finalize kernel walks (and every
         step zeroes) all slots of its buffer.  Producer and finalize are issued inside the block: they see the same count."""
-        if not DETERMINISTIC:
-            yield
-            return
-        n = max(256, -(-int(writers) // 64) * 64)
-        prev = H.STAT_SLOTS
-        if n != prev:
-            H.set_stat_slots(n)
+        self.push_slots(writers)
         try:
             yield
         finally:
-            if H.STAT_SLOTS != prev:
-                H.set_stat_slots(prev)
+            self.pop_slots()
 
     # ---- operand planes of the head GEMMs (csrc/gemm_pl.hip, planes_bn.hip) ------------------------------
     @staticmethod
@@ -892,7 +884,8 @@ def conv_bn_act(x, leaf_scope, num_outputs, relu=True, out=None, out2=None, gbia
     rows -- always the separate pass over the GEMM output, never the epilogue.  The plane mode is NOT packed: a packed tower
     runs the fp32-class GEMMs (bf16-split / fp32 MFMA) even when HEAD_PLANES is set.
     class_tail: NUM_CLASS of the Final layer that consumes this output NEXT (the last FC layer; FUSE_CLASS_TAIL): where the
-    shapes and modes allow, this layer's BatchNorm + dropout pass is held back and runs with the Final layer's product in it."""
+    shapes and modes allow, this layer's BatchNorm + dropout pass is held back and runs with the Final layer's product in it.
+    Behind the GEMM: one of the tails _conv_tail_class / _dropout / _planes or the plain pass, each a BatchNorm pass with its backward."""
     c = ctx()
     R, Cin = x.shape
     tail, c.class_tail = c.class_tail, None
@@ -919,224 +912,272 @@ def conv_bn_act(x, leaf_scope, num_outputs, relu=True, out=None, out2=None, gbia
         if H.load().dgcnn_gemm_stat_writers(0, R, F, Cin, x.data_ptr(), H.ld2(x), Wx.data_ptr(), H.ld2(Wx)) != 0 or planes_ok(R, Cin, F):
             _launch_bn1_act_dropout(tail)       # (not the streaming class product)
             tail = None
+    # the layer's state: what its passes and its tape closure read (the closure keeps every tensor in it alive)
+    L = SimpleNamespace(x=x, Wx=Wx, beta=beta, R=R, F=F, relu=relu, out=out, out2=out2, gbias=gbias, rpg=rpg, arith=arith, seg=seg,
+                        drop_keep=drop_keep, wname=wname, w_rows=w_rows, bname=bname, xp=None)
     if bpc:
-        return _conv_bn_act_per_cloud(c, x, Wx, beta, F, relu, out, out2, gbias, rgrp, arith, gmax, drop_keep, seg, wname, w_rows, bname)
-    T = torch.empty((R, F), dtype=torch.float32, device=x.device)
+        return _conv_bn_act_per_cloud(c, L, rgrp, gmax)
+    L.T = T = torch.empty((R, F), dtype=torch.float32, device=x.device)
     # slots of this layer's statistics buffer = row tiles of its GEMM (asked from the library; another arithmetic: the step's maximum)
     # (0 = a kernel whose grid FOLLOWS the slot count -- the class dimension's streaming product: the step's maximum, more writers)
     c.push_slots((H.load().dgcnn_gemm_stat_writers(0, R, F, Cin, x.data_ptr(), H.ld2(x), Wx.data_ptr(), H.ld2(Wx)) or c.step_slots)
                  if arith is None else c.step_slots)
     st = c.stats(F)
+    if tail is not None:
+        return _conv_tail_class(c, L, tail, st)
     use_pl = arith is None and seg is None and planes_ok(R, Cin, F)
-    xp = None
     # the per-cloud column maximum (model.py:76-77), when asked for, comes out of the GEMM's epilogue as packed (value, first row)
     # keys -- every row tile must lie inside one cloud: clouds of a multiple of 256 points (the library then runs no 192-row tile,
     # gemm.hip:launch<>); otherwise a separate pass over T below
     keys = None
     if seg is not None:
-        plane_out, f32_out = None, True
         if gmax is not None:
             keys = c.stats_raw(seg.nseg * F)                                   # zeroed uint64[nseg][F], filled by the pass below
     elif gmax is not None and gmax[1] % 256 == 0 and gmax[0] * gmax[1] == R and F > 4:
         keys = c.stats_raw(gmax[0] * F)                                    # zeroed uint64[B][F]
-    if tail is not None:
-        # F1: the held-back BatchNorm + dropout pass of the FC layer writes x AND forms T = x W with its column statistics, on the
-        # streaming product's grid; F2 (softmax_loss) folds the statistics, applies this layer's BatchNorm + ReLU and the loss
-        scal = torch.empty(2, dtype=torch.float32, device=x.device)           # [loss, accuracy]: zeroed by F1
-        H.call("dgcnn_bn1_act_class_f32", tail["T"].data_ptr(), R, Cin, tail["mean"].data_ptr(), tail["rstd"].data_ptr(),
-               tail["beta"].data_ptr(), int(tail["relu"]), float(tail["keep"]), tail["seed"].data_ptr(), x.data_ptr(), H.ld2(x),
-               Wx.data_ptr(), H.ld2(Wx), F, T.data_ptr(), F, st.data_ptr(), scal.data_ptr(),
-               tag="bn1_act_class_kernel", work=4.0 * R * Cin * 2)
-        mr = torch.empty((2, F), dtype=torch.float32, device=x.device)
-        mean, rstd = mr[0], mr[1]
-        if out is None:
-            out = c.new_buffer(R, F)
-        c.loss_tail = dict(T=T, st=st, F=F, R=R, beta=beta, relu=relu, mean=mean, rstd=rstd, out=out, scal=scal,
-                           nslots=H.STAT_SLOTS)
-        c.pop_slots()
-        fuse_drop = False
-    elif use_pl:
+    if use_pl:
         c.ensure_plane_scales(R)
-        xp = c.planes_of(x)                                                # (R, Cin) activations
+        L.xp = c.planes_of(x)                                              # (R, Cin) activations
         wt = prepared(("wT", Wx.data_ptr()))                               # (F rows, Cin channels) = W^T
         if wt is None:
             wt = c.new_planes(F, Cin, "w").fill_from(Wx, transpose=True)
-        PL.gemm(PL.KC, xp, wt, T, gbias=gbias, rpg=rpg, stats=st, colmax=keys, colmax_rpg=0 if keys is None else gmax[1])
+        PL.gemm(PL.KC, L.xp, wt, T, gbias=gbias, rpg=rpg, stats=st, colmax=keys, colmax_rpg=0 if keys is None else gmax[1])
+    elif seg is not None:
+        gemm(x, Wx, T, gbias=gbias, stats=st, arith=arith, row_group=rgrp)
+        if gmax is not None:
+            H.call("dgcnn_colmax_seg_f32", T.data_ptr(), H.ld2(T), R, F, seg.device(x.device).data_ptr(), seg.nseg,
+                   keys.data_ptr(), tag="colmax_seg_kernel", work=4.0 * R * F)
     else:
-        plane_out, f32_out = None, True
-        if seg is not None:
-            gemm(x, Wx, T, gbias=gbias, stats=st, arith=arith, row_group=rgrp)
-            if gmax is not None:
-                H.call("dgcnn_colmax_seg_f32", T.data_ptr(), H.ld2(T), R, F, seg.device(x.device).data_ptr(), seg.nseg,
-                       keys.data_ptr(), tag="colmax_seg_kernel", work=4.0 * R * F)
+        gemm(x, Wx, T, gbias=gbias, rpg=rpg, stats=st, arith=arith, colmax=keys, colmax_rpg=0 if keys is None else gmax[1])
+    L.mean, L.rstd = bn_finalize(st, F, R)
+    c.pop_slots()
+    if out is None:
+        L.out = c.new_buffer(R, F)
+    fuse_drop = drop_keep is not None and FUSE_DROPOUT and not use_pl and F % 4 == 0 and out2 is None and gmax is None
+    if fuse_drop:
+        _conv_tail_dropout(c, L, class_tail)
+    elif use_pl:
+        _conv_tail_planes(c, L, plane_out, f32_out)     # (only the plane GEMM's layers write operand planes)
+    else:
+        _bn1_act(L)
+        if c.recording:
+            _record(c, _conv_plain_bwd, L, None)
+    if gmax is None:
+        if drop_keep is not None and not fuse_drop:
+            return dropout(L.out, drop_keep)       # (plane / deterministic modes: the separate pass)
+        return L.out
+    return L.out, _conv_gmax(c, L, gmax, keys)
+
+
+def _record(c, bwd, *args):
+    """Append bwd(c, *args) to the tape; it runs at the slot count of the reduction kernels (their grids follow it: 256 writers)."""
+    def run():
+        with c.op_slots(0):
+            bwd(c, *args)
+    c.tape.append(run)
+
+
+def _dWx(c, L):
+    """The gradient accumulator of the weight rows that multiply the layer's input."""
+    return c.var_grads[L.wname] if L.w_rows is None else c.var_grads[L.wname][L.w_rows[0]:L.w_rows[1]]
+
+
+def _bn1_act(L):
+    """BatchNorm + activation of the GEMM output T into out (and its second copy out2)."""
+    R, F, out, out2 = L.R, L.F, L.out, L.out2
+    H.call("dgcnn_bn_act_kreduce_f32", L.T.data_ptr(), R, 1, F, L.mean.data_ptr(), L.rstd.data_ptr(), L.beta.data_ptr(),
+           int(L.relu), out.data_ptr(), H.ld2(out), 0, 0, H._p(out2), 0 if out2 is None else H.ld2(out2), 0,
+           tag="bn_act_kreduce_kernel<k=1>", work=4.0 * R * F * (2 if out2 is None else 3))
+
+
+def _bn1_bwd_inputs(c, L, join):
+    """(d(out), d(out2) or None, zeroed sums, d(gbias) or None) of a k = 1 BatchNorm backward; None: nobody wants the gradient.
+    join: the passes read ONE gradient (fused dropout, planes; the default passes read both, except for the shapes tested here)."""
+    dout = c.grad(L.out)
+    if dout is None:
+        return None
+    d2 = c.grad(L.out2) if L.out2 is not None else None
+    # (DETERMINISTIC: unaligned parameter slices send the reduce to the fixed-order twin, which takes one gradient)
+    if d2 is not None and (join or L.F % 4 != 0 or
+                           (DETERMINISTIC and not k1_reduce_fixed_order(L.T, 1, L.F, L.mean, L.rstd, L.beta, dout, d2, None))):
+        # the second copy's gradient joins the first (the default passes read both instead)
+        H.call("dgcnn_copy2d_f32", d2.data_ptr(), H.ld2(d2), dout.data_ptr(), H.ld2(dout), L.R, L.F, 1)
+        d2 = None
+    red = c.stats(L.F)
+    dgb = c.grad(L.gbias) if L.gbias is not None else None
+    return dout, d2, red, dgb
+
+
+def _conv_bwd_products(c, L, dT, dgb):
+    """The end of a layer's backward, from dT = d(GEMM output).  Data gradient FIRST, on the critical path; the weight gradient is
+    issued behind it on the side stream, so that it runs under the bandwidth-bound BatchNorm / gather passes that follow on the main
+    stream -- not next to the data gradient, another matrix-pipe kernel at the package power cap (both then run at half speed:
+    profiles/r03/wgrad_order.txt).  Last the gradient of the per-cloud bias."""
+    dx, bx = c.grad_w(L.x)
+    if dx is not None:
+        gemm(dT, L.Wx, dx, transB=True, beta=bx, arith=L.arith)       # dx (+)= dT W^T
+    with c.off_critical_path(rows=L.R):
+        gemm(L.x, dT, _dWx(c, L), transA=True, beta=1.0, arith=L.arith)   # dW += x^T dT
+    if dgb is not None:                                                 # tf.tile^T: sum over the cloud
+        tmp = torch.empty_like(L.gbias)
+        if L.seg is not None:
+            seg_colsum(dT, L.seg, tmp)
         else:
-            gemm(x, Wx, T, gbias=gbias, rpg=rpg, stats=st, arith=arith, colmax=keys, colmax_rpg=0 if keys is None else gmax[1])
-    if tail is None:
-        mean, rstd = bn_finalize(st, F, R)
-        c.pop_slots()
-        if out is None:
-            out = c.new_buffer(R, F)
-        fuse_drop = (drop_keep is not None and FUSE_DROPOUT and not use_pl and F % 4 == 0 and out2 is None and
-                     gmax is None and plane_out is None)
-    held = None
-    if tail is not None:
-        pass                                    # (this layer's BatchNorm + ReLU run with the loss: softmax_loss, F2)
-    elif fuse_drop:
-        if c.seed_dev is None:
-            c.advance_seed()
-        seed = c.seed_dev                       # device-resident: the backward regenerates the mask from the same value
-        held = dict(T=T, R=R, F=F, mean=mean, rstd=rstd, beta=beta, relu=relu, keep=drop_keep, seed=seed, out=out,
-                    ncls=class_tail, bwd=None)
-        if (class_tail is not None and FUSE_CLASS_TAIL and DETERMINISTIC and c.dense_loss_follows and c.recording and
-                seg is None and gbias is None and w_rows is None and F == 256 and 1 <= int(class_tail) <= 4 and
-                out.is_contiguous()):
-            c.class_tail = held                 # runs inside the Final layer's call (F1), or as the plain pass if that is not next
-        else:
-            _launch_bn1_act_dropout(held)
-    elif plane_out is not None:
-        H.call("dgcnn_bn_act_planes_f32", T.data_ptr(), F, R, F, mean.data_ptr(), rstd.data_ptr(), beta.data_ptr(), int(relu),
+            H.call("dgcnn_group_colsum_f32", dT.data_ptr(), H.ld2(dT), L.gbias.shape[0], L.rpg, L.F, tmp.data_ptr())
+        H.call("dgcnn_axpby_f32", tmp.data_ptr(), 1.0, dgb.data_ptr(), 1.0, tmp.numel())
+
+
+def _conv_tail_class(c, L, tail, st):
+    """The Final layer behind a held-back FC layer (tail).  F1: the held-back BatchNorm + dropout pass of the FC layer writes x AND
+    forms T = x W with its column statistics, on the streaming product's grid; F2 (softmax_loss) folds the statistics, applies
+    this layer's BatchNorm + ReLU and the loss.  Backward: the sums here, the rest inside the FC layer's passes where it can."""
+    x, Wx, T, R, F = L.x, L.Wx, L.T, L.R, L.F
+    scal = torch.empty(2, dtype=torch.float32, device=x.device)           # [loss, accuracy]: zeroed by F1
+    H.call("dgcnn_bn1_act_class_f32", tail["T"].data_ptr(), R, x.shape[1], tail["mean"].data_ptr(), tail["rstd"].data_ptr(),
+           tail["beta"].data_ptr(), int(tail["relu"]), float(tail["keep"]), tail["seed"].data_ptr(), x.data_ptr(), H.ld2(x),
+           Wx.data_ptr(), H.ld2(Wx), F, T.data_ptr(), F, st.data_ptr(), scal.data_ptr(),
+           tag="bn1_act_class_kernel", work=4.0 * R * x.shape[1] * 2)
+    mr = torch.empty((2, F), dtype=torch.float32, device=x.device)
+    L.mean, L.rstd = mr[0], mr[1]
+    if L.out is None:
+        L.out = c.new_buffer(R, F)
+    c.loss_tail = dict(T=T, st=st, F=F, R=R, beta=L.beta, relu=L.relu, mean=L.mean, rstd=L.rstd, out=L.out, scal=scal,
+                       nslots=H.STAT_SLOTS)
+    c.pop_slots()
+    if c.recording:
+        _record(c, _conv_plain_bwd, L, tail)
+    return L.out
+
+
+def _conv_plain_bwd(c, L, tail):
+    """Sums, then dT in place of T, then the products.  tail: the FC layer's record when this is the Final layer behind it."""
+    g = _bn1_bwd_inputs(c, L, False)
+    if g is None:
+        return
+    dout, d2, red, dgb = g
+    T, R, F, mean, rstd, beta, relu = L.T, L.R, L.F, L.mean, L.rstd, L.beta, L.relu
+    nsrc = 1 if d2 is None else 2                                  # k = 1: dz = dout + d2 (the kernels' dmax + dmean / k)
+    bn_bwd_reduce(T, R, 1, F, mean, rstd, beta, relu, dout, d2, None, None, red,
+                  tag="bn_bwd_reduce_kernel<k=1>", work=4.0 * R * F * (1 + nsrc))
+    if tail is not None and FUSE_CLASS_TAIL and d2 is None and dgb is None and dout.is_contiguous() and c.first_touch(L.x):
+        # the rest of this layer's backward runs inside the FC layer's passes (B1 / B2: _conv_dropout_bwd)
+        tail["bwd"] = dict(Tf=T, ncls=F, mean=mean, rstd=rstd, beta=beta, relu=relu, dfin=dout, red=red,
+                           dbeta=c.var_grads[L.bname], W=L.Wx, dWx=_dWx(c, L))
+        return
+    H.call("dgcnn_bn_bwd_apply_f32", T.data_ptr(), R, 1, F, mean.data_ptr(), rstd.data_ptr(), beta.data_ptr(),
+           int(relu), dout.data_ptr(), H.ld2(dout), H._p(d2), 0 if d2 is None else H.ld2(d2), 0, 0, 0, red.data_ptr(),
+           T.data_ptr(), 0, 0, c.var_grads[L.bname].data_ptr(), 1.0, tag="bn_bwd_apply_kernel<k=1>", work=4.0 * R * F * (2 + nsrc))
+    _conv_bwd_products(c, L, T, dgb)
+
+
+def _conv_tail_dropout(c, L, class_tail):
+    """tf.nn.dropout inside the layer's BatchNorm passes (FUSE_DROPOUT).  class_tail: the pass is held back for the Final layer's
+    call (c.class_tail; conv_bn_act, flush_class_tail and the backward of that layer answer through the record)."""
+    if c.seed_dev is None:
+        c.advance_seed()
+    L.seed = c.seed_dev                     # device-resident: the backward regenerates the mask from the same value
+    held = dict(T=L.T, R=L.R, F=L.F, mean=L.mean, rstd=L.rstd, beta=L.beta, relu=L.relu, keep=L.drop_keep, seed=L.seed, out=L.out,
+                ncls=class_tail, bwd=None)
+    if (class_tail is not None and FUSE_CLASS_TAIL and DETERMINISTIC and c.dense_loss_follows and c.recording and
+            L.seg is None and L.gbias is None and L.w_rows is None and L.F == 256 and 1 <= int(class_tail) <= 4 and
+            L.out.is_contiguous()):
+        c.class_tail = held                 # runs inside the Final layer's call (F1), or as the plain pass if that is not next
+    else:
+        _launch_bn1_act_dropout(held)
+    if c.recording:
+        _record(c, _conv_dropout_bwd, L, held)
+
+
+def _conv_dropout_bwd(c, L, held):
+    T, R, F, mean, rstd, beta, relu = L.T, L.R, L.F, L.mean, L.rstd, L.beta, L.relu
+    tb = held["bwd"]
+    if tb is not None:
+        # B1, finalize, B2: d(out) = dT_final W_final^T is formed in registers (never stored); B1 also applies the Final
+        # layer's BatchNorm backward (dT_final in place of its GEMM output, d(beta_final))
+        red = c.stats(F)
+        args = (T.data_ptr(), R, F, mean.data_ptr(), rstd.data_ptr(), beta.data_ptr(), int(relu), float(L.drop_keep),
+                L.seed.data_ptr(), tb["Tf"].data_ptr(), tb["ncls"], tb["mean"].data_ptr(), tb["rstd"].data_ptr(),
+                tb["beta"].data_ptr(), int(tb["relu"]), tb["dfin"].data_ptr(), tb["red"].data_ptr(), tb["dbeta"].data_ptr(),
+                1.0, tb["W"].data_ptr(), H.ld2(tb["W"]), red.data_ptr(), T.data_ptr(), c.var_grads[L.bname].data_ptr(), 1.0)
+        H.call("dgcnn_bn1_bwd_class_f32", *args, 1, tag="bn1_bwd_class_kernel", work=4.0 * R * F)
+        # the Final layer's weight gradient starts as soon as B1 has left dT_final: on the side stream, under the two
+        # bandwidth-bound launches below -- not next to this layer's data-gradient GEMM
+        with c.off_critical_path(rows=R):
+            gemm(L.out, tb["Tf"], tb["dWx"], transA=True, beta=1.0)
+        H.call("dgcnn_bn1_bwd_class_f32", *args, 2, tag="bn1_bwd_class_kernel", work=4.0 * R * F * 2)
+        held["bwd"] = None
+        _conv_bwd_products(c, L, T, None)
+        return
+    g = _bn1_bwd_inputs(c, L, True)
+    if g is None:
+        return
+    dout, _, red, dgb = g
+    # sums, finalise (+ dbeta) and dT (in place of T), all reading d(dropped output) through the regenerated mask
+    H.call("dgcnn_bn1_bwd_dropout_f32", T.data_ptr(), R, F, mean.data_ptr(), rstd.data_ptr(), beta.data_ptr(), int(relu),
+           float(L.drop_keep), L.seed.data_ptr(), dout.data_ptr(), H.ld2(dout), red.data_ptr(), T.data_ptr(),
+           c.var_grads[L.bname].data_ptr(), 1.0, tag="bn_bwd_apply_kernel<k=1>", work=4.0 * R * F * 5)
+    _conv_bwd_products(c, L, T, dgb)
+
+
+def _conv_tail_planes(c, L, plane_out, f32_out):
+    """A layer of the plane GEMM: plane_out receives the activated output as operand planes of the next product (else the plain
+    pass); the backward writes dT as planes and runs both products on the plane GEMM."""
+    if plane_out is None:
+        _bn1_act(L)
+    else:
+        T, R, F, out, out2 = L.T, L.R, L.F, L.out, L.out2
+        H.call("dgcnn_bn_act_planes_f32", T.data_ptr(), F, R, F, L.mean.data_ptr(), L.rstd.data_ptr(), L.beta.data_ptr(), int(L.relu),
                plane_out.fmt, H._p(plane_out.scale), plane_out.ptr(), plane_out.plane_stride, plane_out.ra,
                out.data_ptr() if f32_out else 0, H.ld2(out), H._p(out2) if f32_out else 0, 0 if out2 is None else H.ld2(out2),
                tag="bn_act_planes_kernel", work=4.0 * R * F * (2 + (1 if f32_out else 0)))
         c.planes[c.plane_key(out)] = plane_out
-    else:
-        H.call("dgcnn_bn_act_kreduce_f32", T.data_ptr(), R, 1, F, mean.data_ptr(), rstd.data_ptr(), beta.data_ptr(),
-               int(relu), out.data_ptr(), H.ld2(out), 0, 0, H._p(out2), 0 if out2 is None else H.ld2(out2), 0,
-               tag="bn_act_kreduce_kernel<k=1>", work=4.0 * R * F * (2 if out2 is None else 3))
-
     if c.recording:
-        def bwd():
-            c.push_slots(0)                      # (the reduction kernels' grids follow the slot count: 256 writers)
-            try:
-                bwd_body()
-            finally:
-                c.pop_slots()
+        _record(c, _conv_planes_bwd, L)
 
-        def bwd_body():
-            tb = held["bwd"] if held is not None else None
-            if tb is not None:
-                # B1, finalize, B2: d(out) = dT_final W_final^T is formed in registers (never stored); B1 also applies the Final
-                # layer's BatchNorm backward (dT_final in place of its GEMM output, d(beta_final))
-                red = c.stats(F)
-                args = (T.data_ptr(), R, F, mean.data_ptr(), rstd.data_ptr(), beta.data_ptr(), int(relu), float(drop_keep),
-                        seed.data_ptr(), tb["Tf"].data_ptr(), tb["ncls"], tb["mean"].data_ptr(), tb["rstd"].data_ptr(),
-                        tb["beta"].data_ptr(), int(tb["relu"]), tb["dfin"].data_ptr(), tb["red"].data_ptr(), tb["dbeta"].data_ptr(),
-                        1.0, tb["W"].data_ptr(), H.ld2(tb["W"]), red.data_ptr(), T.data_ptr(), c.var_grads[bname].data_ptr(), 1.0)
-                H.call("dgcnn_bn1_bwd_class_f32", *args, 1, tag="bn1_bwd_class_kernel", work=4.0 * R * F)
-                # the Final layer's weight gradient starts as soon as B1 has left dT_final: on the side stream, under the two
-                # bandwidth-bound launches below -- not next to this layer's data-gradient GEMM
-                with c.off_critical_path(rows=R):
-                    gemm(out, tb["Tf"], tb["dWx"], transA=True, beta=1.0)
-                H.call("dgcnn_bn1_bwd_class_f32", *args, 2, tag="bn1_bwd_class_kernel", work=4.0 * R * F * 2)
-                held["bwd"] = None
-                dx, bx = c.grad_w(x)
-                if dx is not None:
-                    gemm(T, Wx, dx, transB=True, beta=bx, arith=arith)
-                with c.off_critical_path(rows=R):
-                    gemm(x, T, c.var_grads[wname] if w_rows is None else c.var_grads[wname][w_rows[0]:w_rows[1]], transA=True,
-                         beta=1.0, arith=arith)
-                return
-            dout = c.grad(out)
-            if dout is None:
-                return
-            d2 = c.grad(out2) if out2 is not None else None
-            # (DETERMINISTIC: unaligned parameter slices send the reduce to the fixed-order twin, which takes one gradient)
-            if d2 is not None and (fuse_drop or use_pl or F % 4 != 0 or
-                                   (DETERMINISTIC and not k1_reduce_fixed_order(T, 1, F, mean, rstd, beta, dout, d2, None))):
-                # the second copy's gradient joins the first (the default passes below read both instead)
-                H.call("dgcnn_copy2d_f32", d2.data_ptr(), H.ld2(d2), dout.data_ptr(), H.ld2(dout), R, F, 1)
-                d2 = None
-            red = c.stats(F)
-            dWx = c.var_grads[wname] if w_rows is None else c.var_grads[wname][w_rows[0]:w_rows[1]]
-            dgb = c.grad(gbias) if gbias is not None else None
-            if fuse_drop:
-                # sums, finalise (+ dbeta) and dT (in place of T), all reading d(dropped output) through the regenerated mask
-                H.call("dgcnn_bn1_bwd_dropout_f32", T.data_ptr(), R, F, mean.data_ptr(), rstd.data_ptr(), beta.data_ptr(), int(relu),
-                       float(drop_keep), seed.data_ptr(), dout.data_ptr(), H.ld2(dout), red.data_ptr(), T.data_ptr(),
-                       c.var_grads[bname].data_ptr(), 1.0, tag="bn_bwd_apply_kernel<k=1>", work=4.0 * R * F * 5)
-                dT = T
-                dx, bx = c.grad_w(x)
-                if dx is not None:
-                    gemm(dT, Wx, dx, transB=True, beta=bx, arith=arith)       # data gradient first, on the critical path
-                with c.off_critical_path(rows=R):
-                    gemm(x, dT, dWx, transA=True, beta=1.0, arith=arith)      # weight gradient behind it, on the side stream
-                if dgb is not None:
-                    tmp = torch.empty_like(gbias)
-                    if seg is not None:
-                        seg_colsum(dT, seg, tmp)
-                    else:
-                        H.call("dgcnn_group_colsum_f32", dT.data_ptr(), H.ld2(dT), gbias.shape[0], rpg, F, tmp.data_ptr())
-                    H.call("dgcnn_axpby_f32", tmp.data_ptr(), 1.0, dgb.data_ptr(), 1.0, tmp.numel())
-                return
-            if use_pl:
-                # sums + column maxima -> bound on |dT| -> the dT plane set's scale -> dT written as planes (never as fp32)
-                maxbits = c.stats_raw(F + 1)                              # uint32[2 F + 1]: column maxima + the tensor-wide bound
-                H.call("dgcnn_bn1_bwd_reduce_max_f32", T.data_ptr(), R, F, mean.data_ptr(), rstd.data_ptr(), beta.data_ptr(),
-                       int(relu), dout.data_ptr(), H.ld2(dout), red.data_ptr(), maxbits.data_ptr(),
-                       tag="bn1_bwd_reduce_max_kernel", work=4.0 * R * F * 2)
-                dTp = PL.PlaneSet(R, F, HEAD_PLANES, device=x.device)
-                sc = torch.empty(1, dtype=torch.float32, device=x.device)
-                if HEAD_PLANES == PL.F16X2:
-                    dTp.scale = sc
-                fused_gsum = dgb is not None and rpg % 64 == 0
-                tmp = H.memset(torch.empty_like(gbias)) if fused_gsum else None
-                dT32 = T if (dgb is not None and not fused_gsum) else None        # (in place: every element is read before it is written)
-                H.call("dgcnn_bn1_bwd_apply_planes_f32", T.data_ptr(), R, F, mean.data_ptr(), rstd.data_ptr(), beta.data_ptr(),
-                       int(relu), dout.data_ptr(), H.ld2(dout), red.data_ptr(), maxbits.data_ptr(), HEAD_PLANES, sc.data_ptr(),
-                       dTp.ptr(), dTp.plane_stride, dTp.ra, H._p(dT32), H._p(tmp), F, int(rpg), c.var_grads[bname].data_ptr(), 1.0,
-                       tag="bn1_bwd_apply_planes_kernel", work=4.0 * R * F * 3)
-                # data gradient FIRST, on the critical path; the weight gradient is issued behind it on the side stream, so that it
-                # runs under the bandwidth-bound BatchNorm / gather passes that follow on the main stream -- not next to the data
-                # gradient, another matrix-pipe kernel at the package power cap (both then just run at half speed:
-                # profiles/r03/wgrad_order.txt)
-                dx, bx = c.grad_w(x)
-                if dx is not None:
-                    wd = prepared(("w", Wx.data_ptr()))                                  # (Cin rows, F channels)
-                    if wd is None:
-                        wd = c.new_planes(Wx.shape[0], F, "w").fill_from(Wx)
-                    PL.gemm(PL.KC, dTp, wd, dx, beta=bx)                                 # dx (+)= dT W^T
-                with c.off_critical_path(dTp.buf, sc, rows=R):
-                    PL.gemm(PL.TR, xp, dTp, dWx, beta=1.0, ws=c.workspace())           # dW += x^T dT
-                if dgb is not None:                                                     # tf.tile^T: sum over the cloud
-                    if not fused_gsum:
-                        tmp = torch.empty_like(gbias)
-                        H.call("dgcnn_group_colsum_f32", dT32.data_ptr(), F, gbias.shape[0], rpg, F, tmp.data_ptr())
-                    H.call("dgcnn_axpby_f32", tmp.data_ptr(), 1.0, dgb.data_ptr(), 1.0, tmp.numel())
-                return
-            nsrc = 1 if d2 is None else 2                                  # k = 1: dz = dout + d2 (the kernels' dmax + dmean / k)
-            bn_bwd_reduce(T, R, 1, F, mean, rstd, beta, relu, dout, d2, None, None, red,
-                          tag="bn_bwd_reduce_kernel<k=1>", work=4.0 * R * F * (1 + nsrc))
-            if tail is not None and FUSE_CLASS_TAIL and d2 is None and dgb is None and dout.is_contiguous() and c.first_touch(x):
-                # the rest of this layer's backward runs inside the FC layer's passes (B1 / B2 above)
-                tail["bwd"] = dict(Tf=T, ncls=F, mean=mean, rstd=rstd, beta=beta, relu=relu, dfin=dout, red=red,
-                                   dbeta=c.var_grads[bname], W=Wx, dWx=dWx)
-                return
-            H.call("dgcnn_bn_bwd_apply_f32", T.data_ptr(), R, 1, F, mean.data_ptr(), rstd.data_ptr(), beta.data_ptr(),
-                   int(relu), dout.data_ptr(), H.ld2(dout), H._p(d2), 0 if d2 is None else H.ld2(d2), 0, 0, 0, red.data_ptr(),
-                   T.data_ptr(), 0, 0, c.var_grads[bname].data_ptr(), 1.0, tag="bn_bwd_apply_kernel<k=1>", work=4.0 * R * F * (2 + nsrc))
-            dT = T
-            # data gradient FIRST, on the critical path; the weight gradient is issued behind it on the side stream, so that it
-            # runs under the bandwidth-bound BatchNorm / gather passes that follow on the main stream -- not next to the data
-            # gradient, another matrix-pipe kernel at the package power cap (both then run at half speed: profiles/r03/wgrad_order.txt)
-            dx, bx = c.grad_w(x)
-            if dx is not None:
-                gemm(dT, Wx, dx, transB=True, beta=bx, arith=arith)    # dx (+)= dT W^T
-            with c.off_critical_path(rows=R):
-                gemm(x, dT, dWx, transA=True, beta=1.0, arith=arith)   # dW += x^T dT
-            if dgb is not None:                                         # tf.tile^T: sum over the cloud
-                tmp = torch.empty_like(gbias)
-                if seg is not None:
-                    seg_colsum(dT, seg, tmp)
-                else:
-                    H.call("dgcnn_group_colsum_f32", dT.data_ptr(), H.ld2(dT), gbias.shape[0], rpg, F, tmp.data_ptr())
-                H.call("dgcnn_axpby_f32", tmp.data_ptr(), 1.0, dgb.data_ptr(), 1.0, tmp.numel())
-        c.tape.append(bwd)
-    if gmax is None:
-        if drop_keep is not None and not fuse_drop:
-            return dropout(out, drop_keep)         # (plane / deterministic modes: the separate pass)
-        return out
-    # model.py:76-77 max_pool over the points of each cloud, on the GEMM output: z = relu((t - mean) rstd + beta) is
-    # non-decreasing in t, so max_n z[n] = z(max_n t[n]) and the first arg-max of t is an arg-max of z
+
+def _conv_planes_bwd(c, L):
+    g = _bn1_bwd_inputs(c, L, True)
+    if g is None:
+        return
+    dout, _, red, dgb = g
+    x, Wx, T, R, F, gbias, rpg = L.x, L.Wx, L.T, L.R, L.F, L.gbias, L.rpg
+    # sums + column maxima -> bound on |dT| -> the dT plane set's scale -> dT written as planes (never as fp32)
+    maxbits = c.stats_raw(F + 1)                              # uint32[2 F + 1]: column maxima + the tensor-wide bound
+    H.call("dgcnn_bn1_bwd_reduce_max_f32", T.data_ptr(), R, F, L.mean.data_ptr(), L.rstd.data_ptr(), L.beta.data_ptr(),
+           int(L.relu), dout.data_ptr(), H.ld2(dout), red.data_ptr(), maxbits.data_ptr(),
+           tag="bn1_bwd_reduce_max_kernel", work=4.0 * R * F * 2)
+    dTp = PL.PlaneSet(R, F, HEAD_PLANES, device=x.device)
+    sc = torch.empty(1, dtype=torch.float32, device=x.device)
+    if HEAD_PLANES == PL.F16X2:
+        dTp.scale = sc
+    fused_gsum = dgb is not None and rpg % 64 == 0
+    tmp = H.memset(torch.empty_like(gbias)) if fused_gsum else None
+    dT32 = T if (dgb is not None and not fused_gsum) else None        # (in place: every element is read before it is written)
+    H.call("dgcnn_bn1_bwd_apply_planes_f32", T.data_ptr(), R, F, L.mean.data_ptr(), L.rstd.data_ptr(), L.beta.data_ptr(),
+           int(L.relu), dout.data_ptr(), H.ld2(dout), red.data_ptr(), maxbits.data_ptr(), HEAD_PLANES, sc.data_ptr(),
+           dTp.ptr(), dTp.plane_stride, dTp.ra, H._p(dT32), H._p(tmp), F, int(rpg), c.var_grads[L.bname].data_ptr(), 1.0,
+           tag="bn1_bwd_apply_planes_kernel", work=4.0 * R * F * 3)
+    # the products in the order of _conv_bwd_products (data gradient first, weight gradient on the side stream), on the plane GEMM
+    dx, bx = c.grad_w(x)
+    if dx is not None:
+        wd = prepared(("w", Wx.data_ptr()))                                  # (Cin rows, F channels)
+        if wd is None:
+            wd = c.new_planes(Wx.shape[0], F, "w").fill_from(Wx)
+        PL.gemm(PL.KC, dTp, wd, dx, beta=bx)                                 # dx (+)= dT W^T
+    with c.off_critical_path(dTp.buf, sc, rows=R):
+        PL.gemm(PL.TR, L.xp, dTp, _dWx(c, L), beta=1.0, ws=c.workspace())  # dW += x^T dT
+    if dgb is not None:                                                     # tf.tile^T: sum over the cloud
+        if not fused_gsum:
+            tmp = torch.empty_like(gbias)
+            H.call("dgcnn_group_colsum_f32", dT32.data_ptr(), F, gbias.shape[0], rpg, F, tmp.data_ptr())
+        H.call("dgcnn_axpby_f32", tmp.data_ptr(), 1.0, dgb.data_ptr(), 1.0, tmp.numel())
+
+
+def _conv_gmax(c, L, gmax, keys, per_cloud=False):
+    """model.py:76-77 max_pool over the points of each cloud, on the GEMM output: z = relu((t - mean) rstd + beta) is
+    non-decreasing in t, so max_n z[n] = z(max_n t[n]) and the first arg-max of t is an arg-max of z.  per_cloud: mean / rstd are
+    (nseg, F) tables, every cloud's maxima are normalised with its own row."""
+    x, T, F, out, seg = L.x, L.T, L.F, L.out, L.seg
     Bc, Nc = (seg.nseg, 0) if seg is not None else gmax
     graw = torch.empty((Bc, F), dtype=torch.float32, device=x.device)
     arg = torch.empty((Bc, F), dtype=torch.int32, device=x.device)
@@ -1145,8 +1186,12 @@ def conv_bn_act(x, leaf_scope, num_outputs, relu=True, out=None, out2=None, gbia
     else:
         H.call("dgcnn_global_max_f32", T.data_ptr(), F, Bc, Nc, F, graw.data_ptr(), arg.data_ptr())
     g = c.new_buffer(Bc, F)
-    H.call("dgcnn_bn_act_kreduce_f32", graw.data_ptr(), Bc, 1, F, mean.data_ptr(), rstd.data_ptr(), beta.data_ptr(),
-           int(relu), g.data_ptr(), F, 0, 0, 0, 0, 0)
+    if per_cloud:
+        H.call("dgcnn_seg_bn_act_f32", graw.data_ptr(), F, Bc, F, None, L.mean.data_ptr(), L.rstd.data_ptr(), L.beta.data_ptr(),
+               int(L.relu), g.data_ptr(), F, None, 0)
+    else:
+        H.call("dgcnn_bn_act_kreduce_f32", graw.data_ptr(), Bc, 1, F, L.mean.data_ptr(), L.rstd.data_ptr(), L.beta.data_ptr(),
+               int(L.relu), g.data_ptr(), F, 0, 0, 0, 0, 0)
     if c.recording:
         def bwd_g():
             dg_, dout = c.grad(g), c.grad(out)
@@ -1158,28 +1203,30 @@ def conv_bn_act(x, leaf_scope, num_outputs, relu=True, out=None, out2=None, gbia
             else:
                 H.call("dgcnn_global_max_bwd_f32", dg_.data_ptr(), arg.data_ptr(), Bc, Nc, F, dout.data_ptr(), H.ld2(dout))
         c.tape.append(bwd_g)
-    return out, g
+    return g
 
 
-def _conv_bn_act_per_cloud(c, x, Wx, beta, F, relu, out, out2, gbias, rgrp, arith, gmax, drop_keep, seg, wname, w_rows, bname):
+def _conv_bn_act_per_cloud(c, L, rgrp, gmax):
     """conv_bn_act of a packed tower with per-cloud BatchNorm.  The GEMM runs WITHOUT epilogue statistics (a row
     tile straddles clouds; the per-cloud bias through the row -> cloud map stays); then the per-cloud sums of T in a fixed
     order, the (nseg, F) tables and the apply pass that picks the table row of the row's cloud.  gmax: the per-cloud maxima of T
     are normalised with their own cloud's table row -- BN + ReLU are monotone per cloud, so the max-pool identity holds.
     Recording (seg.bn_per_cloud_train): one tape closure -- per-cloud sum dz / sum dz xhat (both gradient inputs read in place),
-    the c1 / c2 tables (+ dbeta), dT in place of T, then the dense branch's products: dx first, dW on the side stream, the
-    per-cloud bias gradient (mathematically 0 per cloud -- the literal form, as the forward keeps the bias in T)."""
+    the c1 / c2 tables (+ dbeta), dT in place of T, then the dense branch's products (_conv_bwd_products; the per-cloud bias
+    gradient is mathematically 0 per cloud -- the literal form, as the forward keeps the bias in T)."""
+    x, beta, F, relu, out2, seg = L.x, L.beta, L.F, L.relu, L.out2, L.seg
     R = x.shape[0]
     dev = x.device
     off = seg.device(dev)
     rg = seg.row_group(dev)
     T = torch.empty((R, F), dtype=torch.float32, device=dev)
-    gemm(x, Wx, T, gbias=gbias, arith=arith, row_group=rgrp)
+    gemm(x, L.Wx, T, gbias=L.gbias, arith=L.arith, row_group=rgrp)
     st = torch.empty(seg.nseg * 2 * F, dtype=torch.float64, device=dev)
     ws = seg_stats_workspace(R, seg.nseg, F, dev)
     H.call("dgcnn_seg_colstats_f32", T.data_ptr(), H.ld2(T), R, F, off.data_ptr(), seg.nseg, st.data_ptr(), ws.data_ptr(), ws.numel(),
            tag="seg_colstats_kernel", work=4.0 * R * F)
     mean, rstd = seg_bn_finalize(st, seg, F, 1)
+    out = L.out
     if out is None:
         out = c.new_buffer(R, F)
     H.call("dgcnn_seg_bn_act_f32", T.data_ptr(), H.ld2(T), R, F, rg.data_ptr(), mean.data_ptr(), rstd.data_ptr(), beta.data_ptr(),
@@ -1198,42 +1245,18 @@ def _conv_bn_act_per_cloud(c, x, Wx, beta, F, relu, out, out2, gbias, rgrp, arit
                    0 if d2 is None else H.ld2(d2))
             H.call("dgcnn_seg_bn_bwd_reduce_f32", T.data_ptr(), H.ld2(T), R, F, off.data_ptr(), seg.nseg, *par, red.data_ptr(),
                    wsb.data_ptr(), wsb.numel(), tag="seg_bn_bwd_reduce_kernel", work=4.0 * R * F * (1 + nsrc))
-            c1, c2 = seg_bn_bwd_finalize(red, seg, F, 1, c.var_grads[bname])
+            c1, c2 = seg_bn_bwd_finalize(red, seg, F, 1, c.var_grads[L.bname])
             H.call("dgcnn_seg_bn_bwd_apply_f32", T.data_ptr(), H.ld2(T), R, F, rg.data_ptr(), *par, c1.data_ptr(), c2.data_ptr(),
                    T.data_ptr(), H.ld2(T), tag="seg_bn_bwd_apply_kernel", work=4.0 * R * F * (2 + nsrc))
-            dT = T
-            dWx = c.var_grads[wname] if w_rows is None else c.var_grads[wname][w_rows[0]:w_rows[1]]
-            dgb = c.grad(gbias) if gbias is not None else None
-            dx, bx = c.grad_w(x)
-            if dx is not None:
-                gemm(dT, Wx, dx, transB=True, beta=bx, arith=arith)    # dx (+)= dT W^T: on the critical path, first
-            with c.off_critical_path(rows=R):
-                gemm(x, dT, dWx, transA=True, beta=1.0, arith=arith)   # dW += x^T dT
-            if dgb is not None:                                         # tf.tile^T: sum over the cloud
-                tmp = torch.empty_like(gbias)
-                seg_colsum(dT, seg, tmp)
-                H.call("dgcnn_axpby_f32", tmp.data_ptr(), 1.0, dgb.data_ptr(), 1.0, tmp.numel())
+            _conv_bwd_products(c, L, T, c.grad(L.gbias) if L.gbias is not None else None)
         c.tape.append(bwd)
     if gmax is None:
-        return out if drop_keep is None else dropout(out, drop_keep)
+        return out if L.drop_keep is None else dropout(out, L.drop_keep)
     keys = c.stats_raw(seg.nseg * F)                                          # zeroed uint64[nseg][F]
     H.call("dgcnn_colmax_seg_f32", T.data_ptr(), H.ld2(T), R, F, off.data_ptr(), seg.nseg, keys.data_ptr(),
            tag="colmax_seg_kernel", work=4.0 * R * F)
-    graw = torch.empty((seg.nseg, F), dtype=torch.float32, device=dev)
-    arg = torch.empty((seg.nseg, F), dtype=torch.int32, device=dev)
-    H.call("dgcnn_colmax_decode_f32", keys.data_ptr(), seg.nseg * F, graw.data_ptr(), arg.data_ptr())
-    g = c.new_buffer(seg.nseg, F)
-    H.call("dgcnn_seg_bn_act_f32", graw.data_ptr(), F, seg.nseg, F, None, mean.data_ptr(), rstd.data_ptr(), beta.data_ptr(),
-           int(relu), g.data_ptr(), F, None, 0)
-    if c.recording:
-        def bwd_g():
-            dg_, dout = c.grad(g), c.grad(out)
-            if dg_ is None or dout is None:
-                return
-            H.call("dgcnn_global_max_bwd_seg_f32", dg_.data_ptr(), arg.data_ptr(), off.data_ptr(), seg.nseg, F, dout.data_ptr(),
-                   H.ld2(dout))
-        c.tape.append(bwd_g)
-    return out, g
+    L.T, L.out, L.mean, L.rstd = T, out, mean, rstd
+    return out, _conv_gmax(c, L, gmax, keys, per_cloud=True)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -1329,26 +1352,232 @@ def build_csr(idx, B, N, k, side=None):
     return off, (rev if srt is None else srt)
 
 
-def _edge_conv_record_per_cloud(c, x, C, k, F, seg, idx, esrc, UV, Cp, xg, wcat, mean, rstd, beta0, w0name, b0name, mm):
-    """conv0's BN + ReLU + max / mean of a packed tower with per-cloud statistics, inside a recording: the forward pass that also
-    keeps the packed tie / positive counts, and the tape closure -- per-cloud sums from the per-point outputs (no pass over the
-    edges), the c1 / c2 tables (+ dbeta), dY and dU = sum_m dY, dV = the incoming sum, then the gather branch's tail
-    (dx += [dU | dV] Wcat^T, dWcat = X^T [dU | dV] on the side stream).  UV stays referenced: esrc holds raw pointers into it."""
-    R = x.shape[0]
+def _csr_ahead(c, L):
+    """The transposed adjacency depends only on idx: built during the forward, off the critical path (None: no side stream)."""
+    if WGRAD_SIDE_STREAM and L.R >= SIDE_STREAM_MIN_ROWS:
+        return build_csr(L.idx, L.B, L.N, L.k, side=(c, L.R))
+    return None
+
+
+def _incoming_sum(L, dY, S, csr=None):
+    """tf.gather^T as a gather: bucket the edges by target (csr: built on the side stream during the forward), then every point
+    sums its incoming dY rows (fp32 or bf16) into S (None: a fresh (R, F), allocated behind the adjacency).  Returns S."""
+    R, k, F = L.R, L.k, L.F
+    off, rev = csr if csr is not None else build_csr(L.idx, L.B, L.N, k)
+    if S is None:
+        S = torch.empty((R, F), dtype=torch.float32, device=dY.device)
+    if dY.dtype == torch.bfloat16:
+        H.call("dgcnn_edge_gather_sum_bf16", dY.data_ptr(), off.data_ptr(), rev.data_ptr(), R, F, S.data_ptr(), H.ld2(S),
+               tag="csr_gather_sum_kernel<bf16>", work=2.0 * R * k * F + 4.0 * R * F)
+    else:
+        H.call("dgcnn_edge_gather_sum_f32", dY.data_ptr(), off.data_ptr(), rev.data_ptr(), R, F, S.data_ptr(), H.ld2(S),
+               tag="csr_gather_sum_kernel", work=4.0 * (R * k * F + R * F))
+    return S
+
+
+def _centre_weight(W0, C, F, bf16=False):
+    """(wd, W): the centre weight wd = W[:C] - W[C:] of E = [x_i, x_j - x_i], a fresh (C, F); W = W0, or with bf16 a copy of W0
+    rounded to bf16 (never W0 itself: a variable)."""
+    W = W0
+    if bf16:
+        W = torch.empty_like(W0)
+        H.call("dgcnn_round_bf16_f32", W0.data_ptr(), W.data_ptr(), W0.numel())
+    wd = torch.empty((C, F), dtype=torch.float32, device=W0.device)
+    H.call("dgcnn_copy2d_f32", W[:C].data_ptr(), F, wd.data_ptr(), F, C, F, 0)
+    H.call("dgcnn_axpby_f32", W[C:].data_ptr(), -1.0, wd.data_ptr(), 1.0, C * F)
+    return wd, W
+
+
+def _edge_dx(L, dx, dysum, dY, bf16=False, wd=None):
+    """dx from the edge gradients dY (dysum = sum_m dY).  dE = dY W^T never exists: the transpose of `edges` is linear, so
+      dx_i += (sum_m dY) (W[:C] - W[C:])^T        dx_j += (sum of the dY rows of the edges that point at j) W[C:]^T
+    -- the same sums of the same products as the literal edge-level product + scatter-add, taken at the points (k times fewer
+    MACs, no atomics).  bf16: W = bf16(W0), dY on the bf16 grid; the point-level products run in the exact arithmetic.
+    wd: the centre weight where the forward kept it.  F % 4 != 0: the second term as the edge-level product + scatter."""
+    C, F, W = L.C, L.F, L.W0
+    if wd is None:
+        wd, W = _centre_weight(W, C, F, bf16)
+    gemm(dysum, wd, dx, transB=True, beta=1.0)
+    if F % 4 != 0:
+        if bf16:
+            raise H.HipError("bf16 edge-MLP: the input gradient needs filter counts that are multiples of 4 (F = %d)" % F)
+        H.call("dgcnn_edge_mlp_dgrad_scatter_f32", dY.data_ptr(), W.data_ptr(), L.idx.data_ptr(), L.B, L.N, C, L.k,
+               F, dx.data_ptr(), H.ld2(dx),
+               tag="gemm_kernel<A_ROW,B_COL,SCATTER,%d,%d>" % (_tile_m(L.R * L.k, C), 64 if C <= 64 else 128),
+               work=2.0 * L.R * L.k * C * F)
+        return
+    # (an fp32 dY's sum is allocated before the adjacency is built, a bf16 dY's behind it: the order either route always had)
+    S = None if dY.dtype == torch.bfloat16 else torch.empty((L.R, F), dtype=torch.float32, device=dx.device)
+    gemm(_incoming_sum(L, dY, S), W[C:], dx, transB=True, beta=1.0)
+
+
+def _edge_outputs(c, L, outs):
+    if outs is None:
+        L.mm, L.net_out = c.new_buffer(L.R, 2 * L.F), None
+    else:
+        L.mm, L.net_out = outs
+    L.mx, L.mn = L.mm[:, :L.F], L.mm[:, L.F:]
+
+
+def _edge_finalize(c, L, st, outs):
+    """conv0's BatchNorm statistics are complete: mean / rstd, the output buffers, the backward's counts."""
+    L.mean, L.rstd = bn_finalize(st, L.F, L.R * L.k)                    # ops.py:53
+    c.pop_slots()
+    _edge_outputs(c, L, outs)
+    L.cnt = torch.empty((L.R, L.F), dtype=torch.float32, device=L.x.device) if c.recording else None   # ties of the max
+
+
+def _edge_bn_act_y(L):
+    R, k, F, mx, mn = L.R, L.k, L.F, L.mx, L.mn
+    H.call("dgcnn_bn_act_kreduce_f32", L.Y.data_ptr(), R, k, F, L.mean.data_ptr(), L.rstd.data_ptr(), L.beta0.data_ptr(), 1,
+           mx.data_ptr(), H.ld2(mx), mn.data_ptr(), H.ld2(mn), 0, 0, H._p(L.cnt),
+           tag="bn_act_kreduce_kernel", work=4.0 * (R * k * F + 2 * R * F))   # ops.py:54-58
+
+
+def _edge_bwd_inputs(c, L):
+    """(d(max), d(mean), zeroed sums) of a conv0 backward, or None when nobody wants the layer's gradient."""
+    dmm = c.grad(L.mm)
+    if dmm is None:
+        return None
+    return dmm[:, :L.F], dmm[:, L.F:], c.stats(L.F)
+
+
+def _edge_reduce_points(L, dmx, dmn, red):
+    """sum dz, sum dz*xhat from the forward's per-point outputs alone (bn.hip): no pass over the edges."""
+    mx, mn, R, F = L.mx, L.mn, L.R, L.F
+    H.call("dgcnn_edge_bn_bwd_reduce_points_f32", mx.data_ptr(), H.ld2(mx), mn.data_ptr(), H.ld2(mn),
+           L.cnt.data_ptr(), dmx.data_ptr(), H.ld2(dmx), dmn.data_ptr(), H.ld2(dmn), L.beta0.data_ptr(), R, L.k, F,
+           red.data_ptr(), tag="edge_bwd_reduce_points_kernel", work=4.0 * 5 * R * F)
+
+
+def _edge_bn_bwd_reduce_y(L, dmx, dmn, red):
+    R, k, F = L.R, L.k, L.F
+    bn_bwd_reduce(L.Y, R, k, F, L.mean, L.rstd, L.beta0, 1, dmx, dmn, L.mx, L.cnt, red,
+                  tag="bn_bwd_reduce_kernel", work=4.0 * (R * k * F + 2 * R * F))
+
+
+def _edge_bn_bwd_apply_y(c, L, dmx, dmn, red, dysum, relu=1):
+    """dY in place of the materialised Y (+ dysum = sum_m dY where asked for, dbeta)."""
+    Y, R, k, F, mx = L.Y, L.R, L.k, L.F, L.mx
+    H.call("dgcnn_bn_bwd_apply_f32", Y.data_ptr(), R, k, F, L.mean.data_ptr(), L.rstd.data_ptr(), L.beta0.data_ptr(),
+           relu, dmx.data_ptr(), H.ld2(dmx), dmn.data_ptr(), H.ld2(dmn), mx.data_ptr(), H.ld2(mx), L.cnt.data_ptr(),
+           red.data_ptr(), Y.data_ptr(),
+           H._p(dysum), 0 if dysum is None else H.ld2(dysum), c.var_grads[L.b0name].data_ptr(), 1.0,
+           tag="bn_bwd_apply_kernel", work=4.0 * (2 * R * k * F + 3 * R * F))
+
+
+def _conv0_fold(c, L, st, outs, virtual):
+    """conv0 is linear: E W0 = x_i (Wa-Wb) + x_j Wb = U[i] + V[j] with [U | V] = X [Wa-Wb | Wb] -- ONE point-level GEMM (k times
+    fewer MACs than the edge tensor product), then a per-edge gather-add that takes the BatchNorm column sums and, unless
+    `virtual`, writes Y (it is then bound by that HBM write).  C = 3 (raw coordinates): _point_gemm pads the reduction dimension
+    to 4 so that the point-level GEMMs take the float4 path (the generic scalar kernel costs ~10x more on them)."""
+    R, k, F = L.R, L.k, L.F
+    L.Y = None if virtual else torch.empty((R * k, F), dtype=torch.float32, device=L.x.device)
+    L.Cp, L.xg, L.wcat, L.UV = _point_gemm(c, L.x, L.W0, R, L.C, F)
+    L.esrc = (L.UV[:, F:].data_ptr(), 2 * F, L.UV.data_ptr(), 2 * F, L.idx.data_ptr(), L.B, L.N, k, F)
+    H.call("dgcnn_edge_gather_add_f32", *L.esrc, H._p(L.Y), st.data_ptr(),
+           tag="edge_gather_add_kernel", work=4.0 * ((0 if virtual else R * k * F) + 2 * R * F) + 4.0 * R * k,
+           nbytes=4.0 * (R * k * F + R * F))   # ops.py:21-52   (nbytes: rows gathered from L2 -- bench.py's l2-gather roof)
+    if not virtual:
+        L.UV = L.esrc = None
+    _edge_finalize(c, L, st, outs)
+    if virtual:
+        # esrc holds raw pointers into UV: L.UV keeps it alive for the backward
+        H.call("dgcnn_edge_bn_act_kreduce_f32", *L.esrc, L.mean.data_ptr(), L.rstd.data_ptr(), L.beta0.data_ptr(), 1,
+               L.mx.data_ptr(), H.ld2(L.mx), L.mn.data_ptr(), H.ld2(L.mn), H._p(L.cnt),
+               tag="bn_act_kreduce_kernel<edge>", work=4.0 * (4 * R * F) + 4.0 * R * k, nbytes=4.0 * (R * k * F + R * F))   # ops.py:54-58
+    else:
+        _edge_bn_act_y(L)
+    if not c.recording:
+        return
+    fv = F // 4
+    fused_l0 = (virtual and EDGE_BWD_FUSED_L0 and L.C <= 4 and F % 4 == 0 and fv & (fv - 1) == 0 and fv <= 256 and
+                not c.tracked(L.x))
+    _record(c, _conv0_fold_bwd, L, None if fused_l0 else _csr_ahead(c, L), fused_l0)
+
+
+def _conv0_fold_bwd(c, L, csr, fused_l0):
+    g = _edge_bwd_inputs(c, L)
+    if g is None:
+        return
+    dmx, dmn, red = g
+    x, R, k, F, mx = L.x, L.R, L.k, L.F, L.mx
+    if L.Y is None:
+        _edge_reduce_points(L, dmx, dmn, red)
+    else:
+        _edge_bn_bwd_reduce_y(L, dmx, dmn, red)
+    dx = c.grad(x)
+    if fused_l0 and dx is None:
+        # first layer (raw coordinates, nobody wants d(points)): dY is formed and consumed in one pass, straight into dW0
+        ws = c.workspace()
+        H.call("dgcnn_edge_bn_bwd_apply_wgrad_f32", *L.esrc, L.mean.data_ptr(), L.rstd.data_ptr(), L.beta0.data_ptr(),
+               dmx.data_ptr(), H.ld2(dmx), dmn.data_ptr(), H.ld2(dmn), mx.data_ptr(), H.ld2(mx), L.cnt.data_ptr(),
+               red.data_ptr(), x.data_ptr(), H.ld2(x), L.C, c.var_grads[L.w0name].data_ptr(), c.var_grads[L.b0name].data_ptr(), 1.0,
+               ws.data_ptr(), ws.numel(), tag="edge_bwd_apply_wgrad_kernel", work=4.0 * (4 * R * F) + 4.0 * R * k,
+               nbytes=4.0 * (R * k * F + R * F))
+        return
+    dUV = torch.empty((R, 2 * F), dtype=torch.float32, device=x.device)    # [dU | dV]
+    dysum = dUV[:, :F]
+    if L.Y is None:
+        assert L.UV is not None          # esrc holds raw pointers into UV: this reference keeps it alive
+        dY = torch.empty((R * k, F), dtype=torch.float32, device=x.device)
+        H.call("dgcnn_edge_bn_bwd_apply_f32", *L.esrc, L.mean.data_ptr(), L.rstd.data_ptr(), L.beta0.data_ptr(),
+               1, dmx.data_ptr(), H.ld2(dmx), dmn.data_ptr(), H.ld2(dmn), mx.data_ptr(), H.ld2(mx), L.cnt.data_ptr(),
+               red.data_ptr(), dY.data_ptr(), dysum.data_ptr(), H.ld2(dysum), c.var_grads[L.b0name].data_ptr(), 1.0,
+               tag="bn_bwd_apply_kernel<edge>", work=4.0 * (R * k * F + 7 * R * F) + 4.0 * R * k, nbytes=4.0 * (R * k * F + R * F))
+    else:
+        _edge_bn_bwd_apply_y(c, L, dmx, dmn, red, dysum)
+        dY = L.Y
+    # dU = sum_m dY, dV = sum of incoming dY;  dWcat = X^T [dU|dV],  dx += [dU|dV] Wcat^T
+    _incoming_sum(L, dY, dUV[:, F:], csr)
+    _fold_bwd_products(c, L, dUV)
+
+
+def _fold_bwd_products(c, L, dUV):
+    """dx += [dU | dV] Wcat^T on the main stream, dWcat = X^T [dU | dV] folded back into dW0 on the side stream."""
+    dwcat = torch.empty((L.Cp, 2 * L.F), dtype=torch.float32, device=dUV.device)
+    # dUV / dwcat are allocated on the main stream by the running closure: record them on the side stream,
+    # or the caching allocator may hand dUV's block to the next main-stream allocation while the side GEMM reads it
+    dx = c.grad(L.x)
+    if dx is not None:                                                  # (layer 0, raw coordinates: nobody wants d(points))
+        gemm(dUV, L.wcat[:L.C], dx, transB=True, beta=1.0, arith=None)
+    with c.off_critical_path(dwcat, dUV, rows=L.R):
+        gemm(L.xg, dUV, dwcat, transA=True, arith=None)
+        H.call("dgcnn_edge_wgrad_combine_f32", dwcat.data_ptr(), L.C, L.F, c.var_grads[L.w0name].data_ptr())
+
+
+def _conv0_per_cloud(c, L, outs):
+    """The fold with the virtual Y, BatchNorm over the edges of each cloud alone (csrc/seg_bn.hip): no statistics slots, the
+    per-cloud sums have buffers of their own.  Returns its scratch (see edge_conv_block)."""
+    x, R, k, F, seg = L.x, L.R, L.k, L.F, L.seg
     dev = x.device
+    L.Cp, L.xg, L.wcat, L.UV = _point_gemm(c, x, L.W0, R, L.C, F)       # [U | V] = X [Wa-Wb | Wb]
+    L.esrc = esrc = (L.UV[:, F:].data_ptr(), 2 * F, L.UV.data_ptr(), 2 * F, L.idx.data_ptr(), R, k, F)
+    st = torch.empty(seg.nseg * 2 * F, dtype=torch.float64, device=dev)
+    ws = seg_stats_workspace(R, seg.nseg, F, dev)
+    H.call("dgcnn_seg_edge_stats_f32", *esrc, seg.device(dev).data_ptr(), seg.nseg, st.data_ptr(), ws.data_ptr(), ws.numel(),
+           tag="seg_edge_stats_kernel", work=4.0 * (2 * R * F) + 4.0 * R * k, nbytes=4.0 * (R * k * F + R * F))
+    L.mean, L.rstd = seg_bn_finalize(st, seg, F, k)                     # ops.py:53, count n_b * k
+    _edge_outputs(c, L, outs)
+    if not c.recording:
+        H.call("dgcnn_seg_edge_bn_act_kreduce_f32", *esrc, seg.row_group(dev).data_ptr(), L.mean.data_ptr(), L.rstd.data_ptr(),
+               L.beta0.data_ptr(), 1, L.mx.data_ptr(), H.ld2(L.mx), L.mn.data_ptr(), H.ld2(L.mn),
+               tag="seg_edge_bn_act_kreduce_kernel", work=4.0 * (4 * R * F) + 4.0 * R * k, nbytes=4.0 * (R * k * F + R * F))   # ops.py:54-58
+        return st, ws
+    # inside a recording: the forward pass that also keeps the packed tie / positive counts, and the tape closure -- per-cloud sums
+    # from the per-point outputs (no pass over the edges), the c1 / c2 tables (+ dbeta), dY and dU = sum_m dY, dV = the incoming
+    # sum, then the fold's products.  L.UV stays referenced: esrc holds raw pointers into it.
+    mean, rstd, beta0, mx, mn = L.mean, L.rstd, L.beta0, L.mx, L.mn
     off, rg = seg.device(dev), seg.row_group(dev)
-    mx, mn = mm[:, :F], mm[:, F:]
     cnt = torch.empty((R, F), dtype=torch.float32, device=dev)             # ties of the max + 256 * positives
     H.call("dgcnn_seg_edge_bn_act_kreduce_cnt_f32", *esrc, rg.data_ptr(), mean.data_ptr(), rstd.data_ptr(), beta0.data_ptr(), 1,
            mx.data_ptr(), H.ld2(mx), mn.data_ptr(), H.ld2(mn), cnt.data_ptr(),
            tag="seg_edge_bn_act_kreduce_kernel<cnt>", work=4.0 * (5 * R * F) + 4.0 * R * k, nbytes=4.0 * (R * k * F + R * F))   # ops.py:54-58
-    csr = None
-    if WGRAD_SIDE_STREAM and R >= SIDE_STREAM_MIN_ROWS:
-        csr = build_csr(idx, 1, R, k, side=(c, R))      # depends on idx only: built now, off the critical path
+    csr = _csr_ahead(c, L)
 
     def bwd():
-        assert UV is not None
-        dmm = c.grad(mm)
+        assert L.UV is not None
+        dmm = c.grad(L.mm)
         if dmm is None:
             return
         dmx, dmn = dmm[:, :F], dmm[:, F:]
@@ -1357,25 +1586,173 @@ def _edge_conv_record_per_cloud(c, x, C, k, F, seg, idx, esrc, UV, Cp, xg, wcat,
         H.call("dgcnn_seg_edge_bn_bwd_reduce_points_f32", mx.data_ptr(), H.ld2(mx), mn.data_ptr(), H.ld2(mn), cnt.data_ptr(),
                dmx.data_ptr(), H.ld2(dmx), dmn.data_ptr(), H.ld2(dmn), beta0.data_ptr(), R, k, F, off.data_ptr(), seg.nseg,
                red.data_ptr(), wsb.data_ptr(), wsb.numel(), tag="seg_edge_bwd_reduce_points_kernel", work=4.0 * 5 * R * F)
-        c1, c2 = seg_bn_bwd_finalize(red, seg, F, k, c.var_grads[b0name])
+        c1, c2 = seg_bn_bwd_finalize(red, seg, F, k, c.var_grads[L.b0name])
         dUV = torch.empty((R, 2 * F), dtype=torch.float32, device=dev)     # [dU | dV]
         dY = torch.empty((R * k, F), dtype=torch.float32, device=dev)
         H.call("dgcnn_seg_edge_bn_bwd_apply_f32", *esrc, rg.data_ptr(), mean.data_ptr(), rstd.data_ptr(), beta0.data_ptr(), 1,
                dmx.data_ptr(), H.ld2(dmx), dmn.data_ptr(), H.ld2(dmn), mx.data_ptr(), H.ld2(mx), cnt.data_ptr(), c1.data_ptr(),
                c2.data_ptr(), dY.data_ptr(), dUV.data_ptr(), 2 * F, tag="seg_edge_bn_bwd_apply_kernel",
                work=4.0 * (R * k * F + 7 * R * F) + 4.0 * R * k, nbytes=4.0 * (R * k * F + R * F))
-        offt, rev = csr if csr is not None else build_csr(idx, 1, R, k)
-        S = dUV[:, F:]
-        H.call("dgcnn_edge_gather_sum_f32", dY.data_ptr(), offt.data_ptr(), rev.data_ptr(), R, F, S.data_ptr(), H.ld2(S),
-               tag="csr_gather_sum_kernel", work=4.0 * (R * k * F + R * F))
-        dwcat = torch.empty((Cp, 2 * F), dtype=torch.float32, device=dev)
-        dx = c.grad(x)
-        if dx is not None:                                                  # (layer 0, raw coordinates: nobody wants d(points))
-            gemm(dUV, wcat[:C], dx, transB=True, beta=1.0, arith=None)
-        with c.off_critical_path(dwcat, dUV, rows=R):
-            gemm(xg, dUV, dwcat, transA=True, arith=None)
-            H.call("dgcnn_edge_wgrad_combine_f32", dwcat.data_ptr(), C, F, c.var_grads[w0name].data_ptr())
+        adj = csr if csr is not None else build_csr(L.idx, 1, R, k)
+        _incoming_sum(L, dY, dUV[:, F:], adj)
+        _fold_bwd_products(c, L, dUV)
     c.tape.append(bwd)
+    return st, ws
+
+
+def _conv0_bf16_fused(c, L, st, outs, one_pass):
+    """csrc/edge_mlp_bf16.hip: E = [x_i, x_j - x_i] gathered, rounded and multiplied tile by tile on the bf16 MFMA pipe;
+    neither E nor y is written: one pass takes the BatchNorm sums, the next one recomputes y for BN + ReLU + max / mean.
+    one_pass: the backward in one pass over the edges (8 <= k <= 128): the forward then packs (#ties, #positives) as the fp32 edge
+    kernels do.  Otherwise the backward forms Y again and goes the way of the forms that wrote it (_conv0_dense_y_bwd)."""
+    R, C, k, F, bsrc = L.R, L.C, L.k, L.F, L.bsrc
+    H.call("dgcnn_edge_mlp_bf16_stats", *bsrc, st.data_ptr(), tag="edge_mlp_bf16_kernel<stats>",
+           work=2.0 * R * k * 2 * C * F, nbytes=4.0 * (R * k * C + R * C))
+    _edge_finalize(c, L, st, outs)
+    mx, mn = L.mx, L.mn
+    H.call("dgcnn_edge_mlp_bf16_bn_kreduce", *bsrc, L.mean.data_ptr(), L.rstd.data_ptr(), L.beta0.data_ptr(),
+           mx.data_ptr(), H.ld2(mx), mn.data_ptr(), H.ld2(mn), H._p(L.cnt), 1 if one_pass else 0,
+           tag="edge_mlp_bf16_kernel<bn_kreduce>", work=2.0 * R * k * 2 * C * F, nbytes=4.0 * (R * k * C + R * C))   # ops.py:53-58
+    if c.recording:
+        _record(c, _conv0_bf16_one_pass_bwd if one_pass else _conv0_dense_y_bwd, L)
+
+
+def _conv0_bf16_one_pass_bwd(c, L):
+    """Sums of the BatchNorm backward from the forward's per-point outputs, then ONE pass over the edges that recomputes y, forms
+    dY (rounded to bf16), takes dW0 = E^T dY on the matrix pipe and leaves dY as bf16 for the transposed-adjacency sum -- E, y
+    and an fp32 dY are never written."""
+    g = _edge_bwd_inputs(c, L)
+    if g is None:
+        return
+    dmx, dmn, red = g
+    x, R, C, k, F, mx = L.x, L.R, L.C, L.k, L.F, L.mx
+    _edge_reduce_points(L, dmx, dmn, red)
+    dx = c.grad(x)
+    dYb = dysum = None
+    if dx is not None:
+        dYb = torch.empty((R * k, F), dtype=torch.bfloat16, device=x.device)
+        dysum = torch.empty((R, F), dtype=torch.float32, device=x.device)
+    ws = c.workspace()
+    H.call("dgcnn_edge_mlp_bf16_bwd", *L.bsrc, L.mean.data_ptr(), L.rstd.data_ptr(), L.beta0.data_ptr(), mx.data_ptr(), H.ld2(mx),
+           L.cnt.data_ptr(), dmx.data_ptr(), H.ld2(dmx), dmn.data_ptr(), H.ld2(dmn), red.data_ptr(), H._p(dYb), H._p(dysum),
+           F, c.var_grads[L.w0name].data_ptr(), c.var_grads[L.b0name].data_ptr(), 1.0, ws.data_ptr(), ws.numel(),
+           tag="edge_mlp_bf16_kernel<bwd>", work=2.0 * R * k * 2 * C * F * 2, nbytes=4.0 * (R * k * C + R * C))
+    if dx is not None:
+        _edge_dx(L, dx, dysum, dYb, bf16=True)
+
+
+def _bf16_operands(L):
+    """The literal edge tensor in fp32 (the difference x_j - x_i BEFORE any rounding; channels padded to a multiple of 4 so
+    that the products take the float4 path) and the matching weight rows -- the operands the bf16 products round.
+    dgcnn_gemm_f32 rounds its operands (arith = 1) only on its float4 path with N > 4 (include/dgcnn_hip.h); where the products
+    E W0 and E^T dY (both N = F) will not take it, E and the weight are rounded here instead: rounded values are bf16 values, so
+    the fp32 product of them is the mode's arithmetic.  (Rounding is idempotent: the other shapes see the same bits as before.)"""
+    x, W0, R, C, Cp, k, F = L.x, L.W0, L.R, L.C, L.Cp, L.k, L.F
+    xg, Wp = x, W0
+    if Cp != C:
+        xg = H.zeros((R, Cp), torch.float32, x.device)
+        H.call("dgcnn_copy2d_f32", x.data_ptr(), H.ld2(x), xg.data_ptr(), Cp, R, C, 0)
+        Wp = H.zeros((2 * Cp, F), torch.float32, x.device)
+        H.call("dgcnn_copy2d_f32", W0[:C].data_ptr(), F, Wp[:C].data_ptr(), F, C, F, 0)
+        H.call("dgcnn_copy2d_f32", W0[C:].data_ptr(), F, Wp[Cp:Cp + C].data_ptr(), F, C, F, 0)
+    E_ = torch.empty((R * k, 2 * Cp), dtype=torch.float32, device=x.device)
+    H.call("dgcnn_edge_gather_f32", xg.data_ptr(), H.ld2(xg), L.idx.data_ptr(), L.B, L.N, Cp, k, E_.data_ptr())   # ops.py:21-40
+    if not (F % 4 == 0 and F > 4 and H.ld2(Wp) % 4 == 0 and Wp.data_ptr() % 16 == 0):
+        H.call("dgcnn_round_bf16_f32", E_.data_ptr(), E_.data_ptr(), E_.numel())
+        Wr = torch.empty((Wp.shape[0], F), dtype=torch.float32, device=x.device)      # (never W0 itself: a variable)
+        Wc = Wp.contiguous()
+        H.call("dgcnn_round_bf16_f32", Wc.data_ptr(), Wr.data_ptr(), Wr.numel())
+        Wp = Wr
+    return E_, Wp
+
+
+def _conv0_dense_y(c, L, st, outs):
+    """conv0 written out as Y (R*k, F), L.kind one of
+      "bf16"     shapes the fused bf16 kernels do not take: the edge tensor in fp32, then ONE product whose operands the GEMM rounds
+                 to bf16 (arith = 1: v_cvt_pk_bf16_f32, round to nearest even) with fp32 accumulation on the bf16 MFMA pipe
+      "literal"  the (B*N*k) x 2C product over E = [x_i, x_j - x_i], the gather fused into the GEMM's loads
+      "nbr"      factored conv0, edge-level form (kept for odd F and as a cross-check): centre term once per point (U); the
+                 per-edge (B*N*k) x C GEMM gathers the neighbour rows and adds U[point] in its epilogue
+    then BatchNorm streams Y.  The members differ only in how Y and dW0 are produced.  Returns the forward's scratch."""
+    x, W0, R, C, k, F, idx = L.x, L.W0, L.R, L.C, L.k, L.F, L.idx
+    L.Y = Y = torch.empty((R * k, F), dtype=torch.float32, device=x.device)
+    U = None
+    edge_tag = "gemm_kernel<A_EDGE,B_ROW,STORE,%d,%d>" % (_tile_m(R * k, F), 64 if F <= 64 else 128)
+    if L.kind == "bf16":
+        L.Ee, L.W0p = _bf16_operands(L)
+        gemm(L.Ee, L.W0p, Y, stats=None if DETERMINISTIC else st, arith=1)                                      # ops.py:47-52
+    elif L.kind == "literal":
+        H.call("dgcnn_edge_mlp_f32", x.data_ptr(), H.ld2(x), idx.data_ptr(), W0.data_ptr(), L.B, L.N, C, k, F,
+               Y.data_ptr(), 0 if DETERMINISTIC else st.data_ptr(), tag=edge_tag,
+               work=2.0 * R * k * 2 * C * F)                            # ops.py:21-52 (gather fused)
+    else:
+        L.wd, _ = _centre_weight(W0, C, F)
+        U = torch.empty((R, F), dtype=torch.float32, device=x.device)
+        gemm(x, L.wd, U)
+        H.call("dgcnn_edge_nbr_gemm_f32", x.data_ptr(), H.ld2(x), idx.data_ptr(), W0[C:].data_ptr(), U.data_ptr(), F,
+               L.B, L.N, C, k, F, Y.data_ptr(), 0 if DETERMINISTIC else st.data_ptr(), tag=edge_tag,
+               work=2.0 * R * k * C * F)                                # ops.py:21-52 (gather fused)
+    if DETERMINISTIC:
+        colstats_det(Y, st)
+    if not c.recording:
+        L.Ee = None
+    _edge_finalize(c, L, st, outs)
+    _edge_bn_act_y(L)
+    if c.recording:
+        _record(c, _conv0_dense_y_bwd, L)
+    return U
+
+
+def _conv0_dense_y_bwd(c, L):
+    g = _edge_bwd_inputs(c, L)
+    if g is None:
+        return
+    dmx, dmn, red = g
+    x, R, C, Cp, k, F, idx, kind = L.x, L.R, L.C, L.Cp, L.k, L.F, L.idx, L.kind
+    recompute = L.Y is None
+    if recompute:
+        # the fused bf16 forward wrote neither E nor y: both are formed again for the backward (y by the SAME instruction sequence,
+        # so the recomputed z compares equal to the maxima the forward took), used by the passes below and dropped
+        L.Y = torch.empty((R * k, F), dtype=torch.float32, device=x.device)
+        H.call("dgcnn_edge_mlp_bf16", *L.bsrc, L.Y.data_ptr(), tag="edge_mlp_bf16_kernel<write>",
+               work=2.0 * R * k * 2 * C * F, nbytes=4.0 * (R * k * C + R * C))
+        L.Ee, L.W0p = _bf16_operands(L)
+    _edge_bn_bwd_reduce_y(L, dmx, dmn, red)
+    dx = c.grad(x)
+    dysum = None
+    if dx is not None or kind == "nbr":
+        dysum = torch.empty((R, F), dtype=torch.float32, device=x.device)
+    _edge_bn_bwd_apply_y(c, L, dmx, dmn, red, dysum, relu=3 if kind == "bf16" else 1)
+    dY = L.Y
+    ws = c.workspace()
+    dW0 = c.var_grads[L.w0name]
+    wgrad_tag = "edge_wgrad_smallc_kernel" if C <= 4 else "gemm_kernel<A_EDGE_T,B_ROW,STORE,128,%d>" % (64 if F <= 64 else 128)
+    if kind == "bf16":
+        # dW0 = E^T dY with bf16 operands: E and W0 rounded as in the forward; dY was written on the bf16 grid by the
+        # apply pass (relu flag 3), so the product's own rounding (arith = 1) leaves it unchanged
+        if L.W0p is L.W0:
+            gemm(L.Ee, dY, dW0, transA=True, beta=1.0, arith=1)
+        else:
+            dWp = torch.empty_like(L.W0p)
+            gemm(L.Ee, dY, dWp, transA=True, arith=1)
+            H.call("dgcnn_copy2d_f32", dWp[:C].data_ptr(), F, dW0[:C].data_ptr(), F, C, F, 1)
+            H.call("dgcnn_copy2d_f32", dWp[Cp:Cp + C].data_ptr(), F, dW0[C:].data_ptr(), F, C, F, 1)
+    elif kind == "literal":
+        H.call("dgcnn_edge_mlp_wgrad_f32", x.data_ptr(), H.ld2(x), idx.data_ptr(), dY.data_ptr(), L.B, L.N, C, k, F,
+               dW0.data_ptr(), 1.0, ws.data_ptr(), ws.numel(), tag=wgrad_tag, work=2.0 * R * k * 2 * C * F)
+    else:
+        # dW0[C:] += sum_e x_j^T dY  -  X^T dYsum ;  dW0[:C] += X^T dYsum   (W0[:C]-W0[C:] and W0[C:] are the
+        # factors of the forward: d(Wa-Wb) = X^T dYsum, dWb = edge part)
+        H.call("dgcnn_edge_nbr_wgrad_f32", x.data_ptr(), H.ld2(x), idx.data_ptr(), dY.data_ptr(), L.B, L.N, C, k, F,
+               dW0[C:].data_ptr(), 1.0, ws.data_ptr(), ws.numel(), tag=wgrad_tag, work=2.0 * R * k * C * F)
+        dwd = torch.empty((C, F), dtype=torch.float32, device=x.device)
+        gemm(x, dysum, dwd, transA=True)
+        H.call("dgcnn_axpby_f32", dwd.data_ptr(), 1.0, dW0[:C].data_ptr(), 1.0, C * F)
+        H.call("dgcnn_axpby_f32", dwd.data_ptr(), -1.0, dW0[C:].data_ptr(), 1.0, C * F)
+    if dx is not None:
+        _edge_dx(L, dx, dysum, dY, bf16=kind == "bf16", wd=L.wd)
+    if recompute:
+        dY = L.Y = L.Ee = None              # (recomputed for this backward only)
 
 
 def edge_conv_block(x, B, N, k, num_filters, relu1=True, outs=None, net2=None, seed=None, seg=None):
@@ -1385,7 +1762,8 @@ def edge_conv_block(x, B, N, k, num_filters, relu1=True, outs=None, net2=None, s
     seg: a packed tower (Segments) with B = 1, N = R: only the k-NN is tied to a cloud (idx holds tower rows), every other pass is
     row-wise -- BatchNorm statistics run over all rows of the tower, as in a dense (B, N) tower; seg.bn_per_cloud: over the rows
     (conv0: the edges) of each cloud alone -- only the default form of conv0 (the fold with the virtual Y); recorded only with
-    seg.bn_per_cloud_train (the general backward: dY is written, the fused layer-0 pass has no per-cloud form)."""
+    seg.bn_per_cloud_train (the general backward: dY is written, the fused layer-0 pass has no per-cloud form).
+    conv0: one of _conv0_per_cloud / _fold / _bf16_fused / _dense_y -- its forward into L.mm and, in a recording, its backward."""
     c = ctx()
     R, C = x.shape
     F = int(num_filters)
@@ -1409,345 +1787,37 @@ def edge_conv_block(x, B, N, k, num_filters, relu1=True, outs=None, net2=None, s
     with variable_scope("conv0"):
         w0name, W0 = c.get_variable("weights", (2 * C, F))
         b0name, beta0 = c.get_variable("BatchNorm/beta", (F,))
+    # the layer's state: what conv0's passes and its tape closure read (the closure keeps every tensor in it alive)
+    L = SimpleNamespace(x=x, B=B, N=N, R=R, C=C, Cp=(C + 3) // 4 * 4, k=k, F=F, seg=seg, W0=W0, beta0=beta0, w0name=w0name,
+                        b0name=b0name, Y=None, UV=None, Ee=None, W0p=None, wd=None)
+    scratch = None
     if bpc:
-        dev = x.device
-        idx = knn(x, B, N, k, seed=seed, seg=seg)                           # ops.py:8-19
-        Cp, xg, wcat, UV = _point_gemm(c, x, W0, R, C, F)                   # [U | V] = X [Wa-Wb | Wb]
-        esrc = (UV[:, F:].data_ptr(), 2 * F, UV.data_ptr(), 2 * F, idx.data_ptr(), R, k, F)
-        st = torch.empty(seg.nseg * 2 * F, dtype=torch.float64, device=dev)
-        ws = seg_stats_workspace(R, seg.nseg, F, dev)
-        H.call("dgcnn_seg_edge_stats_f32", *esrc, seg.device(dev).data_ptr(), seg.nseg, st.data_ptr(), ws.data_ptr(), ws.numel(),
-               tag="seg_edge_stats_kernel", work=4.0 * (2 * R * F) + 4.0 * R * k, nbytes=4.0 * (R * k * F + R * F))
-        mean, rstd = seg_bn_finalize(st, seg, F, k)                         # ops.py:53, count n_b * k
-        if outs is None:
-            mm, net_out = c.new_buffer(R, 2 * F), None
-        else:
-            mm, net_out = outs
-        mx, mn = mm[:, :F], mm[:, F:]
-        if not c.recording:
-            H.call("dgcnn_seg_edge_bn_act_kreduce_f32", *esrc, seg.row_group(dev).data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                   beta0.data_ptr(), 1, mx.data_ptr(), H.ld2(mx), mn.data_ptr(), H.ld2(mn),
-                   tag="seg_edge_bn_act_kreduce_kernel", work=4.0 * (4 * R * F) + 4.0 * R * k, nbytes=4.0 * (R * k * F + R * F))   # ops.py:54-58
-        else:
-            _edge_conv_record_per_cloud(c, x, C, k, F, seg, idx, esrc, UV, Cp, xg, wcat, mean, rstd, beta0, w0name, b0name, mm)
-        net = conv_bn_act(mm, "conv1", 64, relu=relu1, out=net_out, out2=net2, arith=None, seg=seg)   # ops.py:62-70
-        return mm, net, idx
-    c.push_slots(c.step_slots)                   # conv0's statistics come from passes whose grids FOLLOW the slot count: the maximum
-    st = c.stats(F)
-    bf16 = EDGE_MLP_DTYPE == "bf16"
-    literal = EDGE_MLP_LITERAL or bf16
-    gather = (not literal) and (not EDGE_MLP_NBR_GEMM) and F % 4 == 0 and F <= 1024
-    idx = knn(x, B, N, k, seed=seed, seg=seg)                           # ops.py:8-19
-    virtual = gather and not EDGE_MATERIALIZE_Y and k < 256   # conv0 output never written: recomputed from (V, U, idx)
-    #                                                           (the edge BN passes pack tie / positive counts: k < 256)
-    # the fused bf16 kernels write neither E nor y: decided BEFORE anything of (R*k, F) is allocated (1.3 GB per layer at configs[2])
-    fused_bf16 = (bf16 and bool(H.load().dgcnn_edge_mlp_bf16_supported(C, k, F)) and W0.is_contiguous() and
-                  (C <= 4 or (H.ld2(x) % 4 == 0 and x.data_ptr() % 16 == 0)))
-    Y = None if (virtual or fused_bf16) else torch.empty((R * k, F), dtype=torch.float32, device=x.device)
-    wd = wcat = UV = None
-    Ee = W0p = None
-    fused_bwd = False
-    Cp = (C + 3) // 4 * 4
-
-    def bf16_operands():
-        """The literal edge tensor in fp32 (the difference x_j - x_i BEFORE any rounding; channels padded to a multiple of 4 so
-        that the products take the float4 path) and the matching weight rows -- the operands the bf16 products round.
-        dgcnn_gemm_f32 rounds its operands (arith = 1) only on its float4 path with N > 4 (include/dgcnn_hip.h); where the products
-        E W0 and E^T dY (both N = F) will not take it, E and the weight are rounded here instead: rounded values are bf16 values, so
-        the fp32 product of them is the mode's arithmetic.  (Rounding is idempotent: the other shapes see the same bits as before.)"""
-        xg, Wp = x, W0
-        if Cp != C:
-            xg = H.zeros((R, Cp), torch.float32, x.device)
-            H.call("dgcnn_copy2d_f32", x.data_ptr(), H.ld2(x), xg.data_ptr(), Cp, R, C, 0)
-            Wp = H.zeros((2 * Cp, F), torch.float32, x.device)
-            H.call("dgcnn_copy2d_f32", W0[:C].data_ptr(), F, Wp[:C].data_ptr(), F, C, F, 0)
-            H.call("dgcnn_copy2d_f32", W0[C:].data_ptr(), F, Wp[Cp:Cp + C].data_ptr(), F, C, F, 0)
-        E_ = torch.empty((R * k, 2 * Cp), dtype=torch.float32, device=x.device)
-        H.call("dgcnn_edge_gather_f32", xg.data_ptr(), H.ld2(xg), idx.data_ptr(), B, N, Cp, k, E_.data_ptr())   # ops.py:21-40
-        if not (F % 4 == 0 and F > 4 and H.ld2(Wp) % 4 == 0 and Wp.data_ptr() % 16 == 0):
-            H.call("dgcnn_round_bf16_f32", E_.data_ptr(), E_.data_ptr(), E_.numel())
-            Wr = torch.empty((Wp.shape[0], F), dtype=torch.float32, device=x.device)      # (never W0 itself: a variable)
-            Wc = Wp.contiguous()
-            H.call("dgcnn_round_bf16_f32", Wc.data_ptr(), Wr.data_ptr(), Wr.numel())
-            Wp = Wr
-        return E_, Wp
-
-    if bf16:
-        bsrc = (x.data_ptr(), H.ld2(x), idx.data_ptr(), W0.data_ptr(), B, N, C, k, F)
-        # the backward in one pass over the edges (8 <= k <= 128): the forward then packs (#ties, #positives) as the fp32 edge kernels do
-        fused_bwd = fused_bf16 and c.recording and BF16_FUSED_BWD and bool(H.load().dgcnn_edge_mlp_bf16_bwd_supported(C, k, F))
-        if fused_bf16:
-            # csrc/edge_mlp_bf16.hip: E = [x_i, x_j - x_i] gathered, rounded and multiplied tile by tile on the bf16 MFMA pipe;
-            # neither E nor y is written: this pass takes the BatchNorm sums, the next one recomputes y for BN + ReLU + max / mean
-            H.call("dgcnn_edge_mlp_bf16_stats", *bsrc, st.data_ptr(), tag="edge_mlp_bf16_kernel<stats>",
-                   work=2.0 * R * k * 2 * C * F, nbytes=4.0 * (R * k * C + R * C))
-        else:
-            # shapes the fused kernels do not take: the edge tensor in fp32, then ONE product whose operands the GEMM rounds to
-            # bf16 (arith = 1: v_cvt_pk_bf16_f32, round to nearest even) with fp32 accumulation on the bf16 MFMA pipe
-            Ee, W0p = bf16_operands()
-            gemm(Ee, W0p, Y, stats=None if DETERMINISTIC else st, arith=1)                                      # ops.py:47-52
-            if DETERMINISTIC:
-                colstats_det(Y, st)
-            if not c.recording:
-                Ee = None
-    elif literal:
-        H.call("dgcnn_edge_mlp_f32", x.data_ptr(), H.ld2(x), idx.data_ptr(), W0.data_ptr(), B, N, C, k, F,
-               Y.data_ptr(), 0 if DETERMINISTIC else st.data_ptr(),
-               tag="gemm_kernel<A_EDGE,B_ROW,STORE,%d,%d>" % (_tile_m(R * k, F), 64 if F <= 64 else 128),
-               work=2.0 * R * k * 2 * C * F)                            # ops.py:21-52 (gather fused)
-        if DETERMINISTIC:
-            colstats_det(Y, st)
-    elif gather:
-        # conv0 is linear: E W0 = x_i (Wa-Wb) + x_j Wb = U[i] + V[j] with [U | V] = X [Wa-Wb | Wb] -- ONE
-        # point-level GEMM (k times fewer MACs than the edge tensor product), then a per-edge gather-add
-        # bound by the HBM write of Y, which also takes the BatchNorm column sums.
-        # C = 3 (raw coordinates): pad the reduction dimension to 4 with a zero column / zero weight row so that
-        # the point-level GEMMs take the float4 path (the generic scalar kernel costs ~10x more on them)
-        Cp, xg, wcat, UV = _point_gemm(c, x, W0, R, C, F)
-        H.call("dgcnn_edge_gather_add_f32", UV[:, F:].data_ptr(), 2 * F, UV.data_ptr(), 2 * F, idx.data_ptr(),
-               B, N, k, F, H._p(Y), st.data_ptr(),
-               tag="edge_gather_add_kernel", work=4.0 * ((0 if virtual else R * k * F) + 2 * R * F) + 4.0 * R * k,
-               nbytes=4.0 * (R * k * F + R * F))   # ops.py:21-52   (nbytes: rows gathered from L2 -- bench.py's l2-gather roof)
-        if not virtual:
-            UV = None
+        L.idx = idx = knn(x, B, N, k, seed=seed, seg=seg)                   # ops.py:8-19
+        scratch = _conv0_per_cloud(c, L, outs)
     else:
-        # factored conv0, edge-level form (kept for odd F and as a cross-check): centre term once per point
-        # (U); the per-edge (B*N*k) x C GEMM gathers the neighbour rows and adds U[point] in its epilogue.
-        wd = torch.empty((C, F), dtype=torch.float32, device=x.device)
-        H.call("dgcnn_copy2d_f32", W0[:C].data_ptr(), F, wd.data_ptr(), F, C, F, 0)
-        H.call("dgcnn_axpby_f32", W0[C:].data_ptr(), -1.0, wd.data_ptr(), 1.0, C * F)
-        U = torch.empty((R, F), dtype=torch.float32, device=x.device)
-        gemm(x, wd, U)
-        H.call("dgcnn_edge_nbr_gemm_f32", x.data_ptr(), H.ld2(x), idx.data_ptr(), W0[C:].data_ptr(), U.data_ptr(), F,
-               B, N, C, k, F, Y.data_ptr(), 0 if DETERMINISTIC else st.data_ptr(),
-               tag="gemm_kernel<A_EDGE,B_ROW,STORE,%d,%d>" % (_tile_m(R * k, F), 64 if F <= 64 else 128),
-               work=2.0 * R * k * C * F)                                # ops.py:21-52 (gather fused)
-        if DETERMINISTIC:
-            colstats_det(Y, st)
-    mean, rstd = bn_finalize(st, F, R * k)                              # ops.py:53
-    c.pop_slots()
-    if outs is None:
-        mm = c.new_buffer(R, 2 * F)
-        net_out = None
-    else:
-        mm, net_out = outs
-    mx, mn = mm[:, :F], mm[:, F:]
-    cnt = torch.empty((R, F), dtype=torch.float32, device=x.device) if c.recording else None   # ties of the max
-    if fused_bf16:
-        H.call("dgcnn_edge_mlp_bf16_bn_kreduce", *bsrc, mean.data_ptr(), rstd.data_ptr(), beta0.data_ptr(),
-               mx.data_ptr(), H.ld2(mx), mn.data_ptr(), H.ld2(mn), H._p(cnt), 1 if fused_bwd else 0,
-               tag="edge_mlp_bf16_kernel<bn_kreduce>", work=2.0 * R * k * 2 * C * F, nbytes=4.0 * (R * k * C + R * C))   # ops.py:53-58
-    elif virtual:
-        esrc = (UV[:, F:].data_ptr(), 2 * F, UV.data_ptr(), 2 * F, idx.data_ptr(), B, N, k, F)
-        H.call("dgcnn_edge_bn_act_kreduce_f32", *esrc, mean.data_ptr(), rstd.data_ptr(), beta0.data_ptr(), 1,
-               mx.data_ptr(), H.ld2(mx), mn.data_ptr(), H.ld2(mn), H._p(cnt),
-               tag="bn_act_kreduce_kernel<edge>", work=4.0 * (4 * R * F) + 4.0 * R * k, nbytes=4.0 * (R * k * F + R * F))   # ops.py:54-58
-    else:
-        H.call("dgcnn_bn_act_kreduce_f32", Y.data_ptr(), R, k, F, mean.data_ptr(), rstd.data_ptr(), beta0.data_ptr(), 1,
-               mx.data_ptr(), H.ld2(mx), mn.data_ptr(), H.ld2(mn), 0, 0, H._p(cnt),
-               tag="bn_act_kreduce_kernel", work=4.0 * (R * k * F + 2 * R * F))   # ops.py:54-58
-
-    fv = F // 4
-    fused_l0 = (c.recording and virtual and EDGE_BWD_FUSED_L0 and EDGE_BWD_REDUCE_POINTS and C <= 4 and F % 4 == 0 and
-                fv & (fv - 1) == 0 and fv <= 256 and not c.tracked(x))
-    csr = None
-    if c.recording and gather and WGRAD_SIDE_STREAM and R >= SIDE_STREAM_MIN_ROWS and not fused_l0:
-        # the transposed adjacency depends only on idx: build it now, off the critical path, for the backward
-        off_t, rev_t = build_csr(idx, B, N, k, side=(c, R))
-        csr = (off_t, rev_t)
-
-    if c.recording:
-        def bwd():
-            c.push_slots(0)
-            try:
-                bwd_body()
-            finally:
-                c.pop_slots()
-
-        def bwd_body():
-            nonlocal Y, Ee, W0p
-            dmm = c.grad(mm)
-            if dmm is None:
-                return
-            dmx, dmn = dmm[:, :F], dmm[:, F:]
-            red = c.stats(F)
-            if fused_bf16 and fused_bwd:
-                # csrc/edge_mlp_bf16.hip: sums of the BatchNorm backward from the forward's per-point outputs, then ONE pass over the
-                # edges that recomputes y, forms dY (rounded to bf16), takes dW0 = E^T dY on the matrix pipe and leaves dY as bf16
-                # for the transposed-adjacency sum -- E, y and an fp32 dY are never written
-                H.call("dgcnn_edge_bn_bwd_reduce_points_f32", mx.data_ptr(), H.ld2(mx), mn.data_ptr(), H.ld2(mn),
-                       cnt.data_ptr(), dmx.data_ptr(), H.ld2(dmx), dmn.data_ptr(), H.ld2(dmn), beta0.data_ptr(), R, k, F,
-                       red.data_ptr(), tag="edge_bwd_reduce_points_kernel", work=4.0 * 5 * R * F)
-                dx = c.grad(x)
-                dYb = dysum = None
-                if dx is not None:
-                    dYb = torch.empty((R * k, F), dtype=torch.bfloat16, device=x.device)
-                    dysum = torch.empty((R, F), dtype=torch.float32, device=x.device)
-                ws = c.workspace()
-                H.call("dgcnn_edge_mlp_bf16_bwd", *bsrc, mean.data_ptr(), rstd.data_ptr(), beta0.data_ptr(), mx.data_ptr(), H.ld2(mx),
-                       cnt.data_ptr(), dmx.data_ptr(), H.ld2(dmx), dmn.data_ptr(), H.ld2(dmn), red.data_ptr(), H._p(dYb), H._p(dysum),
-                       F, c.var_grads[w0name].data_ptr(), c.var_grads[b0name].data_ptr(), 1.0, ws.data_ptr(), ws.numel(),
-                       tag="edge_mlp_bf16_kernel<bwd>", work=2.0 * R * k * 2 * C * F * 2, nbytes=4.0 * (R * k * C + R * C))
-                if dx is not None:
-                    # dx_i += (sum_m dY) (W0'[:C] - W0'[C:])^T,  dx_j += (sum of the incoming dY rows) W0'[C:]^T,  W0' = bf16(W0)
-                    W0r = torch.empty_like(W0)
-                    H.call("dgcnn_round_bf16_f32", W0.data_ptr(), W0r.data_ptr(), W0.numel())
-                    wdb = torch.empty((C, F), dtype=torch.float32, device=x.device)
-                    H.call("dgcnn_copy2d_f32", W0r[:C].data_ptr(), F, wdb.data_ptr(), F, C, F, 0)
-                    H.call("dgcnn_axpby_f32", W0r[C:].data_ptr(), -1.0, wdb.data_ptr(), 1.0, C * F)
-                    gemm(dysum, wdb, dx, transB=True, beta=1.0)
-                    if csr is not None:
-                        off, rev = csr
-                    else:
-                        off, rev = build_csr(idx, B, N, k)
-                    S = torch.empty((R, F), dtype=torch.float32, device=x.device)
-                    H.call("dgcnn_edge_gather_sum_bf16", dYb.data_ptr(), off.data_ptr(), rev.data_ptr(), R, F, S.data_ptr(), F,
-                           tag="csr_gather_sum_kernel<bf16>", work=2.0 * R * k * F + 4.0 * R * F)
-                    gemm(S, W0r[C:], dx, transB=True, beta=1.0)
-                return
-            if fused_bf16:
-                # the forward wrote neither E nor y: both are formed again for the backward (y by the SAME instruction sequence,
-                # so the recomputed z compares equal to the maxima the forward took), used by the passes below and dropped
-                Y = torch.empty((R * k, F), dtype=torch.float32, device=x.device)
-                H.call("dgcnn_edge_mlp_bf16", *bsrc, Y.data_ptr(), tag="edge_mlp_bf16_kernel<write>",
-                       work=2.0 * R * k * 2 * C * F, nbytes=4.0 * (R * k * C + R * C))
-                Ee, W0p = bf16_operands()
-            if virtual and EDGE_BWD_REDUCE_POINTS:
-                # sum dz, sum dz*xhat from the forward's per-point outputs alone (bn.hip): no pass over the edges
-                H.call("dgcnn_edge_bn_bwd_reduce_points_f32", mx.data_ptr(), H.ld2(mx), mn.data_ptr(), H.ld2(mn),
-                       cnt.data_ptr(), dmx.data_ptr(), H.ld2(dmx), dmn.data_ptr(), H.ld2(dmn), beta0.data_ptr(), R, k, F,
-                       red.data_ptr(), tag="edge_bwd_reduce_points_kernel", work=4.0 * 5 * R * F)
-            elif virtual:
-                assert UV is not None          # esrc holds raw pointers into UV: this reference keeps it alive
-                H.call("dgcnn_edge_bn_bwd_reduce_f32", *esrc, mean.data_ptr(), rstd.data_ptr(),
-                       beta0.data_ptr(), 1, dmx.data_ptr(), H.ld2(dmx), dmn.data_ptr(), H.ld2(dmn),
-                       mx.data_ptr(), H.ld2(mx), cnt.data_ptr(), red.data_ptr(),
-                       tag="bn_bwd_reduce_kernel<edge>", work=4.0 * (6 * R * F) + 4.0 * R * k)
-            else:
-                bn_bwd_reduce(Y, R, k, F, mean, rstd, beta0, 1, dmx, dmn, mx, cnt, red,
-                              tag="bn_bwd_reduce_kernel", work=4.0 * (R * k * F + 2 * R * F))
-            dx = c.grad(x)
-            if fused_l0 and dx is None:
-                # first layer (raw coordinates, nobody wants d(points)): dY is formed and consumed in one pass, straight into dW0
-                ws = c.workspace()
-                H.call("dgcnn_edge_bn_bwd_apply_wgrad_f32", *esrc, mean.data_ptr(), rstd.data_ptr(), beta0.data_ptr(),
-                       dmx.data_ptr(), H.ld2(dmx), dmn.data_ptr(), H.ld2(dmn), mx.data_ptr(), H.ld2(mx), cnt.data_ptr(),
-                       red.data_ptr(), x.data_ptr(), H.ld2(x), C, c.var_grads[w0name].data_ptr(), c.var_grads[b0name].data_ptr(), 1.0,
-                       ws.data_ptr(), ws.numel(), tag="edge_bwd_apply_wgrad_kernel", work=4.0 * (4 * R * F) + 4.0 * R * k,
-                       nbytes=4.0 * (R * k * F + R * F))
-                return
-            need_sum = (dx is not None) or not literal
-            dUV = dysum = None
-            if gather:
-                dUV = torch.empty((R, 2 * F), dtype=torch.float32, device=x.device)    # [dU | dV]
-                dysum = dUV[:, :F]
-            elif need_sum:
-                dysum = torch.empty((R, F), dtype=torch.float32, device=x.device)
-            if virtual:
-                assert UV is not None          # esrc holds raw pointers into UV: this reference keeps it alive
-                dY = torch.empty((R * k, F), dtype=torch.float32, device=x.device)
-                H.call("dgcnn_edge_bn_bwd_apply_f32", *esrc, mean.data_ptr(), rstd.data_ptr(), beta0.data_ptr(),
-                       1, dmx.data_ptr(), H.ld2(dmx), dmn.data_ptr(), H.ld2(dmn), mx.data_ptr(), H.ld2(mx), cnt.data_ptr(),
-                       red.data_ptr(), dY.data_ptr(),
-                       H._p(dysum), 0 if dysum is None else H.ld2(dysum), c.var_grads[b0name].data_ptr(), 1.0,
-                       tag="bn_bwd_apply_kernel<edge>", work=4.0 * (R * k * F + 7 * R * F) + 4.0 * R * k, nbytes=4.0 * (R * k * F + R * F))
-            else:
-                H.call("dgcnn_bn_bwd_apply_f32", Y.data_ptr(), R, k, F, mean.data_ptr(), rstd.data_ptr(), beta0.data_ptr(),
-                       3 if bf16 else 1, dmx.data_ptr(), H.ld2(dmx), dmn.data_ptr(), H.ld2(dmn), mx.data_ptr(), H.ld2(mx), cnt.data_ptr(),
-                       red.data_ptr(), Y.data_ptr(),
-                       H._p(dysum), 0 if dysum is None else H.ld2(dysum), c.var_grads[b0name].data_ptr(), 1.0,
-                       tag="bn_bwd_apply_kernel", work=4.0 * (2 * R * k * F + 3 * R * F))
-                dY = Y
-            ws = c.workspace()
-            dW0 = c.var_grads[w0name]
-
-            def incoming_sum(S):
-                # tf.gather^T as a gather: bucket edges by target, then every point sums its incoming dY rows
-                if csr is not None:
-                    off, rev = csr                    # built on the side stream during the forward
-                else:
-                    off, rev = build_csr(idx, B, N, k)
-                H.call("dgcnn_edge_gather_sum_f32", dY.data_ptr(), off.data_ptr(), rev.data_ptr(), R, F, S.data_ptr(),
-                       H.ld2(S), tag="csr_gather_sum_kernel", work=4.0 * (R * k * F + R * F))
-
-            if gather:
-                # dU = sum_m dY, dV = sum of incoming dY;  dWcat = X^T [dU|dV],  dx += [dU|dV] Wcat^T
-                incoming_sum(dUV[:, F:])
-                dwcat = torch.empty((Cp, 2 * F), dtype=torch.float32, device=x.device)
-                # dUV / dwcat are locals of this closure allocated on the main stream: record them on the side stream,
-                # or the caching allocator may hand dUV's block to the next main-stream allocation while the side GEMM reads it
-                if dx is not None:
-                    gemm(dUV, wcat[:C], dx, transB=True, beta=1.0, arith=None)
-                with c.off_critical_path(dwcat, dUV, rows=R):
-                    gemm(xg, dUV, dwcat, transA=True, arith=None)
-                    H.call("dgcnn_edge_wgrad_combine_f32", dwcat.data_ptr(), C, F, dW0.data_ptr())
-                return
-            if bf16:
-                # dW0 = E^T dY with bf16 operands: E and W0 rounded as in the forward; dY was written on the bf16 grid by the
-                # apply pass (relu flag 3), so the product's own rounding (arith = 1) leaves it unchanged
-                if W0p is W0:
-                    gemm(Ee, dY, dW0, transA=True, beta=1.0, arith=1)
-                else:
-                    dWp = torch.empty_like(W0p)
-                    gemm(Ee, dY, dWp, transA=True, arith=1)
-                    H.call("dgcnn_copy2d_f32", dWp[:C].data_ptr(), F, dW0[:C].data_ptr(), F, C, F, 1)
-                    H.call("dgcnn_copy2d_f32", dWp[Cp:Cp + C].data_ptr(), F, dW0[C:].data_ptr(), F, C, F, 1)
-                if dx is not None:
-                    # dE = dY W0'^T (W0' = bf16(W0)) never exists: the transpose of `edges` is linear, so
-                    #   dx_i += (sum_m dY) (W0'[:C] - W0'[C:])^T        dx_j += (sum of the dY rows of the edges that point at j) W0'[C:]^T
-                    # -- the same sums of the same bf16 x bf16 products as the literal edge-level product + scatter-add, taken at
-                    # the points (k times fewer MACs, no atomics); the point-level products run in the exact arithmetic
-                    W0r = torch.empty_like(W0)
-                    H.call("dgcnn_round_bf16_f32", W0.data_ptr(), W0r.data_ptr(), W0.numel())
-                    wdb = torch.empty((C, F), dtype=torch.float32, device=x.device)
-                    H.call("dgcnn_copy2d_f32", W0r[:C].data_ptr(), F, wdb.data_ptr(), F, C, F, 0)
-                    H.call("dgcnn_axpby_f32", W0r[C:].data_ptr(), -1.0, wdb.data_ptr(), 1.0, C * F)
-                    gemm(dysum, wdb, dx, transB=True, beta=1.0)
-                    if F % 4 != 0:
-                        raise H.HipError("bf16 edge-MLP: the input gradient needs filter counts that are multiples of 4 (F = %d)" % F)
-                    S = torch.empty((R, F), dtype=torch.float32, device=x.device)
-                    incoming_sum(S)
-                    gemm(S, W0r[C:], dx, transB=True, beta=1.0)
-                if fused_bf16:
-                    Y = Ee = None                   # (recomputed for this backward only)
-                return
-            if literal:
-                H.call("dgcnn_edge_mlp_wgrad_f32", x.data_ptr(), H.ld2(x), idx.data_ptr(), dY.data_ptr(), B, N, C, k, F,
-                       dW0.data_ptr(), 1.0, ws.data_ptr(), ws.numel(),
-                       tag=("edge_wgrad_smallc_kernel" if C <= 4 else "gemm_kernel<A_EDGE_T,B_ROW,STORE,128,%d>" % (64 if F <= 64 else 128)),
-                       work=2.0 * R * k * 2 * C * F)
-            else:
-                # dW0[C:] += sum_e x_j^T dY  -  X^T dYsum ;  dW0[:C] += X^T dYsum   (W0[:C]-W0[C:] and W0[C:] are the
-                # factors of the forward: d(Wa-Wb) = X^T dYsum, dWb = edge part)
-                H.call("dgcnn_edge_nbr_wgrad_f32", x.data_ptr(), H.ld2(x), idx.data_ptr(), dY.data_ptr(), B, N, C, k, F,
-                       dW0[C:].data_ptr(), 1.0, ws.data_ptr(), ws.numel(),
-                       tag=("edge_wgrad_smallc_kernel" if C <= 4 else "gemm_kernel<A_EDGE_T,B_ROW,STORE,128,%d>" % (64 if F <= 64 else 128)),
-                       work=2.0 * R * k * C * F)
-                dwd = torch.empty((C, F), dtype=torch.float32, device=x.device)
-                gemm(x, dysum, dwd, transA=True)
-                H.call("dgcnn_axpby_f32", dwd.data_ptr(), 1.0, dW0[:C].data_ptr(), 1.0, C * F)
-                H.call("dgcnn_axpby_f32", dwd.data_ptr(), -1.0, dW0[C:].data_ptr(), 1.0, C * F)
-            if dx is not None:
-                # E = [x_i, x_j - x_i]  =>  dx_i += (sum_m dY) (W0[:C]-W0[C:])^T ; dx_j += dY W0[C:]^T
-                wdb = wd
-                if wdb is None:
-                    wdb = torch.empty((C, F), dtype=torch.float32, device=x.device)
-                    H.call("dgcnn_copy2d_f32", W0[:C].data_ptr(), F, wdb.data_ptr(), F, C, F, 0)
-                    H.call("dgcnn_axpby_f32", W0[C:].data_ptr(), -1.0, wdb.data_ptr(), 1.0, C * F)
-                gemm(dysum, wdb, dx, transB=True, beta=1.0)
-                if SCATTER_ATOMICS or F % 4 != 0:
-                    H.call("dgcnn_edge_mlp_dgrad_scatter_f32", dY.data_ptr(), W0.data_ptr(), idx.data_ptr(), B, N, C, k,
-                           F, dx.data_ptr(), H.ld2(dx),
-                           tag="gemm_kernel<A_ROW,B_COL,SCATTER,%d,%d>" % (_tile_m(R * k, C), 64 if C <= 64 else 128),
-                           work=2.0 * R * k * C * F)
-                else:
-                    S = torch.empty((R, F), dtype=torch.float32, device=x.device)
-                    incoming_sum(S)
-                    gemm(S, W0[C:], dx, transB=True, beta=1.0)
-        c.tape.append(bwd)
-
-    net = conv_bn_act(mm, "conv1", 64, relu=relu1, out=net_out, out2=net2, arith=None)   # ops.py:62-70 (64 hard-coded)
-    return mm, net, idx
+        c.push_slots(c.step_slots)               # conv0's statistics come from passes whose grids FOLLOW the slot count: the maximum
+        st = c.stats(F)
+        L.idx = idx = knn(x, B, N, k, seed=seed, seg=seg)                   # ops.py:8-19
+        bf16 = EDGE_MLP_DTYPE == "bf16"
+        fold = not (EDGE_MLP_LITERAL or bf16 or EDGE_MLP_NBR_GEMM) and F % 4 == 0 and F <= 1024
+        # conv0 output never written: recomputed from (V, U, idx) (the edge BN passes pack tie / positive counts: k < 256)
+        virtual = fold and not EDGE_MATERIALIZE_Y and k < 256
+        # the fused bf16 kernels write neither E nor y: decided BEFORE anything of (R*k, F) is allocated (1.3 GB per layer at configs[2])
+        fused_bf16 = (bf16 and bool(H.load().dgcnn_edge_mlp_bf16_supported(C, k, F)) and W0.is_contiguous() and
+                      (C <= 4 or (H.ld2(x) % 4 == 0 and x.data_ptr() % 16 == 0)))
+        if fold:
+            _conv0_fold(c, L, st, outs, virtual)
+        elif fused_bf16:
+            L.kind = "bf16"
+            L.bsrc = (x.data_ptr(), H.ld2(x), idx.data_ptr(), W0.data_ptr(), B, N, C, k, F)
+            _conv0_bf16_fused(c, L, st, outs, one_pass=(c.recording and BF16_FUSED_BWD and
+                                                        bool(H.load().dgcnn_edge_mlp_bf16_bwd_supported(C, k, F))))
+        else:
+            L.kind = "bf16" if bf16 else "literal" if EDGE_MLP_LITERAL else "nbr"
+            scratch = _conv0_dense_y(c, L, st, outs)
+    # (scratch, and L outside a recording: the forward's temporaries stay allocated until conv1 has been issued)
+    net = conv_bn_act(L.mm, "conv1", 64, relu=relu1, out=L.net_out, out2=net2, arith=None, seg=seg if bpc else None)   # ops.py:62-70 (64 hard-coded)
+    return L.mm, net, idx
 
 
 # ----------------------------------------------------------------------------------------------
