@@ -5,12 +5,18 @@ CPU (numpy) restatement of the EdgeConv hot path of DeepLearnPhysics/dynamic-gcn
 checker for the HIP path.  Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg
 may import this module; the product package (dynamic-gcnn_amd/dgcnn) never does.
 
-PARITY UNPINNED.  The reference's arithmetic lives in TensorFlow 1.x + tf.contrib.slim
+PARITY: GRAPH PINNED, LIBRARY SEMANTICS ASSUMED.  The reference's arithmetic lives in TensorFlow 1.x + tf.contrib.slim
 (README.md:6, dgcnn/ops.py:5-7) which is neither vendored under /root/reference nor
 installable here, and the reference ships no tests / golden vectors.
 Every function below restates the reference's *graph* line by line (citations are
 file:line into /root/reference) with the TF1 library semantics of SURVEY.md Appendix A;
 the k-NN arithmetic order is made normative in oracle/knn_oracle.c.
+  Pinned: the graph and the training rule.  tests/test_reference_program.py executes the reference's own ops.py, model.py
+  and trainval.py under a TF1 stand-in (tests/tf1_standin.py, float64) and holds this module to them at 1e-10 (forward) /
+  1e-8 (gradients, Adam); tests/golden/ref_*.npz are recorded from that run and pin the HIP path.
+  Still resting on Appendix A: what the TF library calls compute (slim.conv2d / batch_norm defaults, top_k's tie order,
+  max_pool and reduce_max gradients, dropout scaling, Adam) -- the stand-in is our reading of them -- and TF's own float32
+  rounding order, which nothing here models.
 
 All functions are dtype-generic: run them in float32 (the oracle proper) or float64
 (the "twin" used to set tolerances).  Backward passes are hand-written and are themselves
@@ -441,7 +447,8 @@ def model_forward(point_cloud, flags, params, idx_list=None, dropout_mask=None, 
 
 
 def model_backward(dlogits, cache):
-    """-> dict name -> gradient, for every trainable variable."""
+    """-> dict name -> gradient, for every trainable variable.  The gradient of the input points (B,N,C) is left in
+    cache["d_points"]."""
     G = {}
     L = cache["L"]
     d = dlogits[:, :, None, :]
@@ -495,6 +502,8 @@ def model_backward(dlogits, cache):
         d_next = dx[:, :, None, :]
         if d_short is not None:
             d_next = d_next + d_short
+        if i == 0:
+            cache["d_points"] = dx
     return G
 
 

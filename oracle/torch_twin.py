@@ -4,8 +4,8 @@ An independent op-for-op restatement of the reference graph (dgcnn/ops.py:8-163,
 dgcnn/model.py:9-106, dgcnn/trainval.py:39-52) on torch-CPU tensors, with torch autograd supplying
 the backward.  Two uses: (1) tests/test_oracle.py checks the numpy oracle's hand-written backward
 against it; (2) bench.py's `cpu_baseline` leg times it on the GPU box's host cores (multi-threaded
-MKL), as the stand-in for the un-runnable TF1-CPU path.  PARITY UNPINNED,
-same caveat as oracle/dgcnn_oracle.py.  Never imported by the product package.
+MKL), as the stand-in for the un-runnable TF1-CPU path.  Graph pinned against the reference's
+program text by tests/test_reference_program.py; library semantics assumed -- as oracle/dgcnn_oracle.py.  Never imported by the product package.
 """
 import torch
 
@@ -42,9 +42,10 @@ def as_list(v, n):
     return [int(a) for a in v] if isinstance(v, list) else [int(v)] * n
 
 
-def model(points, flags, P, idx_list=None, k=None):
+def model(points, flags, P, idx_list=None, k=None, dropout_mask=None):
     """logits (B,N,num_class).  idx_list forces the neighbour graph (tests); None = compute it.  k: None = int(flags.KVALUE) for
-    every layer (model.py:16); a list = one k per layer, the form ops.repeat_edge_conv accepts (ops.py:77-82)."""
+    every layer (model.py:16); a list = one k per layer, the form ops.repeat_edge_conv accepts (ops.py:77-82).
+    dropout_mask: a given draw of model.py:91 ({0, 1/0.7}, the shape of Final's input), applied when flags.TRAIN (tests)."""
     L = int(flags.EDGE_CONV_LAYERS)
     residual = flags.MODEL_NAME != "dgcnn"
     ecf = as_list(flags.EDGE_CONV_FILTERS, L)
@@ -80,7 +81,9 @@ def model(points, flags, P, idx_list=None, k=None):
     net = torch.cat([g] + tensors, dim=3)
     for i in range(int(flags.FC_LAYERS)):
         net = conv_bn_act(net, P["FC%d/weights" % i], P["FC%d/BatchNorm/beta" % i])
-    if bool(flags.TRAIN) and getattr(flags, "_DROPOUT", False):
+    if bool(flags.TRAIN) and dropout_mask is not None:
+        net = net * dropout_mask
+    elif bool(flags.TRAIN) and getattr(flags, "_DROPOUT", False):
         net = torch.nn.functional.dropout(net, p=0.3, training=True)            # keep_prob 0.7, model.py:91
     return conv_bn_act(net, P["Final/weights"], P["Final/BatchNorm/beta"])[:, :, 0, :]
 
