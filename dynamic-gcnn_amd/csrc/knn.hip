@@ -1468,6 +1468,10 @@ int launch_knn_grid_seg(const float* x, const float* sq, int nseg, const int32_t
                         int32_t* idx, void* ws, hipStream_t st);
 int launch_knn_grid_listed(const char* what, const float* x, const float* sq, const int32_t* seg_off, const int32_t* list, int nlist,
                            int rows, int max_n, int C, int64_t ldx, int k, int32_t* idx, void* ws, hipStream_t st);
+// knn_wide.hip: the channel-slab matrix-pipe scan (C up to 1024; seg_off null = dense clouds) and the s_i kernel for C > 128
+void launch_sqnorm_wide(const float* x, int64_t ldx, int64_t rows, int C, float* sq, hipStream_t st);
+void launch_knn_wide(const float* x, const float* sq, const int32_t* seg_off, int ny, int max_n, int C, int64_t ldx, int k, int vec_ok,
+                     int32_t* idx, hipStream_t st);
 }  // namespace dg
 
 static bool knn_append_lx(int N) { return N < 8192; }     // which form of the append scan (knn_bf16a_kernel<LX>)
@@ -1588,6 +1592,27 @@ extern "C" int dgcnn_knn_hist(int stride) {              // tools / tests: 0 off
   return prev;
 }
 
+// Smallest C that the channel-slab scan of knn_wide.hip takes (dense and packed, any k <= 64): 5 ... 129, default 129 = only the widths
+// no other kernel has an instance for, so every narrower shape launches what it always launched.  C > 128 goes there whatever the
+// value.  DGCNN_KNN_WIDE_MIN_C=<5 ... 129>
+constexpr int KNN_MAX_C = 1024, KNN_WIDE_ONLY_C = 129;
+static int g_knn_wide_min_c = -1;
+static int knn_wide_min_c() {
+  if (g_knn_wide_min_c < 0) {
+    const char* e = getenv("DGCNN_KNN_WIDE_MIN_C");
+    g_knn_wide_min_c = e ? atoi(e) : KNN_WIDE_ONLY_C;
+    if (g_knn_wide_min_c < 5 || g_knn_wide_min_c > KNN_WIDE_ONLY_C) g_knn_wide_min_c = KNN_WIDE_ONLY_C;
+  }
+  return g_knn_wide_min_c;
+}
+extern "C" int dgcnn_knn_wide_min_c(int c) {            // tools / tests: 5 ... 129; any other value only queries; returns the previous value
+  const int prev = knn_wide_min_c();
+  if (c >= 5 && c <= KNN_WIDE_ONLY_C) g_knn_wide_min_c = c;
+  return prev;
+}
+// the channel-slab scan takes this width (the VALU switch keeps every width it has an instance for)
+static bool knn_wide_takes(int C) { return C >= KNN_WIDE_ONLY_C || (C >= knn_wide_min_c() && !knn_force_valu()); }
+
 
 // ---- one dispatch for dense, packed and listed clouds ------------------------------------------------------------------------------
 namespace {
@@ -1621,6 +1646,10 @@ struct KnnCall {
 int knn_vec_ok(const float* x, int64_t ldx) { return (ldx % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0); }
 
 void launch_sqnorm(const KnnCall& a, int64_t rows) {
+  if (a.C > 128) {                           // [64][C + 1] floats would not fit: the chunked form of knn_wide.hip, the same sum
+    dg::launch_sqnorm_wide(a.x, a.ldx, rows, a.C, a.w.s_i(), a.st);
+    return;
+  }
   dg::launch(sqnorm_kernel, dim3((unsigned)dg::cdiv(rows, SQ_ROWS)), dim3(256), sizeof(float) * SQ_ROWS * (a.C + 1), a.st, a.x, a.ldx, rows,
              a.C, a.w.s_i());
 }
@@ -1695,6 +1724,11 @@ int knn_scan(const CloudSet<Clouds>& s, const KnnCall& a, const int32_t* seed, i
   }
   if constexpr (CloudSet<Clouds>::kRawOnly) launch_scan_k<4>(s, a, launch_hist_bound(s, a));
   else if (tau0 && append) launch_append_scan(s, a, tau0);
+  else if (knn_wide_takes(a.C)) {            // wide rows, or the switch: the channel-slab scan; it takes no bound (a seed is ignored)
+    const int32_t* off = nullptr;            // dense clouds
+    if constexpr (!CloudSet<Clouds>::kDense && !CloudSet<Clouds>::kRawOnly) off = s.cl.off;
+    dg::launch_knn_wide(a.x, a.sq(), off, s.ny, s.max_n, a.C, a.ldx, a.k, a.vec_ok, a.idx, a.st);
+  }
   else if (a.C <= 4) launch_scan_k<4>(s, a, launch_hist_bound(s, a));
   else if (a.C <= 16) launch_scan_k<16>(s, a, tau0);
   else if (a.C <= 64) launch_scan_k<64>(s, a, tau0);
@@ -1727,9 +1761,10 @@ int knn_impl(const char* what, const float* x, int B, int N, int C, int64_t ldx,
   DG_REQUIRE(B > 0 && N > 0 && C > 0 && ldx >= C, DGCNN_EINVAL, "%s: bad shape B=%d N=%d C=%d", what, B, N, C);
   DG_REQUIRE(k > 0 && k <= N, DGCNN_EINVAL, "%s: k=%d must be in [1, N=%d] (tf.nn.top_k raises otherwise)", what, k, N);
   DG_REQUIRE(k <= 64, DGCNN_EUNSUP, "%s: k=%d > 64 unsupported", what, k);
-  DG_REQUIRE(C <= 128, DGCNN_EUNSUP, "%s: C=%d > 128 unsupported", what, C);
+  DG_REQUIRE(C <= KNN_MAX_C, DGCNN_EUNSUP, "%s: C=%d > %d unsupported", what, C, KNN_MAX_C);
+  DG_REQUIRE(C <= 128 || !knn_force_valu(), DGCNN_EUNSUP, "%s: C=%d > 128 unsupported by the VALU scan (dgcnn_knn_force_valu)", what, C);
   const KnnCall a{what, x, C, ldx, k, knn_vec_ok(x, ldx), idx, knn_ws_dense(ws, ws_bytes, B, N, C, k), (hipStream_t)stream};
-  DG_REQUIRE(a.w.aligned() && a.w.holds(a.w.bound), DGCNN_EINVAL,
+  DG_REQUIRE(a.w.aligned() && a.w.holds(C > 128 ? a.w.end : a.w.bound), DGCNN_EINVAL,
              "%s: workspace must be 16-byte aligned and hold dgcnn_knn_workspace_bytes(B, N, C, k) bytes (got %zu)", what, ws_bytes);
   const CloudSet<DenseClouds> s{DenseClouds(N), B, N, N, (int64_t)B * N};
   const bool append = knn_append_usable(a);
@@ -1805,10 +1840,11 @@ extern "C" int dgcnn_knn_seg_f32(const float* x, int64_t ldx, int C, int k, int 
   const char* what = "dgcnn_knn_seg_f32";
   if (const int rc = knn_check_tower(what, x && idx && ws && seg_off, nseg, rows, C, ldx, k, false, min_n, max_n)) return rc;
   DG_REQUIRE(k <= 64, DGCNN_EUNSUP, "%s: k=%d > 64 unsupported", what, k);
-  DG_REQUIRE(C <= 128, DGCNN_EUNSUP, "%s: C=%d > 128 unsupported", what, C);
+  DG_REQUIRE(C <= KNN_MAX_C, DGCNN_EUNSUP, "%s: C=%d > %d unsupported", what, C, KNN_MAX_C);
+  DG_REQUIRE(C <= 128 || !knn_force_valu(), DGCNN_EUNSUP, "%s: C=%d > 128 unsupported by the VALU scan (dgcnn_knn_force_valu)", what, C);
   DG_REQUIRE(!seed || (ldseed >= kseed && kseed > 0), DGCNN_EINVAL, "%s: bad seed shape", what);
   const KnnCall a{what, x, C, ldx, k, knn_vec_ok(x, ldx), idx, knn_ws_seg(ws, ws_bytes, rows, max_n, C, k), (hipStream_t)stream};
-  DG_REQUIRE(a.w.aligned() && a.w.holds(a.w.bound), DGCNN_EINVAL,
+  DG_REQUIRE(a.w.aligned() && a.w.holds(C > 128 ? a.w.end : a.w.bound), DGCNN_EINVAL,
              "%s: workspace must be 16-byte aligned and hold dgcnn_knn_seg_workspace_bytes(rows, max_n, C, k) bytes (got %zu)", what,
              ws_bytes);
   const CloudSet<PackedClouds> s{PackedClouds{seg_off, nseg}, nseg, min_n, max_n, (int64_t)rows};

@@ -602,6 +602,8 @@ def knn(x2d, B, N, k, seed=None, seg=None):
         tag = "knn_call<C%d,k%d>[sqnorm_kernel+knn_seed_bound_kernel+knn_bf16a_kernel+knn_select_kernel]" % (Cp, kc)
     elif C <= 4:
         tag = "knn_call<C%d,k%d>[%s]" % (Cp, kc, "knn_grid_*" if N >= 4096 else "sqnorm_kernel+knn_hist_bound_kernel+knn_kernel")
+    elif _knn_wide(C):
+        tag = "knn_call<C%d,k%d>[%s+knn_wide_kernel]" % (Cp, kc, "sqnorm_wide_kernel" if C > 128 else "sqnorm_kernel")
     else:
         tag = "knn_call<C%d,k%d>[sqnorm_kernel+%s]" % (Cp, kc, "knn_bf16f_kernel" if N >= 8192 else "knn_mfma_kernel")
     if seeded:
@@ -613,9 +615,19 @@ def knn(x2d, B, N, k, seed=None, seg=None):
     return idx
 
 
+def _knn_wide(C):
+    """the library gives this width to the channel-slab scan (knn_wide.hip; knn.hip:knn_wide_takes): C > 128 always, narrower rows
+    from dgcnn_knn_wide_min_c on"""
+    return C >= min(int(H.load().dgcnn_knn_wide_min_c(-1)), 129)
+
+
 def _knn_instance(C, k):
-    """(CP, KC) of the scan kernel a shape instantiates (knn.hip:knn_scan, launch_scan_k), for bench.py's tags"""
-    return (4 if C <= 4 else 16 if C <= 16 else 64 if C <= 64 else 128), (8 if k <= 8 else 20 if k <= 20 else 40 if k <= 40 else 64)
+    """(CP, KC) of the scan kernel a shape instantiates (knn.hip:knn_scan, launch_scan_k), for bench.py's tags; CP = the channels
+    rounded up to whole slabs of 64 where the channel-slab scan takes the width (its kernel has no CP parameter)"""
+    kc = 8 if k <= 8 else 20 if k <= 20 else 40 if k <= 40 else 64
+    if C > 4 and _knn_wide(C):
+        return (C + 63) // 64 * 64, kc
+    return (4 if C <= 4 else 16 if C <= 16 else 64 if C <= 64 else 128), kc
 
 
 def _knn_workspace(x2d, query, *shape):
@@ -674,6 +686,8 @@ def knn_packed(x2d, k, seg, seed=None):
     seeded = _knn_seed_ok(seed, 1, R, k)
     if seeded and 16 < C <= 64:
         tag = "knn_seg_call<C%d,k%d>[sqnorm_kernel+knn_seed_bound_kernel+knn_bf16a_kernel+knn_select_kernel]" % (Cp, kc)
+    elif C > 4 and _knn_wide(C):
+        tag = "knn_seg_call<C%d,k%d>[%s+knn_wide_kernel]" % (Cp, kc, "sqnorm_wide_kernel" if C > 128 else "sqnorm_kernel")
     else:
         tag = "knn_seg_call<C%d,k%d>[sqnorm_kernel+%sknn_kernel]" % (Cp, kc, "knn_hist_bound_kernel+" if C <= 4 else "")
     H.call("dgcnn_knn_seg_f32", x2d.data_ptr(), H.ld2(x2d), C, k, seg.nseg, off.data_ptr(), R, seg.min_n, seg.max_n,
