@@ -836,11 +836,6 @@ __global__ __launch_bounds__(256, (Bf16fCfg<KC>::OCC)) void knn_bf16f_kernel(con
 //            +inf) work the same way -- they just compact after their first tiles.
 // Append order is arbitrary (LDS atomics), the result is not: the selection is by a total order on distinct keys, and WHEN a row
 // compacts depends only on its counts at tile boundaries.  Distances are the normative ones (same chain as above): bit-exact indices.
-__device__ __forceinline__ unsigned long long knn_key(float d, int j) {
-  const unsigned u = __float_as_uint(d + 0.0f);
-  const unsigned o = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ((unsigned long long)o << 32) | (unsigned)j;
-}
 __device__ __forceinline__ float knn_key_dist(unsigned long long key) {
   const unsigned o = (unsigned)(key >> 32);
   return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
@@ -863,32 +858,6 @@ __device__ __forceinline__ constexpr float ka_level(int m) {
   return L[m];
 }
 
-// value of lane (l ^ M): quad permutes and bank-masked row shifts on the DPP path for M < 16 (no LDS round trip, no address register),
-// ds_swizzle for 16, ds_bpermute for 32
-template <int M>
-__device__ __forceinline__ unsigned xchg32(unsigned v) {
-  if constexpr (M == 1) return (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0xB1, 0xF, 0xF, false);        // quad_perm [1,0,3,2]
-  else if constexpr (M == 2) return (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
-  else if constexpr (M == 4) {
-    const int t = __builtin_amdgcn_update_dpp((int)v, (int)v, 0x104, 0xF, 0x5, false);       // row_shl:4 into banks 0, 2 (lanes with bit 2 clear)
-    return (unsigned)__builtin_amdgcn_update_dpp(t, (int)v, 0x114, 0xF, 0xA, false);         // row_shr:4 into banks 1, 3
-  } else if constexpr (M == 8) {
-    const int t = __builtin_amdgcn_update_dpp((int)v, (int)v, 0x108, 0xF, 0x3, false);       // row_shl:8 into banks 0, 1
-    return (unsigned)__builtin_amdgcn_update_dpp(t, (int)v, 0x118, 0xF, 0xC, false);         // row_shr:8 into banks 2, 3
-  } else if constexpr (M == 16) return (unsigned)__builtin_amdgcn_ds_swizzle((int)v, 0x401F);   // bit mode: and 0x1f, or 0, xor 16
-  else return __shfl_xor(v, M, 64);
-}
-template <int M>
-__device__ __forceinline__ unsigned long long xchg64(unsigned long long v) {
-  const unsigned lo = xchg32<M>((unsigned)v), hi = xchg32<M>((unsigned)(v >> 32));
-  return ((unsigned long long)hi << 32) | lo;
-}
-template <int J2>
-__device__ __forceinline__ unsigned long long bitonic_step(unsigned long long key, int lane, bool up) {
-  const unsigned long long pk = xchg64<J2>(key);
-  const bool take_min = ((lane & J2) == 0) == up;
-  return (take_min == (pk < key)) ? pk : key;
-}
 template <int J2>
 __device__ __forceinline__ unsigned long long bitonic_steps_down(unsigned long long key, int lane, bool up) {
   key = bitonic_step<J2>(key, lane, up);
@@ -1472,6 +1441,11 @@ int launch_knn_grid_listed(const char* what, const float* x, const float* sq, co
 void launch_sqnorm_wide(const float* x, int64_t ldx, int64_t rows, int C, float* sq, hipStream_t st);
 void launch_knn_wide(const float* x, const float* sq, const int32_t* seg_off, int ny, int max_n, int C, int64_t ldx, int k, int vec_ok,
                      int32_t* idx, hipStream_t st);
+// knn_bigk.hip: the append-and-compact scan for 64 < k <= 256 (any C up to 1024; seg_off null = dense clouds); ent: knn_bigk_cap(k)
+// 8-byte keys for every row
+int knn_bigk_cap(int k);
+void launch_knn_bigk(const float* x, const float* sq, const int32_t* seg_off, int ny, int max_n, int C, int64_t ldx, int k, int vec_ok,
+                     int32_t* idx, unsigned long long* ent, hipStream_t st);
 }  // namespace dg
 
 static bool knn_append_lx(int N) { return N < 8192; }     // which form of the append scan (knn_bf16a_kernel<LX>)
@@ -1487,10 +1461,31 @@ static int knn_append_tighten_mask(bool lx) {
   return (tight ? tight : (lx ? 4 : 8)) - 1;
 }
 
+// Smallest k that the large-k scan of knn_bigk.hip takes (dense and packed, any C): 1 ... 65, default 65 = only the neighbour counts no
+// other kernel has an instance for, so every k <= 64 launches what it always launched.  k > 64 goes there whatever the value.
+// DGCNN_KNN_BIG_K_MIN=<1 ... 65>
+constexpr int KNN_MAX_K = 256, KNN_BIG_ONLY_K = 65;
+static int g_knn_big_k_min = -1;
+static int knn_big_k_min() {
+  if (g_knn_big_k_min < 0) {
+    const char* e = getenv("DGCNN_KNN_BIG_K_MIN");
+    g_knn_big_k_min = e ? atoi(e) : KNN_BIG_ONLY_K;
+    if (g_knn_big_k_min < 1 || g_knn_big_k_min > KNN_BIG_ONLY_K) g_knn_big_k_min = KNN_BIG_ONLY_K;
+  }
+  return g_knn_big_k_min;
+}
+extern "C" int dgcnn_knn_big_k_min(int k) {             // tools / tests: 1 ... 65; any other value only queries; returns the previous value
+  const int prev = knn_big_k_min();
+  if (k >= 1 && k <= KNN_BIG_ONLY_K) g_knn_big_k_min = k;
+  return prev;
+}
+// the large-k scan takes this k (the VALU switch keeps every k it has an instance for)
+static bool knn_bigk_takes(int k) { return k >= KNN_BIG_ONLY_K || (k >= knn_big_k_min() && !knn_force_valu()); }
+
 // ---- the workspace of every k-NN entry ---------------------------------------------------------------------------------------------
 // [s_i of every row | bounds of every row: the seeds' or the histogram's (not in the cell-grid-only entry) | scratch: the cell grid's
-// (knn_grid.hip), or the append-form scan's -- one count and `cap` 8-byte entries per row], every region but the last padded to 256
-// bytes.  An entry and its *_workspace_bytes query build the layout with the same function below: the query answers `end`.
+// (knn_grid.hip), or the append-form scan's -- one count and `cap` 8-byte entries per row -- or the large-k scan's: the same layout
+// (its counts stay in LDS; the count region is left unused)], every region but the last padded to 256 bytes.  An entry and its *_workspace_bytes query build the layout with the same function below: the query answers `end`.
 struct KnnWorkspace {
   char* base;                                // the caller's buffer and its size (null, 0: a size query)
   size_t bytes;
@@ -1511,11 +1506,13 @@ struct KnnWorkspace {
 };
 // dense: the cell grid's scratch for raw coordinates (C <= 4, k <= 40), the append form's for 16 < C <= 64
 static KnnWorkspace knn_ws_dense(void* ws, size_t n, int B, int N, int C, int k) {
+  if (knn_bigk_takes(k)) return KnnWorkspace(ws, n, (size_t)B * (size_t)N, true, 0, dg::knn_bigk_cap(k));
   const bool grid = dg::knn_grid_applicable(C, k);
   return KnnWorkspace(ws, n, (size_t)B * (size_t)N, true, grid ? dg::knn_grid_workspace_bytes(B, N) : 0,
                       !grid && knn_append_shape(C, k) ? knn_append_cap(k, N) : 0);
 }
 static KnnWorkspace knn_ws_seg(void* ws, size_t n, int rows, int max_n, int C, int k) {
+  if (knn_bigk_takes(k)) return KnnWorkspace(ws, n, (size_t)rows, true, 0, dg::knn_bigk_cap(k));
   return KnnWorkspace(ws, n, (size_t)rows, true, 0, knn_append_shape(C, k) ? knn_append_cap(k, max_n) : 0);
 }
 static KnnWorkspace knn_ws_seg_grid(void* ws, size_t n, int rows, int nseg) {              // no bounds: the grid uses none
@@ -1719,6 +1716,12 @@ template <class Clouds>
 int knn_scan(const CloudSet<Clouds>& s, const KnnCall& a, const int32_t* seed, int64_t ldseed, bool append) {
   const float* tau0 = nullptr;
   if constexpr (!CloudSet<Clouds>::kRawOnly) {
+    if (knn_bigk_takes(a.k)) {               // k > 64, or the switch: the large-k scan; it takes no bound (a seed is ignored)
+      const int32_t* off = nullptr;          // dense clouds
+      if constexpr (!CloudSet<Clouds>::kDense) off = s.cl.off;
+      dg::launch_knn_bigk(a.x, a.sq(), off, s.ny, s.max_n, a.C, a.ldx, a.k, a.vec_ok, a.idx, a.w.entries(), a.st);
+      return dg::check_launch(a.what);
+    }
     // the bound of the first k seeds of every row (C in {16, 32, 64}; otherwise none)
     if (seed && launch_seed_bound(a.x, a.sq(), s.rows, s.cl, a.C, a.ldx, seed, ldseed, a.k, a.w.bounds(), a.st)) tau0 = a.w.bounds();
   }
@@ -1760,18 +1763,20 @@ int knn_impl(const char* what, const float* x, int B, int N, int C, int64_t ldx,
   DG_REQUIRE(x && idx && ws, DGCNN_EINVAL, "%s: null pointer", what);
   DG_REQUIRE(B > 0 && N > 0 && C > 0 && ldx >= C, DGCNN_EINVAL, "%s: bad shape B=%d N=%d C=%d", what, B, N, C);
   DG_REQUIRE(k > 0 && k <= N, DGCNN_EINVAL, "%s: k=%d must be in [1, N=%d] (tf.nn.top_k raises otherwise)", what, k, N);
-  DG_REQUIRE(k <= 64, DGCNN_EUNSUP, "%s: k=%d > 64 unsupported", what, k);
+  DG_REQUIRE(k <= KNN_MAX_K, DGCNN_EUNSUP, "%s: k=%d > %d unsupported", what, k, KNN_MAX_K);
   DG_REQUIRE(C <= KNN_MAX_C, DGCNN_EUNSUP, "%s: C=%d > %d unsupported", what, C, KNN_MAX_C);
   DG_REQUIRE(C <= 128 || !knn_force_valu(), DGCNN_EUNSUP, "%s: C=%d > 128 unsupported by the VALU scan (dgcnn_knn_force_valu)", what, C);
+  DG_REQUIRE(k <= 64 || !knn_force_valu(), DGCNN_EUNSUP, "%s: k=%d > 64 unsupported by the VALU scan (dgcnn_knn_force_valu)", what, k);
   const KnnCall a{what, x, C, ldx, k, knn_vec_ok(x, ldx), idx, knn_ws_dense(ws, ws_bytes, B, N, C, k), (hipStream_t)stream};
-  DG_REQUIRE(a.w.aligned() && a.w.holds(C > 128 ? a.w.end : a.w.bound), DGCNN_EINVAL,
+  const bool bigk = knn_bigk_takes(k);       // the large-k scan keeps its row buffers in the workspace: all of it is required
+  DG_REQUIRE(a.w.aligned() && a.w.holds(C > 128 || bigk ? a.w.end : a.w.bound), DGCNN_EINVAL,
              "%s: workspace must be 16-byte aligned and hold dgcnn_knn_workspace_bytes(B, N, C, k) bytes (got %zu)", what, ws_bytes);
   const CloudSet<DenseClouds> s{DenseClouds(N), B, N, N, (int64_t)B * N};
-  const bool append = knn_append_usable(a);
-  const bool seeded = knn_seeds_used_dense(a, seed, kseed, N, append);
+  const bool append = !bigk && knn_append_usable(a);
+  const bool seeded = !bigk && knn_seeds_used_dense(a, seed, kseed, N, append);
   launch_sqnorm(a, s.rows);
   // raw coordinates (C <= 4) when the caller provided the scratch: exact search over a uniform cell grid (knn_grid.hip)
-  if (dg::knn_grid_applicable(C, k) && !knn_force_valu() && a.w.holds(a.w.end) && N >= dg::knn_grid_min_n())
+  if (!bigk && dg::knn_grid_applicable(C, k) && !knn_force_valu() && a.w.holds(a.w.end) && N >= dg::knn_grid_min_n())
     return dg::launch_knn_grid(x, a.sq(), B, N, C, ldx, k, idx, a.w.grid(), a.st);
   return knn_scan(s, a, seeded ? seed : nullptr, ldseed, append);
 }
@@ -1839,17 +1844,19 @@ extern "C" int dgcnn_knn_seg_f32(const float* x, int64_t ldx, int C, int k, int 
                                  void* stream) {
   const char* what = "dgcnn_knn_seg_f32";
   if (const int rc = knn_check_tower(what, x && idx && ws && seg_off, nseg, rows, C, ldx, k, false, min_n, max_n)) return rc;
-  DG_REQUIRE(k <= 64, DGCNN_EUNSUP, "%s: k=%d > 64 unsupported", what, k);
+  DG_REQUIRE(k <= KNN_MAX_K, DGCNN_EUNSUP, "%s: k=%d > %d unsupported", what, k, KNN_MAX_K);
   DG_REQUIRE(C <= KNN_MAX_C, DGCNN_EUNSUP, "%s: C=%d > %d unsupported", what, C, KNN_MAX_C);
   DG_REQUIRE(C <= 128 || !knn_force_valu(), DGCNN_EUNSUP, "%s: C=%d > 128 unsupported by the VALU scan (dgcnn_knn_force_valu)", what, C);
+  DG_REQUIRE(k <= 64 || !knn_force_valu(), DGCNN_EUNSUP, "%s: k=%d > 64 unsupported by the VALU scan (dgcnn_knn_force_valu)", what, k);
   DG_REQUIRE(!seed || (ldseed >= kseed && kseed > 0), DGCNN_EINVAL, "%s: bad seed shape", what);
   const KnnCall a{what, x, C, ldx, k, knn_vec_ok(x, ldx), idx, knn_ws_seg(ws, ws_bytes, rows, max_n, C, k), (hipStream_t)stream};
-  DG_REQUIRE(a.w.aligned() && a.w.holds(C > 128 ? a.w.end : a.w.bound), DGCNN_EINVAL,
+  const bool bigk = knn_bigk_takes(k);       // the large-k scan keeps its row buffers in the workspace: all of it is required
+  DG_REQUIRE(a.w.aligned() && a.w.holds(C > 128 || bigk ? a.w.end : a.w.bound), DGCNN_EINVAL,
              "%s: workspace must be 16-byte aligned and hold dgcnn_knn_seg_workspace_bytes(rows, max_n, C, k) bytes (got %zu)", what,
              ws_bytes);
   const CloudSet<PackedClouds> s{PackedClouds{seg_off, nseg}, nseg, min_n, max_n, (int64_t)rows};
-  const bool append = knn_append_usable(a);
-  const bool seeded = knn_seeds_used_packed(a, seed, kseed, min_n, max_n, append);
+  const bool append = !bigk && knn_append_usable(a);
+  const bool seeded = !bigk && knn_seeds_used_packed(a, seed, kseed, min_n, max_n, append);
   launch_sqnorm(a, s.rows);
   return knn_scan(s, a, seeded ? seed : nullptr, ldseed, append);
 }

@@ -1,5 +1,5 @@
 // knn_common.h -- the cloud maps (dense / packed tower), lane-mask selects and the register-resident sorted (d, j) list shared by the
-// k-NN kernels (knn.hip, knn_grid.hip).
+// k-NN kernels (knn.hip, knn_grid.hip, knn_wide.hip, knn_bigk.hip).
 #pragma once
 #include "common.h"
 #include <math.h>
@@ -126,6 +126,41 @@ __device__ __forceinline__ void fill_short_list(const int (&jl)[KC], int k, int 
 #pragma unroll
   for (int t = 0; t < KC; ++t) F += (t < k && jl[t] != 0x7fffffff) ? 1 : 0;
   if (F < k) fill_short_row<KC>([&](int t) { return jl[t]; }, F, k, N, base, out);
+}
+
+// ---- 64-bit selection keys and the wave-level compare-exchange (the append-form scan of knn.hip, the large-k scan of knn_bigk.hip) ----
+// key = orderable bits of d << 32 | j: unsigned order == (d, j) lexicographic order (d never NaN / -0)
+__device__ __forceinline__ unsigned long long knn_key(float d, int j) {
+  const unsigned u = __float_as_uint(d + 0.0f);
+  const unsigned o = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((unsigned long long)o << 32) | (unsigned)j;
+}
+
+// value of lane (l ^ M): quad permutes and bank-masked row shifts on the DPP path for M < 16 (no LDS round trip, no address register),
+// ds_swizzle for 16, ds_bpermute for 32
+template <int M>
+__device__ __forceinline__ unsigned xchg32(unsigned v) {
+  if constexpr (M == 1) return (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0xB1, 0xF, 0xF, false);        // quad_perm [1,0,3,2]
+  else if constexpr (M == 2) return (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
+  else if constexpr (M == 4) {
+    const int t = __builtin_amdgcn_update_dpp((int)v, (int)v, 0x104, 0xF, 0x5, false);       // row_shl:4 into banks 0, 2 (lanes with bit 2 clear)
+    return (unsigned)__builtin_amdgcn_update_dpp(t, (int)v, 0x114, 0xF, 0xA, false);         // row_shr:4 into banks 1, 3
+  } else if constexpr (M == 8) {
+    const int t = __builtin_amdgcn_update_dpp((int)v, (int)v, 0x108, 0xF, 0x3, false);       // row_shl:8 into banks 0, 1
+    return (unsigned)__builtin_amdgcn_update_dpp(t, (int)v, 0x118, 0xF, 0xC, false);         // row_shr:8 into banks 2, 3
+  } else if constexpr (M == 16) return (unsigned)__builtin_amdgcn_ds_swizzle((int)v, 0x401F);   // bit mode: and 0x1f, or 0, xor 16
+  else return __shfl_xor(v, M, 64);
+}
+template <int M>
+__device__ __forceinline__ unsigned long long xchg64(unsigned long long v) {
+  const unsigned lo = xchg32<M>((unsigned)v), hi = xchg32<M>((unsigned)(v >> 32));
+  return ((unsigned long long)hi << 32) | lo;
+}
+template <int J2>
+__device__ __forceinline__ unsigned long long bitonic_step(unsigned long long key, int lane, bool up) {
+  const unsigned long long pk = xchg64<J2>(key);
+  const bool take_min = ((lane & J2) == 0) == up;
+  return (take_min == (pk < key)) ? pk : key;
 }
 
 }  // namespace

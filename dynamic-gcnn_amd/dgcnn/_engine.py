@@ -598,7 +598,9 @@ def knn(x2d, B, N, k, seed=None, seg=None):
     Cp, kc = _knn_instance(C, k)
     seeded = _knn_seed_ok(seed, B, N, k)
     # bench.py's tag of the CALL: the kernels it launches (the library picks the form: knn.hip:knn_impl, knn_scan)
-    if seeded and 16 < C <= 64:
+    if _knn_big(k):
+        tag = "knn_call<C%d,k%d>[%s+knn_bigk_kernel]" % (Cp, kc, _sqnorm_name(C))
+    elif seeded and 16 < C <= 64:
         tag = "knn_call<C%d,k%d>[sqnorm_kernel+knn_seed_bound_kernel+knn_bf16a_kernel+knn_select_kernel]" % (Cp, kc)
     elif C <= 4:
         tag = "knn_call<C%d,k%d>[%s]" % (Cp, kc, "knn_grid_*" if N >= 4096 else "sqnorm_kernel+knn_hist_bound_kernel+knn_kernel")
@@ -615,6 +617,16 @@ def knn(x2d, B, N, k, seed=None, seg=None):
     return idx
 
 
+def _knn_big(k):
+    """the library gives this k to the large-k scan (knn_bigk.hip; knn.hip:knn_bigk_takes): k > 64 always, smaller k from
+    dgcnn_knn_big_k_min on"""
+    return k >= min(int(H.load().dgcnn_knn_big_k_min(-1)), 65)
+
+
+def _sqnorm_name(C):
+    return "sqnorm_wide_kernel" if C > 128 else "sqnorm_kernel"
+
+
 def _knn_wide(C):
     """the library gives this width to the channel-slab scan (knn_wide.hip; knn.hip:knn_wide_takes): C > 128 always, narrower rows
     from dgcnn_knn_wide_min_c on"""
@@ -623,7 +635,10 @@ def _knn_wide(C):
 
 def _knn_instance(C, k):
     """(CP, KC) of the scan kernel a shape instantiates (knn.hip:knn_scan, launch_scan_k), for bench.py's tags; CP = the channels
-    rounded up to whole slabs of 64 where the channel-slab scan takes the width (its kernel has no CP parameter)"""
+    rounded up to whole slabs of 64 where the channel-slab scan or the large-k scan takes the shape (their kernels have no CP
+    parameter); KC = 128 or 256 is the large-k scan's KP (half its row buffer)"""
+    if _knn_big(k):
+        return (C + 63) // 64 * 64, 128 if k <= 128 else 256
     kc = 8 if k <= 8 else 20 if k <= 20 else 40 if k <= 40 else 64
     if C > 4 and _knn_wide(C):
         return (C + 63) // 64 * 64, kc
@@ -663,7 +678,8 @@ def knn_packed(x2d, k, seg, seed=None):
     # raw coordinates: the cell grid, one per cloud, where the library's rule picks it (the same indices; a seed is not needed).  Mode 1
     # with a per-cloud threshold T > 0: the clouds of at least T points through the grid, the others through the scan, in one call
     lib = H.load()
-    T = int(lib.dgcnn_knn_seg_mix_min_n(-1)) if C <= 4 and _knn_grid_mode(lib, C, k) == 1 else 0
+    big = _knn_big(k)                        # the large-k scan: dgcnn_knn_seg_f32 whatever the width
+    T = int(lib.dgcnn_knn_seg_mix_min_n(-1)) if C <= 4 and not big and _knn_grid_mode(lib, C, k) == 1 else 0
     if T > 0:
         lst, n_grid, grid_max, scan_min, scan_max = seg.mix(T, x2d.device)
         use_grid = n_grid == seg.nseg
@@ -675,7 +691,7 @@ def knn_packed(x2d, k, seg, seed=None):
                    work=2.0 * float((n * n).sum()) * C)
             return idx
     else:
-        use_grid = C <= 4 and lib.dgcnn_knn_seg_grid_use(C, k, seg.nseg, R, seg.min_n, seg.max_n, int((n * n).sum()))
+        use_grid = C <= 4 and not big and lib.dgcnn_knn_seg_grid_use(C, k, seg.nseg, R, seg.min_n, seg.max_n, int((n * n).sum()))
     if use_grid:
         ws, nws = _knn_workspace(x2d, "dgcnn_knn_seg_grid_workspace_bytes", R, seg.nseg)
         H.call("dgcnn_knn_seg_grid_f32", x2d.data_ptr(), H.ld2(x2d), C, k, seg.nseg, off.data_ptr(), R, seg.min_n, seg.max_n,
@@ -684,7 +700,9 @@ def knn_packed(x2d, k, seg, seed=None):
         return idx
     ws, nws = _knn_workspace(x2d, "dgcnn_knn_seg_workspace_bytes", R, seg.max_n, C, k)
     seeded = _knn_seed_ok(seed, 1, R, k)
-    if seeded and 16 < C <= 64:
+    if big:
+        tag = "knn_seg_call<C%d,k%d>[%s+knn_bigk_kernel]" % (Cp, kc, _sqnorm_name(C))
+    elif seeded and 16 < C <= 64:
         tag = "knn_seg_call<C%d,k%d>[sqnorm_kernel+knn_seed_bound_kernel+knn_bf16a_kernel+knn_select_kernel]" % (Cp, kc)
     elif C > 4 and _knn_wide(C):
         tag = "knn_seg_call<C%d,k%d>[%s+knn_wide_kernel]" % (Cp, kc, "sqnorm_wide_kernel" if C > 128 else "sqnorm_kernel")

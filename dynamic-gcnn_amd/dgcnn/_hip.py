@@ -27,6 +27,7 @@ PROTOTYPES = {
     "dgcnn_knn_grid": [c_int],
     "dgcnn_knn_force_valu": [c_int],
     "dgcnn_knn_wide_min_c": [c_int],
+    "dgcnn_knn_big_k_min": [c_int],
     "dgcnn_knn_bf16_filter": [c_int],
     "dgcnn_knn_f32": [c_vp, c_int, c_int, c_int, c_i64, c_int, c_vp, c_vp, c_sz, c_vp],
     "dgcnn_knn_seed_min_n": [c_int],

@@ -51,9 +51,15 @@ const char* dgcnn_last_error(void);
  * idx[b][i][0..k) = the k smallest D_ij = (s_i + s_j) - 2 <x_i,x_j> of row i (self included),
  * ascending, ties -> lower j.  Arithmetic order is normative (oracle/knn_oracle.c): bit-exact.
  * x: (B,N,C) with row stride ldx.  No (B,N,N) matrix is ever written to HBM.
- * C <= 1024 and k <= 64 in every entry (dense, seeded, packed); DGCNN_EUNSUP beyond, before any launch.  Rows wider than 128 channels
- *   run the channel-slab matrix-pipe scan (csrc/knn_wide.hip): it takes no bound, so a seed is accepted and ignored there, and its
- *   workspace is [s_i | bounds] with no scratch, all of which the call requires (DGCNN_EINVAL if smaller).
+ * C <= 1024 and k <= 256 in the dense, seeded and packed entries (k <= 40 in the cell-grid and mix entries); DGCNN_EUNSUP beyond,
+ *   before any launch.  Rows wider than 128 channels run the channel-slab matrix-pipe scan (csrc/knn_wide.hip): it takes no bound, so
+ *   a seed is accepted and ignored there, and its workspace is [s_i | bounds] with no scratch, all of which the call requires
+ *   (DGCNN_EINVAL if smaller).
+ * 64 < k <= 256, at every width C <= 1024: the large-k scan (csrc/knn_bigk.hip) -- the same distances on the fp32 matrix pipe, no
+ *   sorted lists: a candidate whose (D~, j) key is below the row's bound is appended to the row's buffer of 256 (k <= 128) or 512
+ *   eight-byte keys, a buffer that fills up is cut back to its k smallest keys, whose largest is the new bound, and one sort per row
+ *   at the end writes the indices.  A seed is accepted and ignored.  Its workspace is [s_i | bounds | one count and 256 or 512 keys
+ *   per row], all of which the call requires (DGCNN_EINVAL if smaller).
  * Non-finite input (NaN or infinite coordinates, or finite ones whose s_i, s_i + s_j or 2 <x_i,x_j> overflow): the key of candidate
  *   j for row i is (D~_ij, j), D~ = +inf where D_ij is NaN and D_ij otherwise (-inf sorts first); idx[i] = the k smallest keys,
  *   ascending, ties -> lower j, in every kernel form and entry (dense, seeded, packed).  So every row of every cloud holds k DISTINCT
@@ -74,7 +80,8 @@ int64_t dgcnn_knn_workspace_bytes(int B, int N, int C, int k);
 int dgcnn_knn_grid(int mode);
 /* A/B switch: 1 = distances by VALU fmaf chains for every C (exact by construction), 0 (default) =
  * v_mfma_f32_32x32x2_f32 for C > 4 (bit-identical on gfx950; the tests compare both).  Returns the
- * previous setting.  The VALU scan has instances for C <= 128 only: while the switch is on, C > 128 is DGCNN_EUNSUP. */
+ * previous setting.  The VALU scan has instances for C <= 128 and k <= 64 only: while the switch is on, C > 128 and k > 64 are
+ * DGCNN_EUNSUP. */
 int dgcnn_knn_force_valu(int on);
 /* Smallest C that the channel-slab scan (csrc/knn_wide.hip: fp32 matrix pipe, the channel dimension in slabs of 64, C <= 1024) takes
  * in the dense, seeded and packed entries: 5 ... 129; any other value (-1) only queries.  Default 129: only the widths that no other
@@ -82,6 +89,13 @@ int dgcnn_knn_force_valu(int on);
  * below, the seeded append-form scan keeps the calls it takes and dgcnn_knn_force_valu(1) keeps every call.  Identical indices either
  * way.  Returns the previous value.  (tools / tests; env DGCNN_KNN_WIDE_MIN_C) */
 int dgcnn_knn_wide_min_c(int c);
+/* Smallest k that the large-k scan (csrc/knn_bigk.hip) takes in the dense, seeded and packed entries: 1 ... 65; any other value (-1)
+ * only queries.  Default 65: only the neighbour counts that no other kernel has an instance for, so every k <= 64 launches what it
+ * launched before and dgcnn_knn_workspace_bytes / dgcnn_knn_seg_workspace_bytes answer what they answered before.  k > 64 goes there
+ * whatever the value; below, dgcnn_knn_force_valu(1) keeps every call (and refuses k > 64: DGCNN_EUNSUP).  While the value is below
+ * 65 the two workspace queries answer the large-k layout for the k it covers, and the entries require it.  Identical indices either
+ * way.  Returns the previous value.  (tools / tests; env DGCNN_KNN_BIG_K_MIN) */
+int dgcnn_knn_big_k_min(int k);
 /* Large feature-space graphs (16 < C <= 64, C % 4 == 0, 16-byte aligned rows): approximate distances from the two leading bf16
  * terms of every operand on the bf16 matrix pipe with a rigorous error bound as a conservative filter, the normative fp32 fmaf
  * chain only for the survivors -- the same indices, bit for bit.  mode 0 = never, 1 = whenever applicable, 2 (default) = for
