@@ -13,13 +13,12 @@
 // conflicts); each lane keeps a private sorted (d, j) list of KC entries in registers and inserts
 // with a branch-free v_med3/v_cndmask network, skipped wave-uniformly when no lane improves.
 // The four per-wave lists are merged through LDS at the end.  The (B,N,N) matrix never exists.
-#include "knn_common.h"
+#include "knn_scan.h"
 #include <type_traits>
 #include <stdlib.h>
 
 namespace {
 
-constexpr int ROWS = 64;
 constexpr int WAVES = 4;
 constexpr int TJ = 128;
 constexpr int PERW = TJ / WAVES;
@@ -164,13 +163,6 @@ __global__ __launch_bounds__(256) void knn_hist_bound_kernel(const float* __rest
   if (row < N) tau0[cb + row] = tau;
 }
 
-// Shared selection bound.  The candidates of a query row are split over FOUR sorted lists (KC entries each, KC % 4 == 0).
-// If every list holds at least KC/4 entries, the row has seen KC candidates with d <= tau := max_i list_i[KC/4 - 1], so a
-// candidate with d > tau has KC candidates strictly before it in (d, j) order and can never enter the row's top KC:
-// dropping it is exact.  Candidates with d == tau pass (the tie is decided by index in the final merge), hence the
-// filter  d < min(own k-th, next_up(tau)).  tau is about the row's GLOBAL k-th distance (the KC/4-th best of a quarter
-// of the candidates), where a list's own k-th is about the global 4k-th: ~2.5x fewer inserts.  The lists publish
-// list_i[KC/4 - 1] in LDS after every drain; a stale (older = larger) value only makes the filter looser.
 // Register budget: x_i (CP) + list (2*KC) + ~70 for the candidate stream -> waves/SIMD target.
 template <int CP, int KC>
 constexpr int knn_min_waves() {
@@ -213,11 +205,7 @@ __global__ __launch_bounds__(256, (knn_min_waves<CP, KC>())) void knn_kernel(con
 
   float dl[KC];
   int jl[KC];
-#pragma unroll
-  for (int t = 0; t < KC; ++t) {
-    dl[t] = INFINITY;
-    jl[t] = 0x7fffffff;
-  }
+  list_init<KC>(dl, jl);
 
   thrw[tid] = INFINITY;
 #pragma unroll 1
@@ -290,39 +278,8 @@ __global__ __launch_bounds__(256, (knn_min_waves<CP, KC>())) void knn_kernel(con
     }
   }
 
-  // ---- merge the 4 per-wave lists into wave 0 through LDS (lexicographic (d, j)) ----
-  __syncthreads();
-  float* md = smem;
-  int* mj = reinterpret_cast<int*>(smem + ROWS * KC);
-#pragma unroll 1
-  for (int src = 1; src < WAVES; ++src) {
-    if (src > 1) __syncthreads();
-    if (w == src) {
-#pragma unroll
-      for (int t = 0; t < KC; ++t) {
-        md[t * ROWS + lane] = dl[t];
-        mj[t * ROWS + lane] = jl[t];
-      }
-    }
-    __syncthreads();
-    if (w == 0) {
-#pragma unroll 1
-      for (int t = 0; t < KC; ++t) {
-        const float d = md[t * ROWS + lane];
-        const int j = mj[t * ROWS + lane];
-        const lmask_t need = key_less<true>(d, j, dl[KC - 1], jl[KC - 1]);
-        if (need == 0) break;  // wave-uniform; the source list is ascending: nothing later can enter either
-        list_insert<KC, true>(dl, jl, d, j);
-      }
-    }
-  }
-  if (w == 0 && row < N) {
-    int32_t* out = idx + (cb + row) * k;
-#pragma unroll
-    for (int t = 0; t < KC; ++t)
-      if (t < k) out[t] = Clouds::kPacked ? (int)cb + jl[t] : jl[t];
-    fill_short_list<KC>(jl, k, N, Clouds::kPacked ? (int)cb : 0, out);      // fewer than k candidates below +inf (knn_common.h)
-  }
+  // ---- the 4 per-wave lists into wave 0 ----
+  merge_lists_write<KC, Clouds::kPacked>(smem, dl, jl, w, lane, w == 0, true, row < N, idx, cb + row, k, N, (int)cb);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -337,6 +294,10 @@ __global__ __launch_bounds__(256, (knn_min_waves<CP, KC>())) void knn_kernel(con
 //   two lanes per row, each with its own register-resident sorted list over its candidate subset.
 // Block = 64 query rows x 2 candidate halves (4 waves); 64-candidate LDS tiles, double buffered, next
 // tile prefetched into registers under the MFMAs; 4 lists per row merged through LDS.
+// This kernel keeps its own text of what knn_scan.h holds for the other scans (ScanLane, load_row_quad, shared_bound, park_and_flag,
+// drain_parked, merge_lists_write: the same code, and the arguments written there hold here).  Calling the shared functions left every
+// resource figure as it was, yet the KC = 40 and KC = 64 instances (256 VGPRs, scratch at two waves) ran 4.5 % and 5.3 % slower at
+// (24, 2048, 64), whichever of the calls was taken back (profiles/knn_scan_shared.txt); with this text the assembly is the parent's.
 template <int CP, int KC, bool VEC>
 __global__ __launch_bounds__(256, (KC <= 20 ? 3 : 2)) void knn_mfma_kernel(const float* __restrict__ x, const float* __restrict__ sq,
                                                                            int N, int C, int64_t ldx, int k,
@@ -564,22 +525,7 @@ __global__ __launch_bounds__(256, (KC <= 20 ? 3 : 2)) void knn_mfma_kernel(const
 // exact filter and the same insert as everywhere else.  Indices are therefore bit-identical to the oracle's; the tests that pin knn_mfma_kernel
 // pin this kernel too (N = 16384 / 65536 compares, and every small-N case with the kernel forced on).
 // No parking area: a survivor is identified by its mask bit, its distance is recomputed anyway.
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-
-__device__ __forceinline__ unsigned cvt_pk_bf16(float lo, float hi) {
-  unsigned r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
-// (x0, x1) -> packed bf16 pairs of the two leading split terms
-__device__ __forceinline__ void split2_pair(float x0, float x1, unsigned& h, unsigned& m) {
-  h = cvt_pk_bf16(x0, x1);
-  const float r0 = x0 - __uint_as_float(h << 16);
-  const float r1 = x1 - __uint_as_float(h & 0xffff0000u);
-  m = cvt_pk_bf16(r0, r1);
-}
-
-template <int KC, bool UNUSED = true>
+template <int KC>
 struct Bf16fCfg {
   static constexpr int OCC = (KC <= 20) ? 3 : 2;
 };
@@ -588,7 +534,6 @@ template <int KC>
 __global__ __launch_bounds__(256, (Bf16fCfg<KC>::OCC)) void knn_bf16f_kernel(const float* __restrict__ x, const float* __restrict__ sq,
                                                                             int N, int C, int64_t ldx, int k,
                                                                             int32_t* __restrict__ idx, const float* __restrict__ tau0) {
-  using f32x16 = __attribute__((ext_vector_type(16))) float;
   constexpr int CP = 64;
   constexpr int TJM = 64;
   constexpr unsigned CS = TJM * 16 + 16;     // bytes per 8-channel chunk of one bf16 plane: [cand][8 bf16], padded (bank shift of 4)
@@ -604,44 +549,19 @@ __global__ __launch_bounds__(256, (Bf16fCfg<KC>::OCC)) void knn_bf16f_kernel(con
   float* sjs = xc + TJM * RS;                                      // [TJM]
   volatile float* thrw = sjs + TJM;                                // [4 lists][64 rows]
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int w = tid >> 6;
-  const int l31 = lane & 31, h = lane >> 5;
-  const int qg = w & 1;
-  const int cs = w >> 1;
+  const ScanLane m;
+  const int tid = m.tid, l31 = m.l31, h = m.h, cbase = m.cbase, lid = m.lid, rslot = m.rslot;
   const int b = blockIdx.y;
   const int row0 = blockIdx.x * ROWS;
-  const int row = row0 + qg * 32 + l31;
+  const int row = row0 + rslot;
   const float* xb = x + (int64_t)b * N * ldx;
   const float* sqb = sq + (int64_t)b * N;
   const int rowc = row < N ? row : N - 1;
-  const int cbase = cs * 32;
-  const int lid = cs * 2 + h;
-  const int rslot = qg * 32 + l31;
   const float si = sqb[rowc];
-  const float t0 = tau0 ? next_up(tau0[(int64_t)b * N + rowc]) : INFINITY;      // seed bound, as in knn_mfma_kernel
-  const float* xi_row = xb + (int64_t)rowc * ldx;
+  const float t0 = tau0 ? next_up(tau0[(int64_t)b * N + rowc]) : INFINITY;      // seed bound: knn_mfma_kernel's t0 (its own line there)
 
-  // B operand: this lane's query row, channels 16 s + 8 h + (0..7), two bf16 planes
-  bf16x8 q1[4], q2[4];
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    float v[8];
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const int c = 16 * s + 8 * h + 4 * e;
-      float4 t4 = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (c < C) t4 = *reinterpret_cast<const float4*>(xi_row + c);
-      v[4 * e] = t4.x; v[4 * e + 1] = t4.y; v[4 * e + 2] = t4.z; v[4 * e + 3] = t4.w;
-    }
-    unsigned hh[4], mm[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) split2_pair(v[2 * e], v[2 * e + 1], hh[e], mm[e]);
-    const uint4 H4 = make_uint4(hh[0], hh[1], hh[2], hh[3]), M4 = make_uint4(mm[0], mm[1], mm[2], mm[3]);
-    q1[s] = *reinterpret_cast<const bf16x8*>(&H4);
-    q2[s] = *reinterpret_cast<const bf16x8*>(&M4);
-  }
+  bf16x8 q1[4], q2[4];                       // B operand
+  split_query_planes(xb + (int64_t)rowc * ldx, C, h, q1, q2);
   // fp32 copy of the block's query rows for the exact re-check
   for (int e = tid; e < ROWS * (CP / 4); e += 256) {
     const int r = e / (CP / 4), c4 = (e % (CP / 4)) * 4;
@@ -653,11 +573,7 @@ __global__ __launch_bounds__(256, (Bf16fCfg<KC>::OCC)) void knn_bf16f_kernel(con
 
   float dl[KC];
   int jl[KC];
-#pragma unroll
-  for (int t = 0; t < KC; ++t) {
-    dl[t] = INFINITY;
-    jl[t] = 0x7fffffff;
-  }
+  list_init<KC>(dl, jl);
 
   // candidate tile: 64 rows x 64 channels -> registers (float4 pieces) -> two bf16 planes in LDS
   constexpr int NV = (TJM * (CP / 4)) / 256;   // 4
@@ -670,11 +586,7 @@ __global__ __launch_bounds__(256, (Bf16fCfg<KC>::OCC)) void knn_bf16f_kernel(con
       const int r = e / (CP / 4);
       const int c4 = (e % (CP / 4)) * 4;
       const int j = j0 + r;
-      const int jc = j < N ? j : N - 1;
-      const int cc = c4 < C ? c4 : C - 4;
-      const float4 t4 = *reinterpret_cast<const float4*>(xb + (int64_t)jc * ldx + cc);
-      const bool ok = c4 < C;
-      pre[i] = make_float4(ok ? t4.x : 0.f, ok ? t4.y : 0.f, ok ? t4.z : 0.f, ok ? t4.w : 0.f);
+      pre[i] = load_row_quad<true>(xb, ldx, j < N ? j : N - 1, c4, C, true);
     }
     if (tid < TJM) pre_s = (j0 + tid < N) ? sqb[j0 + tid] : INFINITY;
   };
@@ -747,7 +659,7 @@ __global__ __launch_bounds__(256, (Bf16fCfg<KC>::OCC)) void knn_bf16f_kernel(con
         const lmask_t live = m_ine((int)mask, 0);
         const int g = __builtin_ctz(mask | 0x80000000u) & 15;
         mask &= mask - 1u;
-        const int i = (g & 3) + 8 * (g >> 2) + 4 * h;
+        const int i = d_layout_index(g, h);
         const int j = j0 + cbase + i;
         const float* xj = xc + (cbase + i) * RS;             // fp32 copy of the candidate row (rows past N: zeros, s_j = +inf)
         const float* xi = xq + rslot * RS;
@@ -785,39 +697,8 @@ __global__ __launch_bounds__(256, (Bf16fCfg<KC>::OCC)) void knn_bf16f_kernel(con
     }
   }
 
-  // ---- merge: 4 lists per query row -> lanes 0..31 of waves 0,1 ----
-  __syncthreads();
-  float* md = reinterpret_cast<float*>(smem_raw);
-  int* mj = reinterpret_cast<int*>(smem_raw) + ROWS * KC;
-#pragma unroll 1
-  for (int src = 1; src < 4; ++src) {
-    if (src > 1) __syncthreads();
-    if (lid == src) {
-#pragma unroll
-      for (int t = 0; t < KC; ++t) {
-        md[t * ROWS + rslot] = dl[t];
-        mj[t * ROWS + rslot] = jl[t];
-      }
-    }
-    __syncthreads();
-    if (cs == 0) {
-#pragma unroll 1
-      for (int t = 0; t < KC; ++t) {
-        const float d = (h == 0) ? md[t * ROWS + rslot] : INFINITY;
-        const int j = (h == 0) ? mj[t * ROWS + rslot] : 0x7fffffff;
-        const lmask_t need = key_less<true>(d, j, dl[KC - 1], jl[KC - 1]);
-        if (need == 0) break;
-        list_insert<KC, true>(dl, jl, d, j);
-      }
-    }
-  }
-  if (lid == 0 && row < N) {
-    int32_t* out = idx + ((int64_t)b * N + row) * k;
-#pragma unroll
-    for (int t = 0; t < KC; ++t)
-      if (t < k) out[t] = jl[t];
-    fill_short_list<KC>(jl, k, N, 0, out);                                  // fewer than k candidates below +inf (knn_common.h)
-  }
+  merge_lists_write<KC, false>(reinterpret_cast<float*>(smem_raw), dl, jl, lid, rslot, m.cs == 0, h == 0, row < N, idx,
+                               (int64_t)b * N + row, k, N, 0);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -910,7 +791,6 @@ __global__ __launch_bounds__(256, ((LX || NPR != 1) ? 3 : 4)) void knn_bf16a_ker
                                                            int64_t ldx, int k, const float* __restrict__ tau0, int cap,
                                                            unsigned long long* __restrict__ ent, int* __restrict__ cnt,
                                                            int ka_tight_mask) {
-  using f32x16 = __attribute__((ext_vector_type(16))) float;
   constexpr int CP = 64;
   constexpr int TJM = 64;
   constexpr unsigned CS = TJM * 16 + 16;
@@ -936,48 +816,25 @@ __global__ __launch_bounds__(256, ((LX || NPR != 1) ? 3 : 4)) void knn_bf16a_ker
   volatile qent_t* queue = reinterpret_cast<qent_t*>(hist + 4 * ROWS);
   volatile int* flags = reinterpret_cast<int*>(const_cast<qent_t*>(queue) + 4 * QN);   // [2]: a row crossed the mark in tile t (t & 1)
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int w = tid >> 6;
-  const int l31 = lane & 31, h = lane >> 5;
-  const int qg = w & 1;
-  const int cs = w >> 1;
+  const ScanLane m;
+  const int tid = m.tid, lane = m.lane, w = m.w, l31 = m.l31, h = m.h, qg = m.qg, cbase = m.cbase, rslot = m.rslot;
   const int b = blockIdx.y;
   const int N = cl.size(b);
   if (Clouds::kPacked && (int)blockIdx.x * ROWS >= N) return;
   const int row0 = blockIdx.x * ROWS;
-  const int row = row0 + qg * 32 + l31;
+  const int row = row0 + rslot;
   const float* xb = x + cl.base(b) * ldx;
   const float* sqb = sq + cl.base(b);
   const int rowc = row < N ? row : N - 1;
-  const int cbase = cs * 32;
-  const int rslot = qg * 32 + l31;
   const float si = sqb[rowc];
-  const float* xi_row = xb + (int64_t)rowc * ldx;
   const int64_t grow0 = cl.base(b) + row0;                         // global row of the block's first query row
   const int trig = cap - (LX ? KA_SLACK_LX : KA_SLACK);
   volatile qent_t* myq = queue + w * QN;
   constexpr float C1 = (NPR == 3) ? KA_C1 : 0.5f * (1.0f - 1.0f / 64.0f);       // the filter's (1 - E') / 2
   const int tight_mask = ka_tight_mask;
 
-  bf16x8 q1[4], q2[4];
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    float v[8];
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const int c = 16 * s + 8 * h + 4 * e;
-      float4 t4 = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (c < C) t4 = *reinterpret_cast<const float4*>(xi_row + c);
-      v[4 * e] = t4.x; v[4 * e + 1] = t4.y; v[4 * e + 2] = t4.z; v[4 * e + 3] = t4.w;
-    }
-    unsigned hh[4], mm[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) split2_pair(v[2 * e], v[2 * e + 1], hh[e], mm[e]);
-    const uint4 H4 = make_uint4(hh[0], hh[1], hh[2], hh[3]), M4 = make_uint4(mm[0], mm[1], mm[2], mm[3]);
-    q1[s] = *reinterpret_cast<const bf16x8*>(&H4);
-    q2[s] = *reinterpret_cast<const bf16x8*>(&M4);
-  }
+  bf16x8 q1[4], q2[4];                       // B operand (NPR == 1: q2 is not used)
+  split_query_planes(xb + (int64_t)rowc * ldx, C, h, q1, q2);
   for (int e = tid; e < ROWS * (CP / 4); e += 256) {
     const int r = e / (CP / 4), c4 = (e % (CP / 4)) * 4;
     const int rr = (row0 + r < N) ? row0 + r : N - 1;
@@ -1009,11 +866,7 @@ __global__ __launch_bounds__(256, ((LX || NPR != 1) ? 3 : 4)) void knn_bf16a_ker
       const int r = e / (CP / 4);
       const int c4 = (e % (CP / 4)) * 4;
       const int j = j0 + r;
-      const int jc = j < N ? j : N - 1;
-      const int cc = c4 < C ? c4 : C - 4;
-      const float4 t4 = *reinterpret_cast<const float4*>(xb + (int64_t)jc * ldx + cc);
-      const bool ok = c4 < C;
-      pre[i] = make_float4(ok ? t4.x : 0.f, ok ? t4.y : 0.f, ok ? t4.z : 0.f, ok ? t4.w : 0.f);
+      pre[i] = load_row_quad<true>(xb, ldx, j < N ? j : N - 1, c4, C, true);
     }
     if (tid < TJM) pre_s = (j0 + tid < N) ? sqb[j0 + tid] : INFINITY;
   };
@@ -1193,7 +1046,7 @@ __global__ __launch_bounds__(256, ((LX || NPR != 1) ? 3 : 4)) void knn_bf16a_ker
         const int g = __builtin_ctz(mask | 0x80000000u) & 15;
         const int before = __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
         if (has) {
-          const unsigned ci = (unsigned)(cbase + (g & 3) + 8 * (g >> 2) + 4 * h);
+          const unsigned ci = (unsigned)(cbase + d_layout_index(g, h));
           myq[qn + before] = LX ? (qent_t)(((unsigned)l31 << 6) | ci) : (qent_t)(((unsigned)l31 << 27) | ((unsigned)j0 + ci));
           mask &= mask - 1u;
         }

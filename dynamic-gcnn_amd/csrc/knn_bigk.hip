@@ -1,11 +1,10 @@
 // knn_bigk.hip -- K1 for 64 < k <= 256: one exact all-pairs scan for every width 1 <= C <= 1024, dense clouds and packed towers.
 //
 // MUST be compiled with -ffp-contract=off (csrc/Makefile).  Distances are the normative ones of oracle/knn_oracle.c, produced by
-// the step loop of knn_wide.hip:knn_wide_kernel unchanged: s_i from sqnorm_kernel / sqnorm_wide_kernel, p_ij the fmaf chain over c
-// ascending from +0 (v_mfma_f32_32x32x2_f32 over 64-channel slabs, the 16 accumulators of a 64-candidate tile carried from slab to
-// slab, channels past C +0 on both operands -- for ANY C, so C <= 4 is one partly filled slab), D = fmaf(-2, p, fl(s_i + s_j)).
+// the code that knn_wide_kernel runs: s_i from sqnorm_kernel / sqnorm_wide_kernel, SlabStage and scan_dist of knn_scan.h -- for ANY
+// C, so C <= 4 is one partly filled slab.  What differs from knn_wide_kernel is the selection.
 //
-// Selection.  The list-keeping kernels hold KC sorted (d, j) pairs per lane in registers (KC = 64 already takes 344 registers in
+// Selection.  The list-keeping kernels hold KC sorted (d, j) pairs per lane in registers (KC = 64 already takes 345 registers in
 // knn_wide_kernel); past 64 the scan keeps no list at all.  Every query row owns a buffer of `cap` 64-bit keys (knn_key: unsigned
 // order == (D~, j) order, D~ = +inf where D is NaN) and a bound key, ~0 at first.  A candidate whose key is below the row's bound
 // is appended (LDS atomic on the row's count, one 8-byte store).  At every tile boundary a row whose count has passed the mark
@@ -40,11 +39,9 @@
 //    VGPRs (float4 loader) / 118 (scalar loader); 8 keys per lane: 130 / 130; no AGPRs, no scratch in any instance (6 ... 28 SGPRs
 //    spilled to VGPR lanes), so nothing in the tile loop touches scratch; LDS 68,864 bytes; 2 waves per SIMD = two blocks per CU,
 //    which is what the LDS admits.  Times: profiles/knn_bigk.txt.
-#include "knn_common.h"
+#include "knn_scan.h"
 
 namespace {
-
-constexpr int ROWS = 64;
 
 // One step of the bitonic sorting network over n = 64 E keys, element i = 64 q + lane in key[q] of `lane`: compare-exchange of
 // elements i and i ^ J within sorted runs of S2, ascending where (i & S2) == 0.  J >= 64: two registers of the same lane; J < 64:
@@ -76,16 +73,12 @@ __device__ __forceinline__ void wave_sort_all(unsigned long long (&key)[E], int 
   if constexpr (S2 < 64 * E) wave_sort_all<E, 2 * S2>(key, lane);
 }
 
-// Block = 64 query rows x 2 candidate halves (4 waves), D layout and slab staging as in knn_wide_kernel.  E = cap / 64.
+// Block and D layout: ScanLane; slab staging: SlabStage (knn_scan.h).  E = cap / 64.
 template <int E, bool VEC, class Clouds>
 __global__ __launch_bounds__(256, 2) void knn_bigk_kernel(const float* __restrict__ x, const float* __restrict__ sq, Clouds cl, int C,
                                                           int64_t ldx, int k, unsigned long long* ent, int32_t* __restrict__ idx) {
-  using f32x16 = __attribute__((ext_vector_type(16))) float;
-  constexpr int SL = 64;                     // channels per slab
-  constexpr int TJM = 64;                    // candidates per tile: 32 per candidate-half wave
-  constexpr int ST = TJM + 2;                // k-major slab tile [SL][ST]
-  constexpr int TILE_F = SL * ST;
-  constexpr int NV = (TJM * (SL / 4)) / 256;  // float4 staged per thread per slab tile
+  using Stage = SlabStage<VEC>;
+  constexpr int SL = Stage::SL, TJM = Stage::TJM, TILE_F = Stage::TILE_F;
   constexpr int CAP = 64 * E;
   constexpr int TRIG = CAP - TJM;            // a row whose count is above this at a tile boundary is compacted
   __shared__ __attribute__((aligned(16))) float smem[4 * TILE_F + 2 * TJM];
@@ -93,81 +86,34 @@ __global__ __launch_bounds__(256, 2) void knn_bigk_kernel(const float* __restric
   __shared__ int cnt_s[ROWS];                // keys in the row's buffer
   float* sjs = smem + 4 * TILE_F;            // [2][TJM], by tile parity
 
+  // The mapping is ScanLane's, written out: `m` goes to slab_mfma only.  With lane and w taken from `m` the 64-bit compares of
+  // wave_sort_all come out with the opposite polarity (v_cmp_lt_u64 for v_cmp_ge_u64, the selects swapped) and the 8-key instances
+  // run 0.8 % slower at (8, 16384, 64, 256); with these lines the network is the one measured in profiles/knn_bigk.txt
+  // (profiles/knn_scan_shared.txt).
+  const ScanLane m;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int w = tid >> 6;
   const int l31 = lane & 31, h = lane >> 5;
-  const int qg = w & 1;                      // which 32 query rows of the block
-  const int cs = w >> 1;                     // which 32 candidates of every 64-candidate tile
+  const int qg = w & 1;
+  const int cs = w >> 1;
   const int b = blockIdx.y;
   const int N = cl.size(b);
   const int row0 = blockIdx.x * ROWS;
   if (Clouds::kPacked && row0 >= N) return;
   const int64_t cb = cl.base(b);
   const int row = row0 + qg * 32 + l31;
-  const float* xb = x + cb * ldx;
   const float* sqb = sq + cb;
   const int rowc = row < N ? row : N - 1;
   const float si = sqb[rowc];
 
-  // ---- slab tiles (knn_wide_kernel): global -> registers one step ahead, transposed ([c][row]) into the other LDS buffer after the
-  // current step's MFMAs; one barrier per step.  VEC (16-byte aligned rows, C % 4 == 0): one unconditional float4 load per piece from
-  // a clamped, always valid address.  Rows past N repeat row N - 1 (never appended, never written); channel quads past C are zeroed.
-  float4 prec[NV], preq[NV];
-  float pre_s = INFINITY;
-  auto load4 = [&](int r, int ch, bool live) -> float4 {
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (VEC) {
-      const int cc = ch < C ? ch : C - 4;
-      const float4 t4 = *reinterpret_cast<const float4*>(xb + (int64_t)r * ldx + cc);
-      const bool ok = ch < C;
-      v.x = ok ? t4.x : 0.f; v.y = ok ? t4.y : 0.f; v.z = ok ? t4.z : 0.f; v.w = ok ? t4.w : 0.f;
-    } else if (live) {
-      const float* src = xb + (int64_t)r * ldx + ch;
-      if (ch + 0 < C) v.x = src[0];
-      if (ch + 1 < C) v.y = src[1];
-      if (ch + 2 < C) v.z = src[2];
-      if (ch + 3 < C) v.w = src[3];
-    }
-    return v;
-  };
-  auto fetch = [&](int j0, int c0) {
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int e = tid + 256 * i;
-      const int r = e >> 4;
-      const int ch = c0 + (e & 15) * 4;
-      const int j = j0 + r, q = row0 + r;
-      prec[i] = load4(j < N ? j : N - 1, ch, j < N);
-      preq[i] = load4(q < N ? q : N - 1, ch, true);
-    }
-    if (c0 == 0 && tid < TJM) pre_s = (j0 + tid < N) ? sqb[j0 + tid] : INFINITY;
-  };
-  auto stash = [&](int buf, int tpar, bool first_slab) {
-    float* dc = smem + buf * 2 * TILE_F;
-    float* dqr = dc + TILE_F;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int e = tid + 256 * i;
-      const int r = e >> 4;
-      const int c4 = (e & 15) * 4;
-      dc[(c4 + 0) * ST + r] = prec[i].x;
-      dc[(c4 + 1) * ST + r] = prec[i].y;
-      dc[(c4 + 2) * ST + r] = prec[i].z;
-      dc[(c4 + 3) * ST + r] = prec[i].w;
-      dqr[(c4 + 0) * ST + r] = preq[i].x;
-      dqr[(c4 + 1) * ST + r] = preq[i].y;
-      dqr[(c4 + 2) * ST + r] = preq[i].z;
-      dqr[(c4 + 3) * ST + r] = preq[i].w;
-    }
-    if (first_slab && tid < TJM) sjs[tpar * TJM + tid] = pre_s;
-  };
-
+  // (rows past N repeat row N - 1: never appended, never written)
+  Stage stage(x + cb * ldx, sqb, ldx, N, C, row0, tid, smem, sjs);
   const int nt = (N + TJM - 1) / TJM;
   const int ns = (C + SL - 1) / SL;
   const int nu = nt * ns;                    // steps of the flattened (tile, slab) sequence
-  fetch(0, 0);
-  stash(0, 0, true);
+  stage.fetch(0, 0);
+  stage.stash(0, 0, true);
   if (tid < ROWS) {
     bnd[tid] = ~0ull;
     cnt_s[tid] = 0;
@@ -228,22 +174,9 @@ __global__ __launch_bounds__(256, 2) void knn_bigk_kernel(const float* __restric
     const int j0 = t * TJM;
     const int sn = (s + 1 < ns) ? s + 1 : 0; // the next step's slab and tile
     const int tn = (s + 1 < ns) ? t : t + 1;
-    if (u + 1 < nu) fetch(tn * TJM, sn * SL);
+    if (u + 1 < nu) stage.fetch(tn * TJM, sn * SL);
     if (j0 + cbase < N) {                    // wave-uniform, the same for every slab of a tile
-      const float* ap = smem + buf * 2 * TILE_F + h * ST + cbase + l31;          // A: candidate cbase + l31, channel 2 s2 + h
-      const float* bp = smem + buf * 2 * TILE_F + TILE_F + h * ST + qg * 32 + l31;   // B: query row, channel 2 s2 + h
-      {
-        // operand rings, two MFMAs deep (knn_wide_kernel)
-        constexpr int NS = SL / 2;
-        float a0 = ap[0], b0 = bp[0], a1 = ap[2 * ST], b1 = bp[2 * ST];
-#pragma unroll
-        for (int s2 = 0; s2 < NS; s2 += 2) {
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc, 0, 0, 0);
-          if (s2 + 2 < NS) { a0 = ap[2 * (s2 + 2) * ST]; b0 = bp[2 * (s2 + 2) * ST]; }
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc, 0, 0, 0);
-          if (s2 + 3 < NS) { a1 = ap[2 * (s2 + 3) * ST]; b1 = bp[2 * (s2 + 3) * ST]; }
-        }
-      }
+      stage.slab_mfma(acc, buf, m);
       if (s == ns - 1) {
         // ---- the chain is complete: the keys of this lane's 16 candidates against the row's bound ----
         const unsigned long long bk = bnd[rslot];
@@ -254,10 +187,8 @@ __global__ __launch_bounds__(256, 2) void knn_bigk_kernel(const float* __restric
           const float sv[4] = {s4.x, s4.y, s4.z, s4.w};
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            const int j = j0 + cbase + 8 * q + 4 * h + e;
-            const float tt = si + sv[e];
-            // (tt - 2 p in ONE rounding: 2 p is exact, so the fused form equals the oracle's  tt - fl(2 p)  bit for bit)
-            const float d = __builtin_fmaf(-2.0f, acc[4 * q + e], tt);
+            const int j = j0 + cbase + d_layout_index(4 * q + e, h);
+            const float d = scan_dist(acc[4 * q + e], si, sv[e]);
             const unsigned long long key = knn_key((d != d) ? INFINITY : d, j);
             if (row < N && j < N && key < bk) {
               const int pos = atomicAdd(&cnt_s[rslot], 1);       // < CAP by the invariant
@@ -272,7 +203,7 @@ __global__ __launch_bounds__(256, 2) void knn_bigk_kernel(const float* __restric
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
     }
-    if (u + 1 < nu) stash(buf ^ 1, tn & 1, sn == 0);
+    if (u + 1 < nu) stage.stash(buf ^ 1, tn & 1, sn == 0);
     __syncthreads();
     s = sn;
     t = tn;
