@@ -1299,6 +1299,14 @@ void launch_knn_wide(const float* x, const float* sq, const int32_t* seg_off, in
 int knn_bigk_cap(int k);
 void launch_knn_bigk(const float* x, const float* sq, const int32_t* seg_off, int ny, int max_n, int C, int64_t ldx, int k, int vec_ok,
                      int32_t* idx, unsigned long long* ent, hipStream_t st);
+// s_i of `rows` rows of any width up to 1024 (every entry here, and knn_cross.hip once per operand)
+void launch_sqnorm_rows(const float* x, int64_t ldx, int64_t rows, int C, float* sq, hipStream_t st) {
+  if (C > 128) {                             // [64][C + 1] floats would not fit: the chunked form of knn_wide.hip, the same sum
+    launch_sqnorm_wide(x, ldx, rows, C, sq, st);
+    return;
+  }
+  launch(sqnorm_kernel, dim3((unsigned)cdiv(rows, SQ_ROWS)), dim3(256), sizeof(float) * SQ_ROWS * (C + 1), st, x, ldx, rows, C, sq);
+}
 }  // namespace dg
 
 static bool knn_append_lx(int N) { return N < 8192; }     // which form of the append scan (knn_bf16a_kernel<LX>)
@@ -1495,14 +1503,7 @@ struct KnnCall {
 };
 int knn_vec_ok(const float* x, int64_t ldx) { return (ldx % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0); }
 
-void launch_sqnorm(const KnnCall& a, int64_t rows) {
-  if (a.C > 128) {                           // [64][C + 1] floats would not fit: the chunked form of knn_wide.hip, the same sum
-    dg::launch_sqnorm_wide(a.x, a.ldx, rows, a.C, a.w.s_i(), a.st);
-    return;
-  }
-  dg::launch(sqnorm_kernel, dim3((unsigned)dg::cdiv(rows, SQ_ROWS)), dim3(256), sizeof(float) * SQ_ROWS * (a.C + 1), a.st, a.x, a.ldx, rows,
-             a.C, a.w.s_i());
-}
+void launch_sqnorm(const KnnCall& a, int64_t rows) { dg::launch_sqnorm_rows(a.x, a.ldx, rows, a.C, a.w.s_i(), a.st); }
 
 // Raw coordinates (C <= 4): the histogram bound of every row.  Null (no bound) when it is switched off (stride 0, or a cloud under 256
 // points), VALU distances are forced, the kernel's precondition N >= 4 k stride fails for the smallest cloud, or there is no room.

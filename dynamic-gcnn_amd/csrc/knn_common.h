@@ -1,5 +1,5 @@
 // knn_common.h -- the cloud maps (dense / packed tower), lane-mask selects and the register-resident sorted (d, j) list shared by the
-// k-NN kernels (knn.hip, knn_grid.hip, knn_wide.hip, knn_bigk.hip).  What only the all-pairs scans share is in knn_scan.h.
+// k-NN kernels (knn.hip, knn_grid.hip, knn_wide.hip, knn_bigk.hip, knn_cross.hip).  What only the all-pairs scans share is in knn_scan.h.
 #pragma once
 #include "common.h"
 #include <math.h>

@@ -1,7 +1,8 @@
-// knn_scan.h -- the pieces that the all-pairs scan kernels of knn.hip, knn_wide.hip and knn_bigk.hip have in common, each once: the
-// thread mapping and D layout of the matrix-pipe forms, the guarded row-quad load, the channel-slab stage and its MFMA step, the
-// distance, park / flag / drain, the bf16 query planes and the 4-list merge with the index write-out.  The bit-exactness and
-// non-finite-input arguments of these blocks are written here, at the function.
+// knn_scan.h -- the pieces that the all-pairs scan kernels of knn.hip, knn_wide.hip, knn_bigk.hip and knn_cross.hip have in common,
+// each once: the thread mapping and D layout of the matrix-pipe forms, the guarded row-quad load, the channel-slab stage and its MFMA
+// step (and its two-source sibling for the search between two sets), the distance, park / flag / drain, the bf16 query planes and
+// the 4-list merge with the index (and distance) write-out.  The bit-exactness and non-finite-input arguments of these blocks are
+// written here, at the function.
 // ONE SECOND COPY EXISTS: knn.hip:knn_mfma_kernel keeps its own text of the mapping, the guarded load, shared_bound, park_and_flag,
 // drain_parked (all 16 slots at once) and merge_lists_write, for speed (said there).  A change to one of these functions -- a
 // non-finite-input fix above all -- has to be made in that kernel too.  knn_bigk_kernel writes out ScanLane's mapping lines.
@@ -158,6 +159,83 @@ struct SlabStage {
   }
 };
 
+// ---- the same stage with TWO operand sources and a slab width of its own (knn_cross.hip:knn_cross_kernel) ----------------------------
+// SlabStage with the ties between its two tiles cut: the query tile comes from (qb, ldq), rows clamped to M - 1 (never written past
+// M), the candidate tile from (pb, ldp), rows clamped to N - 1 with |p_j|^2 = +inf past N, from spb.  SLV = channels per slab, 64 or
+// 16: a 16-channel slab is one float4 per thread per tile and 8 MFMAs where the 64-channel one is four and 32, for rows of at most 16
+// channels (raw coordinates above all); the zero channels past C change nothing, as said at SlabStage.  Layout, fetch / stash protocol
+// and the MFMA ring are SlabStage's, line for line; with qb == pb, ldq == ldp, M == N and SLV = 64 the two stage the same floats.
+template <bool VEC, int SLV>
+struct CrossSlabStage {
+  static_assert(SLV == 16 || SLV == 64, "CrossSlabStage: slabs of 16 or 64 channels");
+  static constexpr int SL = SLV;             // channels per slab
+  static constexpr int TJM = 64;             // candidates per tile: 32 per candidate-half wave
+  static constexpr int ST = TJM + 2;         // k-major slab tile [SL][ST]
+  static constexpr int TILE_F = SL * ST;
+  static constexpr int QR = SL / 4;          // float4 per row per slab
+  static constexpr int NV = (TJM * QR) / 256;   // float4 staged per thread per slab tile
+
+  const float* __restrict__ qb;              // the query cloud's first row
+  const float* __restrict__ pb;              // the candidate cloud's first row
+  const float* __restrict__ spb;             // ... and its s_j
+  int64_t ldq, ldp;
+  int M, N, C, row0, tid;
+  float* tiles;
+  float* sjs;
+  float4 prec[NV], preq[NV];
+  float pre_s = INFINITY;
+
+  __device__ __forceinline__ CrossSlabStage(const float* qb_, int64_t ldq_, int M_, const float* pb_, const float* spb_, int64_t ldp_,
+                                            int N_, int C_, int row0_, int tid_, float* tiles_, float* sjs_)
+      : qb(qb_), pb(pb_), spb(spb_), ldq(ldq_), ldp(ldp_), M(M_), N(N_), C(C_), row0(row0_), tid(tid_), tiles(tiles_), sjs(sjs_) {}
+
+  __device__ __forceinline__ void fetch(int j0, int c0) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int e = tid + 256 * i;
+      const int r = e / QR;
+      const int ch = c0 + (e % QR) * 4;
+      const int j = j0 + r, q = row0 + r;
+      prec[i] = load_row_quad<VEC>(pb, ldp, j < N ? j : N - 1, ch, C, j < N);
+      preq[i] = load_row_quad<VEC>(qb, ldq, q < M ? q : M - 1, ch, C, true);
+    }
+    if (c0 == 0 && tid < TJM) pre_s = (j0 + tid < N) ? spb[j0 + tid] : INFINITY;
+  }
+  __device__ __forceinline__ void stash(int buf, int tpar, bool first_slab) {
+    float* dc = tiles + buf * 2 * TILE_F;
+    float* dqr = dc + TILE_F;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int e = tid + 256 * i;
+      const int r = e / QR;
+      const int c4 = (e % QR) * 4;
+      dc[(c4 + 0) * ST + r] = prec[i].x;
+      dc[(c4 + 1) * ST + r] = prec[i].y;
+      dc[(c4 + 2) * ST + r] = prec[i].z;
+      dc[(c4 + 3) * ST + r] = prec[i].w;
+      dqr[(c4 + 0) * ST + r] = preq[i].x;
+      dqr[(c4 + 1) * ST + r] = preq[i].y;
+      dqr[(c4 + 2) * ST + r] = preq[i].z;
+      dqr[(c4 + 3) * ST + r] = preq[i].w;
+    }
+    if (first_slab && tid < TJM) sjs[tpar * TJM + tid] = pre_s;
+  }
+  // SL / 2 MFMAs on buffer `buf`: A = candidate cbase + l31, B = query row rslot, channel 2 s2 + h at step s2 (SlabStage::slab_mfma)
+  __device__ __forceinline__ void slab_mfma(f32x16& acc, int buf, const ScanLane& m) const {
+    const float* ap = tiles + buf * 2 * TILE_F + m.h * ST + m.cbase + m.l31;
+    const float* bp = tiles + buf * 2 * TILE_F + TILE_F + m.h * ST + m.qg * 32 + m.l31;
+    constexpr int NS = SL / 2;
+    float a0 = ap[0], b0 = bp[0], a1 = ap[2 * ST], b1 = bp[2 * ST];
+#pragma unroll
+    for (int s2 = 0; s2 < NS; s2 += 2) {
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc, 0, 0, 0);
+      if (s2 + 2 < NS) { a0 = ap[2 * (s2 + 2) * ST]; b0 = bp[2 * (s2 + 2) * ST]; }
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc, 0, 0, 0);
+      if (s2 + 3 < NS) { a1 = ap[2 * (s2 + 3) * ST]; b1 = bp[2 * (s2 + 3) * ST]; }
+    }
+  }
+};
+
 // ---- shared selection bound, park / flag / drain over the D layout: NP slots of a lane's 16 at a time (knn_wide_kernel: two halves
 // of 8, the only caller; knn_mfma_kernel's own copy does all 16 at once) ----
 // The candidates of a query row are split over FOUR sorted lists (KC entries each, KC % 4 == 0).  If every list holds at least KC/4
@@ -263,10 +341,9 @@ __device__ __forceinline__ void split_query_planes(const float* __restrict__ xi_
 // PACKED: the keys hold the cloud-local j and `base`, the cloud's first tower row, is added when the indices are written.
 // Non-finite input: every trip count is KC or k and every store goes to the row's LDS slot or its k output slots (out = idx +
 // grow k); rows with fewer than k candidates below +inf end with open slots, which fill_short_list (knn_common.h) fills.
-template <int KC, bool PACKED>
-__device__ __forceinline__ void merge_lists_write(float* smem, float (&dl)[KC], int (&jl)[KC], int lid, int rslot, bool dst_wave,
-                                                  bool active, bool row_ok, int32_t* __restrict__ idx, int64_t grow, int k, int N,
-                                                  int base) {
+template <int KC>
+__device__ __forceinline__ void merge_lists(float* smem, float (&dl)[KC], int (&jl)[KC], int lid, int rslot, bool dst_wave,
+                                            bool active) {
   __syncthreads();
   float* md = smem;
   int* mj = reinterpret_cast<int*>(smem + ROWS * KC);
@@ -292,11 +369,40 @@ __device__ __forceinline__ void merge_lists_write(float* smem, float (&dl)[KC], 
       }
     }
   }
+}
+template <int KC, bool PACKED>
+__device__ __forceinline__ void merge_lists_write(float* smem, float (&dl)[KC], int (&jl)[KC], int lid, int rslot, bool dst_wave,
+                                                  bool active, bool row_ok, int32_t* __restrict__ idx, int64_t grow, int k, int N,
+                                                  int base) {
+  merge_lists<KC>(smem, dl, jl, lid, rslot, dst_wave, active);
   if (lid == 0 && row_ok) {
     int32_t* out = idx + grow * k;
 #pragma unroll
     for (int t = 0; t < KC; ++t)
       if (t < k) out[t] = PACKED ? base + jl[t] : jl[t];
+    fill_short_list<KC>(jl, k, N, PACKED ? base : 0, out);
+  }
+}
+// The same merge with the selected D~ written beside the indices (knn_cross_kernel): dist null, or k floats per row in the order of
+// idx.  An open slot of a list holds d = +inf (list_init; an entry is listed only with d < thr <= +inf), so the slots that
+// fill_short_list fills -- candidates at D~ = +inf, by its argument -- carry +inf without another pass.  N and base are the
+// CANDIDATE cloud's size and first tower row, grow the query's global row.
+template <int KC, bool PACKED>
+__device__ __forceinline__ void merge_lists_write_dist(float* smem, float (&dl)[KC], int (&jl)[KC], int lid, int rslot, bool dst_wave,
+                                                       bool active, bool row_ok, int32_t* __restrict__ idx, float* __restrict__ dist,
+                                                       int64_t grow, int k, int N, int base) {
+  merge_lists<KC>(smem, dl, jl, lid, rslot, dst_wave, active);
+  if (lid == 0 && row_ok) {
+    int32_t* out = idx + grow * k;
+#pragma unroll
+    for (int t = 0; t < KC; ++t)
+      if (t < k) out[t] = PACKED ? base + jl[t] : jl[t];
+    if (dist) {
+      float* dout = dist + grow * k;
+#pragma unroll
+      for (int t = 0; t < KC; ++t)
+        if (t < k) dout[t] = dl[t];
+    }
     fill_short_list<KC>(jl, k, N, PACKED ? base : 0, out);
   }
 }

@@ -714,6 +714,49 @@ def knn_packed(x2d, k, seg, seed=None):
     return idx
 
 
+KNN_CROSS_MAX_K = 64                         # knn_cross.hip: the large-k scan searches a cloud against itself only
+
+
+def knn_cross(q2d, p2d, B, M, N, k, qseg=None, pseg=None, want_dist=False):
+    """k-NN between two point sets (dgcnn_knn_cross_f32): idx (B,M,k) int32 -- for every row of q2d (B*M, C) the k nearest rows of
+    p2d (B*N, C) of the same cloud, cloud-local j; with want_dist also dist (B,M,k) float32, the selected D~ in the same order.
+    qseg / pseg (both or neither): packed towers (Segments; B = 1, M / N = the towers' rows) of the same number of clouds: query
+    cloud b searches candidate cloud b, idx holds rows of the candidate tower.  Returns idx or (idx, dist)."""
+    C = q2d.shape[1]
+    if p2d.shape[1] != C:
+        raise ValueError("knn_cross: queries have %d channels, points %d" % (C, p2d.shape[1]))
+    if (qseg is None) != (pseg is None):
+        raise ValueError("knn_cross: both towers packed (qseg and pseg) or neither")
+    if k > KNN_CROSS_MAX_K:
+        raise ValueError("knn_cross: k=%d > %d: the search between two sets keeps at most %d neighbours" % (k, KNN_CROSS_MAX_K,
+                                                                                                       KNN_CROSS_MAX_K))
+    if qseg is not None:
+        if qseg.nseg != pseg.nseg:
+            raise ValueError("knn_cross: %d query clouds, %d candidate clouds" % (qseg.nseg, pseg.nseg))
+        if q2d.shape[0] != qseg.rows or p2d.shape[0] != pseg.rows:
+            raise ValueError("knn_cross: offsets end at %d / %d, the towers have %d / %d rows" % (qseg.rows, pseg.rows, q2d.shape[0],
+                                                                                                p2d.shape[0]))
+        pseg.check_k(k)
+        nseg, q_rows, p_rows, max_m, min_n, max_n = qseg.nseg, qseg.rows, pseg.rows, qseg.max_n, pseg.min_n, pseg.max_n
+        qo, po = qseg.device(q2d.device), pseg.device(p2d.device)
+        pairs = float((np.diff(qseg.host) * np.diff(pseg.host)).sum())
+    else:
+        if k <= 0 or k > N:
+            raise ValueError("knn_cross: k=%d must be in [1, N=%d]" % (k, N))
+        nseg, q_rows, p_rows, max_m, min_n, max_n = B, B * M, B * N, M, N, N
+        qo = po = None
+        pairs = float(B) * M * N
+    idx = torch.empty((B, M, k), dtype=torch.int32, device=q2d.device)
+    dist = torch.empty((B, M, k), dtype=torch.float32, device=q2d.device) if want_dist else None
+    ws, nws = _knn_workspace(q2d, "dgcnn_knn_cross_workspace_bytes", q_rows, p_rows)
+    kc = 8 if k <= 8 else 20 if k <= 20 else 40 if k <= 40 else 64
+    Cp = 16 if C <= 16 else (C + 63) // 64 * 64                  # channels rounded up to whole slabs (16 or 64 wide)
+    tag = "knn_cross_call<C%d,k%d>[%s+knn_cross_kernel]" % (Cp, kc, _sqnorm_name(C))
+    H.call("dgcnn_knn_cross_f32", q2d.data_ptr(), H.ld2(q2d), p2d.data_ptr(), H.ld2(p2d), C, k, nseg, H._p(qo), H._p(po), q_rows, p_rows,
+           max_m, min_n, max_n, idx.data_ptr(), H._p(dist), ws.data_ptr(), nws, tag=tag, work=2.0 * pairs * C)
+    return (idx, dist) if want_dist else idx
+
+
 def _tile_m(M, N):
     """Mirror of gemm.hip:tile_m (only used to name the kernel instance in bench.py's roofline tags)."""
     return 128

@@ -49,12 +49,66 @@ def _segments(points, offsets, ks, bn_per_cloud=False, bn_per_cloud_train=False)
     return seg
 
 
-def k_nn(points, k, offsets=None):
+def _rows_channels(t, what, packed):
+    """(B, rows per cloud, C) of a dense (B,N,C) set, or (1, R, C) of a packed (R,C) / (1,R,C) tower -- from the shape alone"""
+    shp = tuple(t.shape)
+    if packed:
+        if len(shp) == 2:
+            return 1, shp[0], shp[1]
+        if len(shp) == 3 and shp[0] == 1:
+            return 1, shp[1], shp[2]
+        raise ValueError("k_nn: a packed %s tower is (R,C) or (1,R,C), got %s" % (what, shp))
+    if len(shp) != 3:
+        raise ValueError("k_nn: %s must be (B,N,C), got %s" % (what, shp))
+    return shp
+
+
+def _k_nn_cross(points, k, offsets, queries, query_offsets, return_dist):
+    """k_nn between two sets (queries given) or of one set with its distances (return_dist): every check on the host, from shapes and
+    offsets alone, before any device work; then E.knn_cross."""
+    if queries is None and query_offsets is not None:
+        raise ValueError("k_nn: query_offsets without queries")
+    if queries is not None and (offsets is None) != (query_offsets is None):
+        raise ValueError("k_nn: packed towers need offsets (points) AND query_offsets (queries); got only %s"
+                         % ("offsets" if query_offsets is None else "query_offsets"))
+    if k > E.KNN_CROSS_MAX_K:
+        raise ValueError("k_nn: k=%d > %d: with queries= or return_dist= at most %d neighbours are kept" % (k, E.KNN_CROSS_MAX_K,
+                                                                                                          E.KNN_CROSS_MAX_K))
+    packed = offsets is not None
+    Bp, N, C = _rows_channels(points, "points", packed)
+    Bq, M, Cq = (Bp, N, C) if queries is None else _rows_channels(queries, "queries", packed)
+    if Cq != C:
+        raise ValueError("k_nn: queries have %d channels, points %d" % (Cq, C))
+    if Bq != Bp:
+        raise ValueError("k_nn: %d query clouds, %d clouds of points" % (Bq, Bp))
+    pseg = qseg = None
+    if packed:
+        pseg = _segments(points, offsets, [k])
+        qseg = pseg if queries is None else (query_offsets if isinstance(query_offsets, E.Segments) else E.Segments(query_offsets, M))
+        if qseg.rows != M:
+            raise ValueError("query_offsets end at %d, the query tower has %d rows" % (qseg.rows, M))
+        if qseg.nseg != pseg.nseg:
+            raise ValueError("k_nn: %d query clouds, %d clouds of points" % (qseg.nseg, pseg.nseg))
+    elif k > N or k <= 0:
+        raise ValueError("k_nn: k=%d must be in [1, N=%d] (tf.nn.top_k raises otherwise)" % (k, N))
+    p2d = E.as2d(points)[0]
+    q2d = p2d if queries is None else E.as2d(queries)[0]
+    return E.knn_cross(q2d, p2d, Bp, M, N, k, qseg=qseg, pseg=pseg, want_dist=return_dist)
+
+
+def k_nn(points, k, offsets=None, queries=None, query_offsets=None, return_dist=False):
     """dgcnn/ops.py:8-19.  points (B,N,C) -> idx (B,N,k) int32: the k nearest (squared L2 via
     (s_i+s_j)-2<x_i,x_j>), self included, ascending, ties -> lower index.  Bit-exact vs the oracle.
     offsets: a packed tower of clouds of different sizes, points (R,C) or (1,R,C), cloud b = rows [offsets[b], offsets[b + 1]):
-    idx (1,R,k) holds tower rows (offsets[b] + j), per cloud the dense k_nn of that cloud alone."""
+    idx (1,R,k) holds tower rows (offsets[b] + j), per cloud the dense k_nn of that cloud alone.
+    queries (B,M,C): the search between two sets -- idx (B,M,k) = for every query row the k nearest rows of `points` of the same cloud
+    (cloud-local j; no row is "self"), same arithmetic, tie and non-finite rules; k <= 64.  Packed: queries (Rq,C) or (1,Rq,C) with
+    query_offsets, points with offsets, the same number of clouds; idx (1,Rq,k) holds rows of the `points` tower.
+    return_dist: (idx, dist) with dist float32 in idx's shape, the selected distances (+inf where a NaN or infinite one fills a row);
+    with queries=None the points are their own queries and idx is the plain call's."""
     k = int(k)
+    if queries is not None or query_offsets is not None or return_dist:
+        return _k_nn_cross(points, k, offsets, queries, query_offsets, bool(return_dist))
     if offsets is not None:
         seg = _segments(points, offsets, [k])
         x, _, R = E.as2d(points)

@@ -173,6 +173,30 @@ int dgcnn_knn_seg_mix_f32(const float* x, int64_t ldx, int C, int k, int nseg, c
  * dgcnn_knn_seg_grid_use; n < 0 only queries.  Returns the previous value.  Initialised once from $DGCNN_KNN_MIX_MIN_N if set, else
  * from the library's default. */
 int dgcnn_knn_seg_mix_min_n(int n);
+/* ---- K1 between TWO point sets (csrc/knn_cross.hip): for every row of a query set q the k nearest rows of a separate candidate set p
+ * of the same cloud b -- PyG's knn(x, y, k) beside the knn_graph of the entries above.
+ * idx[(first query row of cloud b) + i][0..k) = the k smallest keys (D~_ij, j) over the candidates j of cloud b, ascending, ties -> lower
+ * j; D_ij = (s_i + s_j) - 2 <q_i,p_j> in K1's normative arithmetic (s = the sequential sum of squares of the row, the product an fmaf
+ * chain over the channels ascending), D~ = +inf where D is NaN, -inf sorts first: K1's non-finite rule, so every row holds k DISTINCT
+ * rows of its own candidate cloud whatever q and p hold.  The candidate set is not assumed to be the query set: there is no "self
+ * included" rule; called with q == p (same rows, same map) the result is dgcnn_knn_f32's / dgcnn_knn_seg_f32's, bit for bit.
+ * dist: NULL, or (q_rows, k) floats: the selected D~ in the order of idx (+inf where a candidate at D~ = +inf fills the row).
+ * Dense call: q_off == p_off == NULL, nseg = B clouds of max_m query rows (q: (B, max_m, C), row stride ldq) and max_n = min_n
+ *   candidate rows (p: (B, max_n, C), row stride ldp) each, q_rows = B max_m, p_rows = B max_n; idx holds cloud-local j.
+ * Packed call: q_off and p_off (device, nseg + 1 int32 each) strictly increasing from 0 to q_rows / p_rows: cloud b = query rows
+ *   [q_off[b], q_off[b + 1]) against candidate rows [p_off[b], p_off[b + 1]); idx holds rows of the candidate TOWER (p_off[b] + j).
+ *   max_m = the largest query cloud, min_n / max_n = the smallest / largest candidate cloud (host-known, as in dgcnn_knn_seg_f32).
+ * 1 <= C <= 1024, 1 <= k <= 64 and k <= min_n, nseg in [1, 65535].  The fp32 matrix-pipe scan of csrc/knn_wide.hip with two operand
+ *   sources; rows of at most 16 channels (raw coordinates) walk 16-channel slabs instead of 64-channel ones.  The large-k scan
+ *   (64 < k <= 256), seeds, the bf16 filter and the cell grid search a cloud against itself only: k > 64 here is DGCNN_EUNSUP.
+ * DGCNN_EUNSUP for k > 64 or C > 1024; DGCNN_EINVAL for a null q, p, idx or ws, exactly one of q_off / p_off null, k < 1 or k > min_n,
+ *   sizes that do not fit (dense: q_rows != nseg max_m, p_rows != nseg max_n, min_n != max_n), a misaligned workspace or one smaller
+ *   than dgcnn_knn_cross_workspace_bytes(q_rows, p_rows) = [s of every query row | s of every candidate row], each rows floats rounded
+ *   up to 256 bytes (ws 16-byte aligned).  Every refusal happens before any launch, with the reason in dgcnn_last_error. */
+int64_t dgcnn_knn_cross_workspace_bytes(int q_rows, int p_rows);
+int dgcnn_knn_cross_f32(const float* q, int64_t ldq, const float* p, int64_t ldp, int C, int k, int nseg, const int32_t* q_off,
+                        const int32_t* p_off, int q_rows, int p_rows, int max_m, int min_n, int max_n, int32_t* idx, float* dist,
+                        void* ws, size_t ws_bytes, void* stream);
 
 /* ---- K3 in its bf16-operand form (BASELINE configs[2] "bf16 edge-MLP MFMA"): conv0 of an EdgeConv layer, ops.py:21-52 ------
  * E[e] = [x_i, x_j - x_i] formed in fp32 and rounded to bf16 once (RNE), W0 (2C x F, row-major) rounded to bf16 once,
