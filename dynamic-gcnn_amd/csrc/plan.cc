@@ -14,6 +14,7 @@
 // inside a private torch memory pool that outlives the plan) and no host-side per-step values among the arguments (the dropout
 // seed lives in device memory; Adam stays outside).  One recorder per process (the Python host is single threaded).
 #include "common.h"
+#include <cxxabi.h>
 #include <stdlib.h>
 #include <string.h>
 #include <memory>
@@ -226,6 +227,35 @@ extern "C" int dgcnn_plan_info(void* plan, int* kernels, int* memsets, int* wait
   if (memsets) *memsets = p.counts[K_MEMSET];
   if (waits) *waits = p.counts[K_WAIT];
   if (collectives) *collectives = p.counts[K_ALLREDUCE];
+  return DGCNN_OK;
+}
+
+// The name is resolved here, when it is read: recording stores the kernel's address only, so its cost and the replay stay as they are.
+extern "C" int dgcnn_plan_kernel(void* plan, int i, char* name, size_t name_bytes, unsigned grid[3], unsigned block[3],
+                                 unsigned* lds_bytes) {
+  DG_REQUIRE(plan && name && name_bytes > 0, DGCNN_EINVAL, "dgcnn_plan_kernel: null plan or no room for the name");
+  const Plan& p = *reinterpret_cast<Plan*>(plan);
+  DG_REQUIRE(i >= 0 && i < p.counts[K_KERNEL], DGCNN_EINVAL, "dgcnn_plan_kernel: node %d of %d", i, p.counts[K_KERNEL]);
+  const Node* nd = nullptr;
+  int seen = 0;
+  for (const Node& n : p.nodes)
+    if (n.kind == K_KERNEL && seen++ == i) {
+      nd = &n;
+      break;
+    }
+  DG_REQUIRE(nd, DGCNN_EINVAL, "dgcnn_plan_kernel: node %d not found", i);
+  const char* raw = hipKernelNameRefByPtr(nd->fn, nd->st);
+  (void)hipGetLastError();
+  DG_REQUIRE(raw && raw[0], DGCNN_ELAUNCH, "dgcnn_plan_kernel: the runtime has no name for kernel node %d", i);
+  int status = 0;
+  char* dem = abi::__cxa_demangle(raw, nullptr, nullptr, &status);
+  const char* s = (status == 0 && dem) ? dem : raw;               // not a mangled name: the raw string
+  strncpy(name, s, name_bytes - 1);
+  name[name_bytes - 1] = 0;
+  free(dem);
+  if (grid) grid[0] = nd->g.x, grid[1] = nd->g.y, grid[2] = nd->g.z;
+  if (block) block[0] = nd->b.x, block[1] = nd->b.y, block[2] = nd->b.z;
+  if (lds_bytes) *lds_bytes = nd->sh;
   return DGCNN_OK;
 }
 

@@ -598,16 +598,10 @@ def knn(x2d, B, N, k, seed=None, seg=None):
     Cp, kc = _knn_instance(C, k)
     seeded = _knn_seed_ok(seed, B, N, k)
     # bench.py's tag of the CALL: the kernels it launches (the library picks the form: knn.hip:knn_impl, knn_scan)
-    if _knn_big(k):
-        tag = "knn_call<C%d,k%d>[%s+knn_bigk_kernel]" % (Cp, kc, _sqnorm_name(C))
-    elif seeded and 16 < C <= 64:
-        tag = "knn_call<C%d,k%d>[sqnorm_kernel+knn_seed_bound_kernel+knn_bf16a_kernel+knn_select_kernel]" % (Cp, kc)
-    elif C <= 4:
-        tag = "knn_call<C%d,k%d>[%s]" % (Cp, kc, "knn_grid_*" if N >= 4096 else "sqnorm_kernel+knn_hist_bound_kernel+knn_kernel")
-    elif _knn_wide(C):
-        tag = "knn_call<C%d,k%d>[%s+knn_wide_kernel]" % (Cp, kc, "sqnorm_wide_kernel" if C > 128 else "sqnorm_kernel")
-    else:
-        tag = "knn_call<C%d,k%d>[sqnorm_kernel+%s]" % (Cp, kc, "knn_bf16f_kernel" if N >= 8192 else "knn_mfma_kernel")
+    tag = None
+    if H.TIMER is not None:
+        tag = "knn_call<C%d,k%d>[%s]" % (Cp, kc, "+".join(_knn_call_kernels(
+            x2d, C, k, N, N, int(seed.shape[2]) if seeded else 0, dense=True)))
     if seeded:
         H.call("dgcnn_knn_seeded_f32", x2d.data_ptr(), B, N, C, H.ld2(x2d), k, seed.data_ptr(), int(seed.shape[2]), int(seed.shape[2]),
                idx.data_ptr(), ws.data_ptr(), nws, tag=tag, work=2.0 * B * N * N * C)
@@ -617,10 +611,71 @@ def knn(x2d, B, N, k, seed=None, seg=None):
     return idx
 
 
+def _knn_switches():
+    """The k-NN switches of the library as they stand, each through its own setter's query form (include/dgcnn_hip.h).  The VALU and
+    bf16-filter setters have none: they are set to a value and put back."""
+    lib = H.load()
+    bf16f = int(lib.dgcnn_knn_bf16_filter(2))
+    lib.dgcnn_knn_bf16_filter(bf16f)
+    return dict(valu=_knn_valu(), bf16f=bf16f, append=bool(lib.dgcnn_knn_append(-1)), seed_min_n=int(lib.dgcnn_knn_seed_min_n(-2)),
+                hist=int(lib.dgcnn_knn_hist(-1)))
+
+
+def _knn_call_kernels(x2d, C, k, min_n, max_n, kseed, dense):
+    """The kernels one dgcnn_knn_f32 / dgcnn_knn_seeded_f32 / dgcnn_knn_seg_f32 call launches with the workspace its *_workspace_bytes
+    query sizes, in order, for bench.py's tags ("knn_grid_*": the two cell-grid kernels).  Only evaluated while a timer is set.
+    kseed: the seeds per row the call passes (0: none).  dense: B clouds of min_n = max_n points; else a packed tower.
+    tests/test_gpu_knn_dispatch.py holds every tag against the launches recorded from the same call.
+    This restates knn.hip:knn_impl / knn_scan / launch_scan because the library has no host query that answers "which kernels would
+    this call launch": its queries give the workspace size, the packed grid rule (dgcnn_knn_seg_grid_use) and each switch, and
+    those are what is asked here; the rest of the rule needs the call's pointer, leading dimension and seed, which only the entry
+    sees.  The dense cell grid's smallest N (4096; $DGCNN_KNN_GRID_MIN_N moves it inside the library) has no query either.  The
+    names come from here only while a timer is set, never on the training path."""
+    sw = _knn_switches()
+    valu = sw["valu"]
+    vec_ok = H.ld2(x2d) % 4 == 0 and x2d.data_ptr() % 16 == 0                  # knn.hip:knn_vec_ok
+    names = [_sqnorm_name(C)]
+    if _knn_big(k):                                                             # knn_scan: no bound, whatever the seed
+        return names + ["knn_bigk_kernel"]
+    append = sw["append"] and 16 < C <= 64 and C % 4 == 0 and k <= 64 and vec_ok and not valu and sw["bf16f"] != 0   # knn_append_usable
+    in_range = max_n * H.ld2(x2d) < 2 ** 31
+    if dense:                                                                   # knn_seeds_used_dense / knn_seeds_used_packed
+        seed_min = sw["seed_min_n"] if sw["seed_min_n"] >= 0 else (0 if append else 4096)
+        seeded = k <= kseed <= 64 and 4 < C <= 64 and C % 4 == 0 and vec_ok and not valu and min_n >= seed_min and in_range
+        if _knn_grid_mode(H.load(), C, k) == 2 or (_knn_grid_mode(H.load(), C, k) == 1 and max_n >= 4096):
+            if not valu:
+                return names + ["knn_grid_*"]
+    else:
+        seeded = append and k <= kseed <= 64 and min_n >= max(sw["seed_min_n"], 0) and in_range
+    bound = seeded and C in (16, 32, 64)                                        # knn.hip:launch_seed_bound takes these widths only
+    if bound:
+        names.append("knn_seed_bound_kernel")
+    if bound and append:
+        return names + ["knn_bf16a_kernel", "knn_select_kernel"]
+    if _knn_wide(C):
+        return names + ["knn_wide_kernel"]
+    if C <= 4:
+        hs = sw["hist"] if min_n >= 256 else 0                                  # knn.hip:launch_hist_bound
+        return names + (["knn_hist_bound_kernel"] if hs and not valu and min_n >= 4 * k * hs else []) + ["knn_kernel"]
+    if dense and C <= 64 and not valu:                                          # knn.hip:launch_scan
+        if 16 < C and C % 4 == 0 and vec_ok and (sw["bf16f"] == 1 or (sw["bf16f"] == 2 and (max_n >= 8192 or bound))):
+            return names + ["knn_bf16f_kernel"]
+        return names + ["knn_mfma_kernel"]
+    return names + ["knn_kernel"]
+
+
+def _knn_valu():
+    """dgcnn_knn_force_valu as it stands (the setter has no query form: it is set to 0 and put back; the host is single threaded)"""
+    lib = H.load()
+    valu = int(lib.dgcnn_knn_force_valu(0))
+    lib.dgcnn_knn_force_valu(valu)
+    return bool(valu)
+
+
 def _knn_big(k):
     """the library gives this k to the large-k scan (knn_bigk.hip; knn.hip:knn_bigk_takes): k > 64 always, smaller k from
-    dgcnn_knn_big_k_min on"""
-    return k >= min(int(H.load().dgcnn_knn_big_k_min(-1)), 65)
+    dgcnn_knn_big_k_min on unless the VALU scan is forced"""
+    return k >= 65 or (k >= int(H.load().dgcnn_knn_big_k_min(-1)) and not _knn_valu())
 
 
 def _sqnorm_name(C):
@@ -629,8 +684,8 @@ def _sqnorm_name(C):
 
 def _knn_wide(C):
     """the library gives this width to the channel-slab scan (knn_wide.hip; knn.hip:knn_wide_takes): C > 128 always, narrower rows
-    from dgcnn_knn_wide_min_c on"""
-    return C >= min(int(H.load().dgcnn_knn_wide_min_c(-1)), 129)
+    from dgcnn_knn_wide_min_c on unless the VALU scan is forced"""
+    return C >= 129 or (C >= int(H.load().dgcnn_knn_wide_min_c(-1)) and not _knn_valu())
 
 
 def _knn_instance(C, k):
@@ -687,7 +742,8 @@ def knn_packed(x2d, k, seg, seed=None):
             ws, nws = _knn_workspace(x2d, "dgcnn_knn_seg_mix_workspace_bytes", R, n_grid)
             H.call("dgcnn_knn_seg_mix_f32", x2d.data_ptr(), H.ld2(x2d), C, k, seg.nseg, off.data_ptr(), R, lst.data_ptr(), n_grid, grid_max,
                    scan_min, scan_max, idx.data_ptr(), ws.data_ptr(), nws,
-                   tag="knn_seg_call<C4,k%d>[sqnorm_kernel+knn_grid_*+knn_hist_bound_kernel+knn_kernel]" % kc,
+                   tag=None if H.TIMER is None else "knn_seg_call<C4,k%d>[sqnorm_kernel+knn_grid_*+%s]" % (
+                       kc, "+".join(_knn_call_kernels(x2d, C, k, scan_min, scan_max, 0, dense=False)[1:])),
                    work=2.0 * float((n * n).sum()) * C)
             return idx
     else:
@@ -700,14 +756,10 @@ def knn_packed(x2d, k, seg, seed=None):
         return idx
     ws, nws = _knn_workspace(x2d, "dgcnn_knn_seg_workspace_bytes", R, seg.max_n, C, k)
     seeded = _knn_seed_ok(seed, 1, R, k)
-    if big:
-        tag = "knn_seg_call<C%d,k%d>[%s+knn_bigk_kernel]" % (Cp, kc, _sqnorm_name(C))
-    elif seeded and 16 < C <= 64:
-        tag = "knn_seg_call<C%d,k%d>[sqnorm_kernel+knn_seed_bound_kernel+knn_bf16a_kernel+knn_select_kernel]" % (Cp, kc)
-    elif C > 4 and _knn_wide(C):
-        tag = "knn_seg_call<C%d,k%d>[%s+knn_wide_kernel]" % (Cp, kc, "sqnorm_wide_kernel" if C > 128 else "sqnorm_kernel")
-    else:
-        tag = "knn_seg_call<C%d,k%d>[sqnorm_kernel+%sknn_kernel]" % (Cp, kc, "knn_hist_bound_kernel+" if C <= 4 else "")
+    tag = None
+    if H.TIMER is not None:
+        tag = "knn_seg_call<C%d,k%d>[%s]" % (Cp, kc, "+".join(_knn_call_kernels(
+            x2d, C, k, seg.min_n, seg.max_n, int(seed.shape[2]) if seeded else 0, dense=False)))
     H.call("dgcnn_knn_seg_f32", x2d.data_ptr(), H.ld2(x2d), C, k, seg.nseg, off.data_ptr(), R, seg.min_n, seg.max_n,
            seed.data_ptr() if seeded else None, int(seed.shape[2]) if seeded else 0, int(seed.shape[2]) if seeded else 0,
            idx.data_ptr(), ws.data_ptr(), nws, tag=tag, work=2.0 * float((n * n).sum()) * C)
@@ -751,7 +803,10 @@ def knn_cross(q2d, p2d, B, M, N, k, qseg=None, pseg=None, want_dist=False):
     ws, nws = _knn_workspace(q2d, "dgcnn_knn_cross_workspace_bytes", q_rows, p_rows)
     kc = 8 if k <= 8 else 20 if k <= 20 else 40 if k <= 40 else 64
     Cp = 16 if C <= 16 else (C + 63) // 64 * 64                  # channels rounded up to whole slabs (16 or 64 wide)
-    tag = "knn_cross_call<C%d,k%d>[%s+knn_cross_kernel]" % (Cp, kc, _sqnorm_name(C))
+    # one set of rows under one map on both sides: the library computes its norms once (knn_cross.hip)
+    same = (q2d.data_ptr() == p2d.data_ptr() and H.ld2(q2d) == H.ld2(p2d) and q_rows == p_rows and
+            (max_m == max_n if qo is None else qo.data_ptr() == po.data_ptr()))
+    tag = "knn_cross_call<C%d,k%d>[%s+knn_cross_kernel]" % (Cp, kc, "+".join([_sqnorm_name(C)] * (1 if same else 2)))
     H.call("dgcnn_knn_cross_f32", q2d.data_ptr(), H.ld2(q2d), p2d.data_ptr(), H.ld2(p2d), C, k, nseg, H._p(qo), H._p(po), q_rows, p_rows,
            max_m, min_n, max_n, idx.data_ptr(), H._p(dist), ws.data_ptr(), nws, tag=tag, work=2.0 * pairs * C)
     return (idx, dist) if want_dist else idx
@@ -762,11 +817,23 @@ def _tile_m(M, N):
     return 128
 
 
-def _gemm_tag(M, N, K, transA, transB, A, Bm, colmax_rpg=0):
-    """Kernel identity of a dgcnn_gemm_f32 launch for bench.py's table (mirrors the C dispatch); None when nobody is timing."""
+def _gemm_tag(M, N, K, transA, transB, A, Bm, colmax_rpg=0, C_out=None, has_bias=False, has_stats=False):
+    """Kernel identity of a dgcnn_gemm_f32 launch for bench.py's table (mirrors the C dispatch); None when nobody is timing.  The tag
+    names the kernel that forms the product; a split reduction adds reduce_partials_kernel to the call without changing the tag.
+    tests/test_gpu_gemm_dispatch.py holds every tag against the launches recorded from the same call."""
     if H.TIMER is None:
         return None
     lda, ldb = H.ld2(A), H.ld2(Bm)
+    # the streaming kernels of the class dimension (gemm.hip:gemm_f32_impl, ahead of every tile kernel); the engine always passes a
+    # workspace, whose size the transA form also checks (512 partial products at most)
+    if N <= 4 and lda % 4 == 0 and A.data_ptr() % 16 == 0:
+        if not transA and not transB and K % 4 == 0 and K <= 4096 and not has_bias:
+            return "gemm_call[skinny_nn_kernel<%d>]" % N
+        if transA and M % 4 == 0 and M <= 4096 and not has_bias and not has_stats and ctx().workspace().numel() >= min(-(-K // 64), 512) * M * N * 4:
+            return "gemm_call[skinny_tn_kernel<%d>+reduce_partials_kernel]" % N
+    if transB and K <= 4 and N % 4 == 0 and not has_bias and not has_stats and C_out is not None and \
+            H.ld2(C_out) % 4 == 0 and C_out.data_ptr() % 16 == 0:
+        return "gemm_call[skinny_nt_kernel<%d>]" % K
     vec = (lda % 4 == 0 and ldb % 4 == 0 and A.data_ptr() % 16 == 0 and Bm.data_ptr() % 16 == 0 and
            ((M if transA else K) % 4 == 0) and ((K if transB else N) % 4 == 0))
     arith = H.gemm_arith()
@@ -807,7 +874,8 @@ def gemm(A, Bm, C, transA=False, transB=False, beta=0.0, gbias=None, rpg=0, stat
     Kb = Bm.shape[1] if transB else Bm.shape[0]
     assert K == Kb and tuple(C.shape) == (M, N), (A.shape, Bm.shape, C.shape, transA, transB)
     ws = ctx().workspace()
-    tag = _gemm_tag(M, N, K, transA, transB, A, Bm, colmax_rpg if colmax is not None else 0)
+    tag = _gemm_tag(M, N, K, transA, transB, A, Bm, colmax_rpg if colmax is not None else 0, C_out=C, has_bias=gbias is not None,
+                    has_stats=stats is not None)
     if row_group is not None:
         if colmax is not None:
             raise ValueError("gemm: the column-maximum epilogue does not take a packed tower")

@@ -169,6 +169,7 @@ PROTOTYPES = {
     "dgcnn_plan_abort": [],
     "dgcnn_plan_replay": [c_vp],
     "dgcnn_plan_info": [c_vp, c_vp, c_vp, c_vp, c_vp],
+    "dgcnn_plan_kernel": [c_vp, c_int, c_vp, c_sz, c_vp, c_vp, c_vp],
     "dgcnn_plan_destroy": [c_vp],
     "dgcnn_stream_wait": [c_vp, c_vp],
     "dgcnn_stream_create": [c_int, c_int, c_vp],
@@ -361,6 +362,16 @@ class Plan(object):
         v = [ctypes.c_int(0) for _ in range(4)]
         _check(load().dgcnn_plan_info(self.handle, *[ctypes.byref(x) for x in v]), "dgcnn_plan_info")
         return dict(zip(("kernels", "memsets", "waits", "collectives"), [int(x.value) for x in v]))
+
+    def kernels(self):
+        """[(demangled kernel name, grid (x, y, z), block (x, y, z), dynamic LDS bytes)] of the kernel nodes, in recorded order."""
+        out = []
+        name = ctypes.create_string_buffer(4096)
+        g, b, lds = (ctypes.c_uint * 3)(), (ctypes.c_uint * 3)(), ctypes.c_uint(0)
+        for i in range(self.info()["kernels"]):
+            _check(load().dgcnn_plan_kernel(self.handle, i, name, len(name), g, b, ctypes.byref(lds)), "dgcnn_plan_kernel")
+            out.append((name.value.decode(), tuple(g), tuple(b), int(lds.value)))
+        return out
 
     def destroy(self):
         if self.handle is not None:

@@ -703,12 +703,21 @@ int dgcnn_adam_f32(float* param, const float* grad, float* m, float* v, int64_t 
  * device address of the recorded step valid and unchanged for as long as the plan is replayed, and keeps per-step host values
  * (dropout seed: device memory; Adam's step size: outside the plan) out of it.  One recorder per process.
  * dgcnn_stream_wait: `waiter` waits for everything issued so far on `signaller` (event record + wait; recordable).
- * dgcnn_memset_async: hipMemsetAsync (recordable): the zero-fills of the step go through it. */
+ * dgcnn_memset_async: hipMemsetAsync (recordable): the zero-fills of the step go through it.
+ * dgcnn_plan_kernel: read kernel node `i` of a finished plan back, 0 <= i < `kernels` of dgcnn_plan_info, in recorded order
+ * (memsets, waits and collectives are not counted).  `name` receives the demangled kernel name with its template arguments, e.g.
+ * "void (anonymous namespace)::knn_mfma_kernel<64, 20, true>(float const*, ...)", NUL-terminated and truncated to name_bytes - 1
+ * (the raw symbol where it does not demangle); grid / block (x, y, z) and the dynamic LDS bytes of the launch go to the other
+ * outputs, each of which may be null.  The name is resolved when it is read, from the recorded kernel address; recording and
+ * replay do not change, and the streams the plan recorded must still exist (the runtime looks the kernel up for the node's
+ * stream).  DGCNN_EINVAL: null plan, null name, name_bytes == 0, i out of range; DGCNN_ELAUNCH: the runtime has no name for the
+ * node.  A read walks the plan from its first node.  Tests assert from this which kernel a call launched (tests/launch_trace.py). */
 int dgcnn_plan_begin(void);
 int dgcnn_plan_end(void** plan_out);
 int dgcnn_plan_abort(void);
 int dgcnn_plan_replay(void* plan);
 int dgcnn_plan_info(void* plan, int* kernels, int* memsets, int* waits, int* collectives);
+int dgcnn_plan_kernel(void* plan, int i, char* name, size_t name_bytes, unsigned grid[3], unsigned block[3], unsigned* lds_bytes);
 int dgcnn_plan_destroy(void* plan);
 int dgcnn_stream_wait(void* waiter, void* signaller);
 int dgcnn_memset_async(void* ptr, int value, size_t bytes, void* stream);

@@ -116,3 +116,15 @@ def test_knn_workspace_sizes_and_switches_are_plain_host_state():
         assert lib.dgcnn_knn_seed_min_n(-1) == 4096 and lib.dgcnn_knn_seed_min_n(-2) == -1  # -1: the library's rule
     finally:
         lib.dgcnn_knn_seed_min_n(prev)
+
+
+def test_plan_kernel_refuses_bad_arguments_without_a_gpu():
+    """dgcnn_plan_kernel: a null plan, a null name or no room for the name is DGCNN_EINVAL with a message, before anything is read."""
+    from dgcnn import _hip as H
+    lib = H.load()
+    name = ctypes.create_string_buffer(64)
+    assert lib.dgcnn_plan_kernel(None, 0, name, len(name), None, None, None) == -1
+    assert b"dgcnn_plan_kernel" in lib.dgcnn_last_error()
+    fake = ctypes.create_string_buffer(8)                             # never dereferenced: the name arguments are checked first
+    assert lib.dgcnn_plan_kernel(fake, 0, None, 64, None, None, None) == -1
+    assert lib.dgcnn_plan_kernel(fake, 0, name, 0, None, None, None) == -1

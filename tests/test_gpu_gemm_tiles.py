@@ -4,7 +4,11 @@ The bf16-split family (csrc/gemm_x3.hip) has five kernels -- gemm_x3_kernel with
 wave-specialised gemm_x3w2_kernel, gemm_x3q_kernel with 256 x 256 and 192 x 256 tiles -- and a cost rule that picks one per
 shape.  Here every kernel is forced in turn (dgcnn_gemm_x3_tile_override) and checked against float64 numpy in each layout
 (NN, NT, TN), with each epilogue option (beta, per-group bias, BatchNorm column sums, per-group column maximum, strided
-output), with split-K, and at ragged shapes whose tails run masked."""
+output), with split-K, and at ragged shapes whose tails run masked.
+
+All tiles of one arithmetic give the same bits, so which kernel a forced call ran is taken from its recorded launches
+(tests/launch_trace.py), not from the host mirrors of the rule (dgcnn_gemm_x3_tile_rows / _cols), which are asserted against the
+recording as well."""
 import contextlib
 
 import numpy as np
@@ -13,6 +17,7 @@ import torch
 
 from oracle import dgcnn_oracle as O
 from gpu_helpers import dev, host, run_model, set_vars
+from launch_trace import launches, names
 
 pytestmark = pytest.mark.gpu
 
@@ -61,14 +66,41 @@ def kernel_name(M, N, K):
     return "gemm_x3w2_kernel" if rows == 256 else "gemm_x3_kernel<%d>" % rows
 
 
-def check_forced(override, M, N, K):
-    """A forced tile is really the one the library reports for this shape."""
+def launched_name(L):
+    """The kernel that formed the product of a recorded dgcnn_gemm_f32 call, in kernel_name's words (a split reduction's
+    reduce_partials_kernel follows it)."""
+    name, args = L[0][0], L[0][1]
+    if name == "gemm_x3q_kernel":                              # <AKIND, BKIND, NP, BM>
+        return "gemm_x3q_kernel<%s>" % args[3]
+    if name == "gemm_x3_kernel":                               # <AKIND, BKIND, BN, NP, BM>
+        return "gemm_x3_kernel<%s>" % args[4]
+    return name
+
+
+def recorded_gemm(A, Bm, C, expect=None, **kw):
+    """E.gemm with its launches recorded -> the recording; expect: the kernel (kernel_name's words) that must have formed the product."""
+    from dgcnn import _engine as E
+    with launches() as L:
+        E.gemm(A, Bm, C, **kw)
+    if expect is not None:
+        assert launched_name(L) == expect, "expected %s, launched %s" % (expect, [(e[0], e[1]) for e in L])
+    return L
+
+
+def check_forced(override, M, N, K, L=None):
+    """A forced tile is really the one the library reports for this shape -- and, given the recording L of a call of that shape
+    without a column maximum, the one that was launched: for every override and for the cost rule the mirrors name the recorded kernel."""
     from dgcnn import _hip as H
     lib = H.load()
     if override in FORCED and H.gemm_arith() == 6:
         rows, wide = FORCED[override]
         assert lib.dgcnn_gemm_x3_tile_rows(M, N, K) == rows, (override, M, N, K)
         assert lib.dgcnn_gemm_x3_tile_cols(M, N, K) == wide, (override, M, N, K)
+        if L is not None:
+            forced_name = {128: "gemm_x3_kernel<128>", 256: "gemm_x3w2_kernel", 512: "gemm_x3q_kernel<256>", 448: "gemm_x3q_kernel<192>"}
+            assert launched_name(L) == forced_name[override], (override, M, N, K, [(e[0], e[1]) for e in L])
+    if L is not None:
+        assert launched_name(L) == kernel_name(M, N, K), (override, M, N, K, kernel_name(M, N, K), [(e[0], e[1]) for e in L])
 
 
 def decode(keys, B, F):
@@ -111,12 +143,19 @@ def assert_colsums(st, C64, slots, what):
 # ------------------------------------------------------------------------------------------
 # 1. per-cloud column maximum from the GEMM epilogue, on every tile
 # ------------------------------------------------------------------------------------------
+# what gemm.hip:launch<> is recorded to run under the column maximum, by override: the cost rule (0) and override 448 pick 192 x 256
+# for these shapes, and a cloud of 512 or 2048 rows is no multiple of 192, so both must be seen to run 256-row tiles instead
+COLMAX_LAUNCHED = {0: "gemm_x3q_kernel<256>", 448: "gemm_x3q_kernel<256>", 128: "gemm_x3_kernel<128>", 256: "gemm_x3w2_kernel",
+                   512: "gemm_x3q_kernel<256>"}
+
+
 @pytest.mark.parametrize("B,N,Cin,F,override", [
     (20, 512, 192, 1024, 0), (12, 2048, 192, 1024, 0), (24, 512, 256, 1024, 0),       # the cost rule picks 192 x 256 here
     (20, 512, 192, 1024, 128), (20, 512, 192, 1024, 256), (20, 512, 192, 1024, 512), (20, 512, 192, 1024, 448)])
 def test_column_maximum_on_every_tile(dg, B, N, Cin, F, override):
     """model.py:76-77 max-pool over the points of each cloud, taken in the GEMM's epilogue: a tile's keys go to the cloud of its
-    first row, so no tile may straddle two clouds -- clouds of 512 or 2048 points are not whole multiples of 192 rows."""
+    first row, so no tile may straddle two clouds -- clouds of 512 or 2048 points are not whole multiples of 192 rows.  The kernel
+    the call is recorded to launch is COLMAX_LAUNCHED's."""
     from dgcnn import _engine as E
     rng = np.random.default_rng(B * N + Cin + override)
     R = B * N
@@ -129,7 +168,7 @@ def test_column_maximum_on_every_tile(dg, B, N, Cin, F, override):
         T = torch.empty((R, F), device="cuda")
         keys = torch.zeros(B * F, dtype=torch.int64, device="cuda")
         st = torch.zeros(E.H.STAT_SLOTS * 2 * F, dtype=torch.float64, device="cuda")
-        E.gemm(dev(X), dev(W), T, stats=st, colmax=keys, colmax_rpg=N)
+        recorded_gemm(dev(X), dev(W), T, expect=COLMAX_LAUNCHED[override], stats=st, colmax=keys, colmax_rpg=N)
         vals, arg = decode(keys, B, F)
     Th = host(T)
     assert_colmax(vals, arg, Th, B, N, F, what)
@@ -268,7 +307,7 @@ def test_tiles_layouts_epilogues_against_float64(dg, M, N, K):
                 A, Bm, tr = P.operands(layout)
                 what = "%s %s arith %d override %d (%d, %d, %d)" % (layout, kname, arith, override, M, N, K)
                 C = torch.full((M, N), float("nan"), device="cuda")         # beta = 0 must not read C
-                E.gemm(A, Bm, C, **tr)
+                check_forced(override, M, N, K, recorded_gemm(A, Bm, C, **tr))
                 e = P.rel_err(C)
                 assert e < REL_BAR, (what, "beta 0", e)
                 if arith == 6 and override in (256, 512, 448):
@@ -287,7 +326,7 @@ def test_tiles_layouts_epilogues_against_float64(dg, M, N, K):
                 C = outw[:, lo:lo + N]
                 gb = gbuf[aligned][:, :N]
                 st = torch.zeros(E.H.STAT_SLOTS * 2 * N, dtype=torch.float64, device="cuda")
-                E.gemm(A, Bm, C, gbias=gb, rpg=RPG, stats=st, **tr)
+                recorded_gemm(A, Bm, C, expect=kname, gbias=gb, rpg=RPG, stats=st, **tr)
                 e = P.rel_err(C, bias)
                 assert e < REL_BAR, (what, e)
                 assert not bool(outw[:, :lo].any()) and not bool(outw[:, lo + N:].any()), (what, "wrote outside its columns")
@@ -319,7 +358,9 @@ def test_split_k_on_every_tile(dg, M, N, K, layout):
         with tile(override, arith):
             what = "%s %s arith %d override %d (%d, %d, %d)" % (layout, kernel_name(M, N, K), arith, override, M, N, K)
             C = torch.full((M, N), float("nan"), device="cuda")
-            E.gemm(A, Bm, C, **tr)
+            L = recorded_gemm(A, Bm, C, **tr)
+            check_forced(override, M, N, K, L)
+            assert names(L)[1:] == ["reduce_partials_kernel"], (what, "not a split reduction", names(L))
             e = P.rel_err(C)
             assert e < REL_BAR, (what, "beta 0", e)
             C1 = C0.clone()
@@ -375,7 +416,10 @@ def test_stat_writers_cover_the_row_tiles(dg, M, N, K, transB, colmax_rpg):
                 st = torch.zeros(slots * 2 * N, dtype=torch.float64, device="cuda")
                 C = torch.empty((M, N), device="cuda")
                 keys = torch.zeros(max(B, 1) * N, dtype=torch.int64, device="cuda")
-                E.gemm(A, Bm, C, stats=st, colmax=keys if B else None, colmax_rpg=colmax_rpg, **tr)
+                # (a group of 512 rows is no multiple of the 192-row tile: gemm.hip:launch<> takes 256 x 256 instead)
+                straddles = arith == 6 and colmax_rpg and colmax_rpg % lib.dgcnn_gemm_x3_tile_rows(M, N, K)
+                launched = "gemm_x3q_kernel<256>" if straddles else kernel_name(M, N, K)
+                recorded_gemm(A, Bm, C, expect=launched, stats=st, colmax=keys if B else None, colmax_rpg=colmax_rpg, **tr)
                 e = P.rel_err(C)
                 assert e < REL_BAR, (what, e)
                 assert_colsums(st, host(C).astype(np.float64), slots, what)

@@ -14,7 +14,11 @@ the only way to a seed bound of 0).  Every kernel form, forced the way the other
   knn_kernel / knn_bf16a_kernel<.., PackedClouds>                                 towers with one cloud of each family
 
 Seeds of every seeded form: the row's own exact graph (the tightest legal bound), the same reversed, the graph of unrelated random
-features, and on `clusters` k rows of the row's own cluster (a bound that is its slack and nothing else)."""
+features, and on `clusters` k rows of the row's own cluster (a bound that is its slack and nothing else).
+
+Every forced call names the kernel it is for (expect=) and is recorded (tests/launch_trace.py): the kernel, with the template
+arguments above, must be among those the call launched -- all forms return the same bits, so nothing else would notice a call that
+the dispatch sent elsewhere."""
 import contextlib
 
 import numpy as np
@@ -23,6 +27,7 @@ import torch
 
 from oracle import dgcnn_oracle as O
 from gpu_helpers import dev, host
+from launch_trace import launches, assert_launched
 import knn_adversarial as A
 
 pytestmark = pytest.mark.gpu
@@ -81,10 +86,37 @@ def up(x):
     return dev(np.array(x, np.float32))
 
 
-def knn(xd, N, k, seed=None, seg=None):
+def cp_of(C):
+    """CP of knn_kernel / knn_mfma_kernel for C <= 128 channels"""
+    return 4 if C <= 4 else 16 if C <= 16 else 64 if C <= 64 else 128
+
+
+def kc_of(k):
+    """KC, the list size class of k <= 64"""
+    return 8 if k <= 8 else 20 if k <= 20 else 40 if k <= 40 else 64
+
+
+def knn(xd, N, k, seed=None, seg=None, expect=None):
+    """expect: [(kernel, leading template arguments), ...] that must be among the kernels the call launches."""
     from dgcnn import _engine as E
     sd = None if seed is None else dev(np.array(seed, np.int32).reshape(1, N, -1))
-    return host(E.knn(xd, 1, N, k, seed=sd, seg=seg))[0]
+    if expect is None:
+        return host(E.knn(xd, 1, N, k, seed=sd, seg=seg))[0]
+    with launches() as L:
+        idx = E.knn(xd, 1, N, k, seed=sd, seg=seg)
+    for name, args in expect:
+        assert_launched(L, name, args)
+    return host(idx)[0]
+
+
+def seeded_kernels(C, k, form, cl="DenseClouds", lx="true"):
+    """What a seeded call of this form is for: the seed bound, then the append-form scan with its selection (C = 32, 64) or, with
+    dgcnn_knn_append(0) / at C = 16, the list-keeping scan that takes the bound."""
+    f = SEEDED_FORMS[form]
+    out = [("knn_seed_bound_kernel", None)]
+    if f["append"] and C > 16:
+        return out + [("knn_bf16a_kernel", [lx, f["append_products"], cl]), ("knn_select_kernel", [cl])]
+    return out + [("knn_mfma_kernel", [16, kc_of(k), "true"]) if C == 16 else ("knn_bf16f_kernel", [kc_of(k)])]
 
 
 def same(got, want, what):
@@ -117,7 +149,8 @@ def _path_args(form):
 @pytest.mark.parametrize("N,C,k", [c for c in A.CASES if c[1] in (16, 20, 64, 128)])
 def test_valu_scan(N, C, k, family):
     with forced(force_valu=1):
-        same(knn(up(A.make(family, N, C, k)), N, k), ref(family, N, C, k), "knn_kernel %s" % ((family, N, C, k),))
+        same(knn(up(A.make(family, N, C, k)), N, k, expect=[("knn_kernel", [cp_of(C), kc_of(k), "DenseClouds"])]),
+             ref(family, N, C, k), "knn_kernel %s" % ((family, N, C, k),))
 
 
 @pytest.mark.parametrize("loader", ["vector", "scalar"])
@@ -134,14 +167,16 @@ def test_mfma_scan(N, C, k, family, loader):
         xd = buf[:, :C]
     assert (H.ld2(xd) % 4 != 0) == (loader == "scalar")
     with forced(force_valu=0, bf16_filter=2):
-        same(knn(xd, N, k), ref(family, N, C, k), "knn_mfma_kernel %s" % ((family, N, C, k, loader),))
+        same(knn(xd, N, k, expect=[("knn_mfma_kernel", [cp_of(C), kc_of(k), "true" if loader == "vector" else "false"])]),
+             ref(family, N, C, k), "knn_mfma_kernel %s" % ((family, N, C, k, loader),))
 
 
 @pytest.mark.parametrize("family", A.FAMILIES)
 @pytest.mark.parametrize("N,C,k", [c for c in A.CASES if 16 < c[1] <= 64])
 def test_bf16_filter_scan(N, C, k, family):
     with forced(force_valu=0, bf16_filter=1):
-        same(knn(up(A.make(family, N, C, k)), N, k), ref(family, N, C, k), "knn_bf16f_kernel %s" % ((family, N, C, k),))
+        same(knn(up(A.make(family, N, C, k)), N, k, expect=[("knn_bf16f_kernel", [kc_of(k)])]), ref(family, N, C, k),
+             "knn_bf16f_kernel %s" % ((family, N, C, k),))
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -159,7 +194,7 @@ def test_seeded_scan_whatever_the_seeds(N, C, k, family, form):
             check_seeded_path(lib, N, C, k, **_path_args(form))
         same(knn(xd, N, k), want, "unseeded %s" % ((family, N, C, k),))
         for name, sd in seeds_of(family, x, want, k).items():
-            same(knn(xd, N, k, seed=sd), want, "%s, seeds: %s %s" % (form, name, (family, N, C, k)))
+            same(knn(xd, N, k, seed=sd, expect=seeded_kernels(C, k, form)), want, "%s, seeds: %s %s" % (form, name, (family, N, C, k)))
 
 
 @pytest.mark.parametrize("form", sorted(SEEDED_FORMS))
@@ -174,7 +209,7 @@ def test_seeded_scan_with_a_seed_bound_of_zero(N, C, k, form):
         if C > 16 or form == "lists":
             check_seeded_path(lib, N, C, k, **_path_args(form))
         for name, sd in (("own graph", want), ("own graph reversed", want[:, ::-1]), ("graph of unrelated features", unrelated(N, k))):
-            got = knn(xd, N, k, seed=sd)
+            got = knn(xd, N, k, seed=sd, expect=seeded_kernels(C, k, form))
             same(got[zr], want[zr], "%s, zero rows, seeds: %s %s" % (form, name, (N, C, k)))
             same(got, want, "%s, seeds: %s %s" % (form, name, (N, C, k)))
 
@@ -194,11 +229,12 @@ def test_seeded_scan_past_8192_points(products):
     xd = up(x)
     with forced(force_valu=0, bf16_filter=2, seed_min_n=0, append=1, append_products=products) as lib:
         check_seeded_path(lib, N, C, k, 1, products)
-        plain = knn(xd, N, k)
+        plain = knn(xd, N, k, expect=[("knn_bf16f_kernel", [20])])
         same(plain[rows], want, "unseeded, N = 8200")
         other = host(E.knn(dev(np.random.default_rng(3).random((N, 3), dtype=np.float32)), 1, N, k))[0]
         for name, sd in (("own graph", plain), ("own graph reversed", plain[:, ::-1]), ("graph of unrelated features", other)):
-            got = knn(xd, N, k, seed=sd)
+            got = knn(xd, N, k, seed=sd, expect=[("knn_seed_bound_kernel", None), ("knn_bf16a_kernel", ["false", products, "DenseClouds"]),
+                                                 ("knn_select_kernel", ["DenseClouds"])])
             same(got[rows], want, "%d products, seeds: %s, N = 8200" % (products, name))
             np.testing.assert_array_equal(got, plain, err_msg=name)
 
@@ -223,7 +259,8 @@ def test_packed_scan(C, k):
     from dgcnn import _engine as E
     x, off, want, _ = packed(C, k)
     with forced(force_valu=0, bf16_filter=2):
-        same(knn(up(x), len(x), k, seg=E.Segments(off, len(x))), want, "packed knn_kernel %s" % ((C, k),))
+        same(knn(up(x), len(x), k, seg=E.Segments(off, len(x)), expect=[("knn_kernel", [cp_of(C), kc_of(k), "PackedClouds"])]), want,
+             "packed knn_kernel %s" % ((C, k),))
 
 
 @pytest.mark.parametrize("products", [1, 3])
@@ -243,4 +280,6 @@ def test_packed_seeded_scan_whatever_the_seeds(C, k, products):
         check_seeded_path(lib, seg.max_n, C, k, 1, products)
         for name, sd in (("own graph", want), ("own graph reversed", want[:, ::-1]), ("graph of unrelated features", other),
                          ("clusters: k rows of the row's own cluster", members)):
-            same(knn(xd, R, k, seed=sd, seg=seg), want, "packed, %d products, seeds: %s %s" % (products, name, (C, k)))
+            same(knn(xd, R, k, seed=sd, seg=seg, expect=[("knn_seed_bound_kernel", None), ("knn_bf16a_kernel", ["true", products, "PackedClouds"]),
+                                                         ("knn_select_kernel", ["PackedClouds"])]), want,
+                 "packed, %d products, seeds: %s %s" % (products, name, (C, k)))

@@ -31,6 +31,7 @@ import torch
 
 from oracle import dgcnn_oracle as O
 from gpu_helpers import dev, host, Guard
+from launch_trace import launches, assert_launched
 import knn_nonfinite as NF
 from test_gpu_knn_adversarial import forced, unrelated
 
@@ -99,12 +100,30 @@ def view(x2d, loader):
     return buf[:, :C]
 
 
-def dense_knn(x, k, loader="contiguous", seed=None):
+def bigk_kernel(xd, k, clouds):
+    """The instance a call on this view is for: knn_bigk_kernel<keys per lane, float4 loader, cloud map> (knn_bigk.hip:launch_knn_bigk)"""
+    from dgcnn import _hip as H
+    vec = H.ld2(xd) % 4 == 0 and xd.data_ptr() % 16 == 0 and xd.shape[1] % 4 == 0
+    return ("knn_bigk_kernel", [4 if k <= 128 else 8, "true" if vec else "false", clouds])
+
+
+def recorded(call, expect):
+    """call() with its launches recorded: the expected kernel (name, leading template arguments) must be among them."""
+    if expect is None:
+        return call()
+    with launches() as L:
+        out = call()
+    assert_launched(L, *expect)
+    return out
+
+
+def dense_knn(x, k, loader="contiguous", seed=None, expect="bigk"):
+    """expect: "bigk" = the call must launch the knn_bigk_kernel instance of its shape; None = whatever the dispatch picks."""
     from dgcnn import _engine as E
     B, N, C = x.shape
     xd = view(x.reshape(B * N, C), loader)
     sd = None if seed is None else dev(np.array(seed, np.int32).reshape(B, N, -1))
-    return host(E.knn(xd, B, N, k, seed=sd))
+    return host(recorded(lambda: E.knn(xd, B, N, k, seed=sd), bigk_kernel(xd, k, "DenseClouds") if expect == "bigk" else expect))
 
 
 def same(got, want, lo, n, what):
@@ -199,11 +218,13 @@ def tower(sizes, C, k):
     return _REF[key]
 
 
-def packed_knn(x, off, k, loader="contiguous", seed=None):
+def packed_knn(x, off, k, loader="contiguous", seed=None, expect="bigk"):
     from dgcnn import _engine as E
     R = len(x)
     sd = None if seed is None else dev(np.array(seed, np.int32).reshape(1, R, -1))
-    return host(E.knn(view(x, loader), 1, R, k, seed=sd, seg=E.Segments(off, R))).reshape(R, k)
+    xd = view(x, loader)
+    return host(recorded(lambda: E.knn(xd, 1, R, k, seed=sd, seg=E.Segments(off, R)),
+                         bigk_kernel(xd, k, "PackedClouds") if expect == "bigk" else expect)).reshape(R, k)
 
 
 def check_tower(idx, off, want, what):
@@ -274,7 +295,7 @@ def test_the_switch_sends_small_k_to_the_large_k_scan(C, N):
     for k in (1, 8, 20, 40, 64):
         want = oracle(x, k, ("normal", B, N, C))
         assert H.load().dgcnn_knn_big_k_min(-1) == DEFAULT_BIG_K_MIN and not E._knn_big(k)
-        default = dense_knn(x, k)
+        default = dense_knn(x, k, expect=None)                # the small-k kernels: what the switch is held against
         same(default, want, 0, N, "default path %s" % ((B, N, C, k),))
         with forced(big_k_min=1) as lib:
             assert lib.dgcnn_knn_big_k_min(-1) == 1 and E._knn_big(k)

@@ -32,6 +32,7 @@ import pytest
 import torch
 
 from gpu_helpers import dev, host, Guard
+from launch_trace import launches, assert_launched
 import knn_cross_reference as R
 import knn_nonfinite as NF
 
@@ -108,9 +109,11 @@ def view(x2d, loader):
     return buf[:, :C]
 
 
-def raw_cross(qd, pd, k, M, N, B=1, q_off=None, p_off=None, want_dist=True):
+def raw_cross(qd, pd, k, M, N, B=1, q_off=None, p_off=None, want_dist=True, expect="cross"):
     """dgcnn_knn_cross_f32 on device views qd (q_rows, C), pd (p_rows, C) with idx, dist and the workspace between guards.
-    Dense: B clouds of M queries against N candidates.  Packed: q_off / p_off host offsets (M, N unused).  -> (idx, dist | None)"""
+    Dense: B clouds of M queries against N candidates.  Packed: q_off / p_off host offsets (M, N unused).  -> (idx, dist | None)
+    The call is recorded (tests/launch_trace.py); expect: (kernel, leading template arguments) that must be among its launches,
+    "cross" = knn_cross_kernel<KC, vector | scalar, slab, cloud map> of the shape and the views."""
     from dgcnn import _hip as H
     lib = H.load()
     g = Guard()
@@ -127,8 +130,14 @@ def raw_cross(qd, pd, k, M, N, B=1, q_off=None, p_off=None, want_dist=True):
     dist = g.new((q_rows, k), torch.float32) if want_dist else None
     need = int(lib.dgcnn_knn_cross_workspace_bytes(q_rows, p_rows))
     ws = g.new((need,), torch.uint8, fill=77)
-    H.call("dgcnn_knn_cross_f32", qd.data_ptr(), H.ld2(qd), pd.data_ptr(), H.ld2(pd), C, k, nseg, H._p(qo), H._p(po), q_rows, p_rows, max_m,
-           min_n, max_n, idx.data_ptr(), H._p(dist), ws.data_ptr(), need)
+    with launches() as L:
+        H.call("dgcnn_knn_cross_f32", qd.data_ptr(), H.ld2(qd), pd.data_ptr(), H.ld2(pd), C, k, nseg, H._p(qo), H._p(po), q_rows, p_rows,
+               max_m, min_n, max_n, idx.data_ptr(), H._p(dist), ws.data_ptr(), need)
+    if expect == "cross":                                     # the instance this shape and these views are for
+        vec = C % 4 == 0 and all(H.ld2(t) % 4 == 0 and t.data_ptr() % 16 == 0 for t in (qd, pd))
+        expect = ("knn_cross_kernel", [8 if k <= 8 else 20 if k <= 20 else 40 if k <= 40 else 64, "true" if vec else "false",
+                                       16 if C <= 16 else 64, "DenseClouds" if q_off is None else "PackedClouds"])
+    assert_launched(L, *expect)
     g.check()
     return host(idx), (host(dist) if want_dist else None)
 

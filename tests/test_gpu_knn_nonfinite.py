@@ -51,7 +51,8 @@ import torch
 from oracle import dgcnn_oracle as O
 from gpu_helpers import dev, host, set_vars
 import knn_nonfinite as NF
-from test_gpu_knn_adversarial import forced, check_seeded_path, knn, up, unrelated, SEEDED_FORMS, _path_args
+from test_gpu_knn_adversarial import (forced, check_seeded_path, knn, up, unrelated, SEEDED_FORMS, _path_args, cp_of, kc_of,
+                                       seeded_kernels)
 from test_gpu_packed_mix import seg_mix_call, classes
 
 pytestmark = pytest.mark.gpu
@@ -116,7 +117,10 @@ def test_raw_coordinate_scan_with_the_histogram_bound(family, N, C, k, hist):
         assert lib.dgcnn_knn_seg_grid_use(C, k, 1, 1, 1, 1, 1 << 62) == 0      # the cell grid is off: the scan takes every N
         assert lib.dgcnn_knn_hist(-1) == hist and lib.dgcnn_knn_force_valu(0) == 0
         for label, x, want in ref(family, N, C, k):
-            same(knn(up(x), N, k), want, 0, N, "form=hist%d+knn_kernel family=%s (%s) %s" % (hist, family, label, (N, C, k)))
+            expect = [("knn_kernel", [4, kc_of(k), "DenseClouds"])]
+            if hist and N >= 256 and N >= 4 * k * hist:
+                expect.append(("knn_hist_bound_kernel", [hist, "DenseClouds"]))
+            same(knn(up(x), N, k, expect=expect), want, 0, N, "form=hist%d+knn_kernel family=%s (%s) %s" % (hist, family, label, (N, C, k)))
 
 
 VALU = cases(NF.C_VALU)
@@ -126,7 +130,8 @@ VALU = cases(NF.C_VALU)
 def test_valu_scan(family, N, C, k):
     with forced(force_valu=1):
         for label, x, want in ref(family, N, C, k):
-            same(knn(up(x), N, k), want, 0, N, "form=knn_kernel family=%s (%s) %s" % (family, label, (N, C, k)))
+            same(knn(up(x), N, k, expect=[("knn_kernel", [cp_of(C), kc_of(k), "DenseClouds"])]), want, 0, N,
+                 "form=knn_kernel family=%s (%s) %s" % (family, label, (N, C, k)))
 
 
 MFMA = cases(NF.C_MFMA)
@@ -145,7 +150,8 @@ def test_mfma_scan(family, N, C, k, loader):
                 buf[:, :C] = up(x)
                 xd = buf[:, :C]
             assert (H.ld2(xd) % 4 != 0) == (loader == "scalar")
-            same(knn(xd, N, k), want, 0, N, "form=knn_mfma_kernel-%s family=%s (%s) %s" % (loader, family, label, (N, C, k)))
+            same(knn(xd, N, k, expect=[("knn_mfma_kernel", [cp_of(C), kc_of(k), "true" if loader == "vector" else "false"])]), want, 0, N,
+                 "form=knn_mfma_kernel-%s family=%s (%s) %s" % (loader, family, label, (N, C, k)))
 
 
 BF16F = cases(NF.C_BF16F)
@@ -155,7 +161,8 @@ BF16F = cases(NF.C_BF16F)
 def test_bf16_filter_scan(family, N, C, k):
     with forced(force_valu=0, bf16_filter=1):
         for label, x, want in ref(family, N, C, k):
-            same(knn(up(x), N, k), want, 0, N, "form=knn_bf16f_kernel family=%s (%s) %s" % (family, label, (N, C, k)))
+            same(knn(up(x), N, k, expect=[("knn_bf16f_kernel", [kc_of(k)])]), want, 0, N,
+                 "form=knn_bf16f_kernel family=%s (%s) %s" % (family, label, (N, C, k)))
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -179,7 +186,7 @@ def test_seeded_scan_whatever_the_seeds(family, N, C, k, form):
         for label, x, want in ref(family, N, C, k):
             xd = up(x)
             for name, sd in seeds_of(want, N, k):
-                same(knn(xd, N, k, seed=sd), want, 0, N,
+                same(knn(xd, N, k, seed=sd, expect=seeded_kernels(C, k, form)), want, 0, N,
                      "form=seeded-%s family=%s (%s) seeds=%s %s" % (form, family, label, name, (N, C, k)))
 
 
@@ -201,13 +208,14 @@ def test_seeded_scan_past_8192_points(family, products):
     what = "family=%s (%s) N=8200" % (family, label)
     with forced(force_valu=0, bf16_filter=2, seed_min_n=0, append=1, append_products=products) as lib:
         check_seeded_path(lib, N, C, k, 1, products)
-        plain = knn(xd, N, k)
+        plain = knn(xd, N, k, expect=[("knn_bf16f_kernel", [20])])
         assert plain.min() >= 0 and plain.max() < N, "form=knn_bf16f_kernel %s: an index outside the cloud" % what
         assert (np.diff(np.sort(plain, 1), axis=1) > 0).all(), "form=knn_bf16f_kernel %s: a row lists an index twice" % what
         same(plain[rows], want, 0, N, "form=knn_bf16f_kernel %s" % what)
         other = host(E.knn(dev(np.random.default_rng(3).random((N, 3), dtype=np.float32)), 1, N, k))[0]
         for name, sd in (("own graph", plain), ("own graph reversed", plain[:, ::-1]), ("graph of unrelated features", other)):
-            got = knn(xd, N, k, seed=sd)
+            got = knn(xd, N, k, seed=sd, expect=[("knn_seed_bound_kernel", None), ("knn_bf16a_kernel", ["false", products, "DenseClouds"]),
+                                                 ("knn_select_kernel", ["DenseClouds"])])
             same(got[rows], want, 0, N, "form=knn_bf16a_kernel<false,%d> %s seeds=%s" % (products, what, name))
             same(got, plain, 0, N, "form=knn_bf16a_kernel<false,%d> against the unseeded search, %s seeds=%s" % (products, what, name))
 
@@ -224,7 +232,9 @@ def test_cell_grid(family, N, C, k):
     with forced(grid=2, force_valu=0) as lib:
         assert lib.dgcnn_knn_seg_grid_use(C, k, 1, 1, 1, 1, 0) == 1          # mode 2: the grid whenever applicable
         for label, x, want in ref(family, N, C, k):
-            same(knn(up(x), N, k), want, 0, N, "form=cell-grid family=%s (%s) %s" % (family, label, (N, C, k)))
+            expect = [("knn_grid_build_kernel", ["DenseClouds"]),
+                      ("knn_grid_query_kernel", [8 if k <= 8 else 20 if k <= 20 else 40, "true" if C == 4 else "false"])]
+            same(knn(up(x), N, k, expect=expect), want, 0, N, "form=cell-grid family=%s (%s) %s" % (family, label, (N, C, k)))
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -258,7 +268,8 @@ def test_packed_scan_raw_coordinates(family, place, sizes):
     from dgcnn import _engine as E
     x, off, want = tower(family, 3, 8, place, sizes)
     with forced(grid=0, force_valu=0, hist=2):
-        got = knn(up(x), len(x), 8, seg=E.Segments(off, len(x)))
+        expect = [("knn_kernel", [4, 8, "PackedClouds"])] + ([("knn_hist_bound_kernel", [2, "PackedClouds"])] if min(sizes) >= 256 else [])
+        got = knn(up(x), len(x), 8, seg=E.Segments(off, len(x)), expect=expect)
         check_tower(got, off, want, "form=packed-scan-C3-%s family=%s bad=%d" % ("hist" if min(sizes) >= 256 else "nohist", family, place))
 
 
@@ -274,14 +285,17 @@ def test_packed_scan_features(family, place):
     xd = up(x)
     what = "family=%s bad=%d" % (family, place)
     with forced(force_valu=0, bf16_filter=2):
-        check_tower(knn(xd, R, 8, seg=seg), off, want, "form=packed-scan-C64 " + what)
+        check_tower(knn(xd, R, 8, seg=seg, expect=[("knn_kernel", [64, 8, "PackedClouds"])]), off, want, "form=packed-scan-C64 " + what)
     full = np.concatenate(want, 0)
     other = np.concatenate([unrelated(int(n), 8) + off[b] for b, n in enumerate(np.diff(off))], 0).astype(np.int32)
     for products in (1, 3):
         with forced(force_valu=0, bf16_filter=2, seed_min_n=0, append=1, append_products=products) as lib:
             check_seeded_path(lib, seg.max_n, 64, 8, 1, products)
             for name, sd in (("own graph", full), ("own graph reversed", full[:, ::-1]), ("graph of unrelated features", other)):
-                check_tower(knn(xd, R, 8, seed=sd, seg=seg), off, want, "form=packed-append-%d %s seeds=%s" % (products, what, name))
+                expect = [("knn_seed_bound_kernel", None), ("knn_bf16a_kernel", ["true", products, "PackedClouds"]),
+                          ("knn_select_kernel", ["PackedClouds"])]
+                check_tower(knn(xd, R, 8, seed=sd, seg=seg, expect=expect), off, want,
+                            "form=packed-append-%d %s seeds=%s" % (products, what, name))
 
 
 @pytest.mark.parametrize("place", [0, 1, 2])
@@ -294,7 +308,10 @@ def test_packed_cell_grid(family, place, C):
     with forced(grid=2, force_valu=0) as lib:
         n = np.diff(off)
         assert lib.dgcnn_knn_seg_grid_use(C, 8, len(n), len(x), int(n.min()), int(n.max()), int((n * n).sum())) == 1
-        check_tower(knn(up(x), len(x), 8, seg=E.Segments(off, len(x))), off, want, "form=packed-grid-C%d family=%s bad=%d" % (C, family, place))
+        expect = [("knn_grid_build_kernel", ["PackedClouds"]),
+                  ("knn_grid_query_kernel", [8, "true" if C == 4 else "false", "false", "PackedClouds"])]
+        check_tower(knn(up(x), len(x), 8, seg=E.Segments(off, len(x)), expect=expect), off, want,
+                    "form=packed-grid-C%d family=%s bad=%d" % (C, family, place))
 
 
 @pytest.mark.parametrize("place", [0, 1, 2])

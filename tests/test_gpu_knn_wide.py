@@ -27,6 +27,7 @@ import torch
 
 from oracle import dgcnn_oracle as O
 from gpu_helpers import dev, host, Guard
+from launch_trace import launches, assert_launched
 import knn_nonfinite as NF
 from test_gpu_knn_adversarial import forced, unrelated
 
@@ -94,12 +95,31 @@ def view(x2d, loader):
     return buf[:, :C]
 
 
-def dense_knn(x, k, loader="contiguous", seed=None):
+def wide_kernel(xd, k, clouds):
+    """The instance a call on this view is for: knn_wide_kernel<KC, float4 loader, cloud map> (knn_wide.hip:launch_knn_wide)"""
+    from dgcnn import _hip as H
+    kc = 8 if k <= 8 else 20 if k <= 20 else 40 if k <= 40 else 64
+    vec = H.ld2(xd) % 4 == 0 and xd.data_ptr() % 16 == 0 and xd.shape[1] % 4 == 0
+    return ("knn_wide_kernel", [kc, "true" if vec else "false", clouds])
+
+
+def recorded(call, expect):
+    """call() with its launches recorded: the expected kernel (name, leading template arguments) must be among them."""
+    if expect is None:
+        return call()
+    with launches() as L:
+        out = call()
+    assert_launched(L, *expect)
+    return out
+
+
+def dense_knn(x, k, loader="contiguous", seed=None, expect="wide"):
+    """expect: "wide" = the call must launch the knn_wide_kernel instance of its shape; None = whatever the dispatch picks."""
     from dgcnn import _engine as E
     B, N, C = x.shape
     xd = view(x.reshape(B * N, C), loader)
     sd = None if seed is None else dev(np.array(seed, np.int32).reshape(B, N, -1))
-    return host(E.knn(xd, B, N, k, seed=sd))
+    return host(recorded(lambda: E.knn(xd, B, N, k, seed=sd), wide_kernel(xd, k, "DenseClouds") if expect == "wide" else expect))
 
 
 def same(got, want, lo, n, what):
@@ -164,11 +184,13 @@ def tower(sizes, C, k, bad=None):
     return _REF[key]
 
 
-def packed_knn(x, off, k, loader="contiguous", seed=None):
+def packed_knn(x, off, k, loader="contiguous", seed=None, expect="wide"):
     from dgcnn import _engine as E
     R = len(x)
     sd = None if seed is None else dev(np.array(seed, np.int32).reshape(1, R, -1))
-    return host(E.knn(view(x, loader), 1, R, k, seed=sd, seg=E.Segments(off, R))).reshape(R, k)
+    xd = view(x, loader)
+    return host(recorded(lambda: E.knn(xd, 1, R, k, seed=sd, seg=E.Segments(off, R)),
+                         wide_kernel(xd, k, "PackedClouds") if expect == "wide" else expect)).reshape(R, k)
 
 
 def check_tower(idx, off, want, what):
@@ -248,7 +270,7 @@ def test_the_switch_sends_narrow_rows_to_the_wide_kernel(C, N):
     x = normal(B, N, C)
     want = oracle(x, k, ("normal", B, N, C))
     assert H.load().dgcnn_knn_wide_min_c(-1) == DEFAULT_MIN_C and not E._knn_wide(C)
-    default = dense_knn(x, k)
+    default = dense_knn(x, k, expect=None)                    # the narrow kernels: what the switch is held against
     same(default, want, 0, N, "default path %s" % ((B, N, C, k),))
     with forced(wide_min_c=5) as lib:
         assert lib.dgcnn_knn_wide_min_c(-1) == 5 and E._knn_wide(C)

@@ -10,11 +10,14 @@ import torch
 
 from oracle import dgcnn_oracle as O
 from gpu_helpers import dev, host, set_vars
+from launch_trace import launches, assert_launched
 
 pytestmark = pytest.mark.gpu
 
+# the engine's tag lists the kernels the call launches: the two cell-grid kernels as one word; the all-pairs scan closes the list, with
+# knn_hist_bound_kernel in front of it only where every scan cloud has the 256 points (and 4 k stride) the histogram bound needs
 GRID_TAG = "knn_grid_*"
-SCAN_TAG = "knn_hist_bound_kernel+knn_kernel"
+SCAN_TAG = "knn_kernel]"
 
 
 @pytest.fixture()
@@ -102,7 +105,8 @@ def classes(off, T):
 
 
 def seg_mix_call(x, off, C, k, T):
-    """dgcnn_knn_seg_mix_f32 directly, the clouds of at least T points as the grid class; idx is pre-filled with -1."""
+    """dgcnn_knn_seg_mix_f32 directly, the clouds of at least T points as the grid class; idx is pre-filled with -1.  The call is
+    recorded (tests/launch_trace.py): both sub-searches must have run as their ListedClouds instances."""
     from dgcnn import _hip as H
     R, nseg = len(x), len(off) - 1
     lst, n_grid, gmax, smin, smax = classes(off, T)
@@ -110,8 +114,15 @@ def seg_mix_call(x, off, C, k, T):
     idx = torch.full((R, k), -1, dtype=torch.int32, device="cuda")
     full = int(lib().dgcnn_knn_seg_mix_workspace_bytes(R, n_grid))
     ws = torch.empty(full, dtype=torch.uint8, device="cuda")
-    H.call("dgcnn_knn_seg_mix_f32", xd.data_ptr(), x.shape[1], C, k, nseg, od.data_ptr(), R, ld.data_ptr(), n_grid, gmax, smin, smax,
-           idx.data_ptr(), ws.data_ptr(), full)
+    with launches() as L:
+        H.call("dgcnn_knn_seg_mix_f32", xd.data_ptr(), x.shape[1], C, k, nseg, od.data_ptr(), R, ld.data_ptr(), n_grid, gmax, smin, smax,
+               idx.data_ptr(), ws.data_ptr(), full)
+    kc = 8 if k <= 8 else 20 if k <= 20 else 40
+    assert_launched(L, "knn_grid_build_kernel", ["ListedClouds"])
+    assert_launched(L, "knn_grid_query_kernel", [kc, "true" if C == 4 else "false", "false", "ListedClouds"])
+    assert_launched(L, "knn_kernel", [4, kc, "ListedClouds"])
+    if smin >= 256 and smin >= 8 * k and lib().dgcnn_knn_hist(-1) == 2:      # every scan cloud can take the histogram bound
+        assert_launched(L, "knn_hist_bound_kernel", [2, "ListedClouds"])
     return idx
 
 
