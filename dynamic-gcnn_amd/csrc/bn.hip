@@ -4,6 +4,7 @@
 // wave reads whole 256-B feature rows, k rows per point streamed with k independent loads.
 #include "common.h"
 #include <stdlib.h>
+#include <type_traits>
 
 namespace {
 
@@ -93,6 +94,8 @@ __device__ __forceinline__ void split_item(int64_t it, int FV, int fv_shift, int
     fq = (int)(it % FV);
   }
 }
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 template <int V> struct Vec;
 template <> struct Vec<4> {
@@ -195,6 +198,79 @@ __device__ __forceinline__ Items items_of(int64_t R, int FV) {
 }
 
 // ---- forward: z = (y-mu)*rstd + beta; relu; max / mean over the k rows of each point ----
+// Register-held form of the edge variant with a ReLU, for k <= HELD_K: the k x 4 values z of an item are computed once
+// into registers (KC = k rounded up to whole groups of NB rows; rows past k - 1 repeat row k - 1 and are left out of sum and counts
+// by wave-uniform branches), then maximum, sum over m ascending and the number of positive z in one walk, the number of z == max
+// in a second.  Same z, same additions in the same order as the loop of bn_act_kreduce_kernel, so max, mean and the packed count
+// are its bits.  What is gone is bookkeeping: the running-tie select chain (3 selects, a compare and a float add per element) and
+// the float select-and-add of the positive count become compare + integer add-with-carry, converted to the packed float once.
+// The maximum may be v_max_f32 HERE because every z left max(., 0): never a NaN, never -0.0, so "z > mx ? z : mx" from -inf picks
+// the same bits (without a ReLU the first zero seen keeps its sign in the loop form; those calls keep the loop).
+constexpr int HELD_GROUPS = 5;              // 5 x NB = 20 rows: 80 values; the kernel stays at 4 waves / SIMD with no scratch
+constexpr int HELD_K = HELD_GROUPS * NB;
+template <int KC>
+__device__ __forceinline__ void kreduce_held(const Rows<4, true>& rows, int k, const float (&mu)[4], const float (&rs)[4],
+                                             const float (&be)[4], float (&mx)[4], float (&sm)[4], float (&cn)[4]) {
+  constexpr int V = 4, H = V / 2;
+  static_assert(KC % NB == 0 && KC <= HELD_K, "whole groups of NB rows");
+  // channel pairs as 2-vectors: the element-wise v_pk_add_f32 / v_pk_mul_f32 the loop form compiles to (no contraction: Makefile)
+  f32x2 u2[H], mu2[H], rs2[H], be2[H], z[KC][H];
+#pragma unroll
+  for (int h = 0; h < H; ++h) {
+    u2[h] = f32x2{rows.u[2 * h], rows.u[2 * h + 1]};
+    mu2[h] = f32x2{mu[2 * h], mu[2 * h + 1]};
+    rs2[h] = f32x2{rs[2 * h], rs[2 * h + 1]};
+    be2[h] = f32x2{be[2 * h], be[2 * h + 1]};
+  }
+#pragma unroll
+  for (int m = 0; m < KC; ++m) {
+    // Rows::load's gather; only the last group can reach past k - 1 (KC - NB < k), the rows before it take their index from a
+    // constant offset
+    const unsigned row = __umul24((unsigned)rows.ip[(m < KC - NB + 1 || m < k) ? m : (k - 1)], (unsigned)rows.ld);
+    float yv[V];
+    Vec<V>::ld(rows.base + row, yv);
+#pragma unroll
+    for (int h = 0; h < H; ++h) {
+      const f32x2 y = f32x2{yv[2 * h], yv[2 * h + 1]} + u2[h];           // Rows::load's add
+      const f32x2 xh = (y - mu2[h]) * rs2[h];                            // bn_z, relu = 1
+      const f32x2 t = xh + be2[h];
+      z[m][h] = f32x2{fmaxf(t.x, 0.f), fmaxf(t.y, 0.f)};
+    }
+  }
+  f32x2 sm2[H];
+  unsigned nt[V], np[V];
+#pragma unroll
+  for (int v = 0; v < V; ++v) { mx[v] = -INFINITY; nt[v] = 0; np[v] = 0; }
+#pragma unroll
+  for (int h = 0; h < H; ++h) sm2[h] = f32x2{0.f, 0.f};
+#pragma unroll
+  for (int m = 0; m < KC; ++m)
+    if (m < KC - NB + 1 || m < k) {          // KC - NB < k <= KC: only the last group can hold repeated rows
+#pragma unroll
+      for (int h = 0; h < H; ++h) {
+        mx[2 * h] = fmaxf(mx[2 * h], z[m][h].x);
+        mx[2 * h + 1] = fmaxf(mx[2 * h + 1], z[m][h].y);
+        sm2[h] += z[m][h];
+        np[2 * h] += (z[m][h].x > 0.f) ? 1u : 0u;
+        np[2 * h + 1] += (z[m][h].y > 0.f) ? 1u : 0u;
+      }
+    }
+#pragma unroll
+  for (int m = 0; m < KC; ++m)
+    if (m < KC - NB + 1 || m < k) {
+#pragma unroll
+      for (int h = 0; h < H; ++h) {          // ties share the max gradient (A.5)
+        nt[2 * h] += (z[m][h].x == mx[2 * h]) ? 1u : 0u;
+        nt[2 * h + 1] += (z[m][h].y == mx[2 * h + 1]) ? 1u : 0u;
+      }
+    }
+#pragma unroll
+  for (int h = 0; h < H; ++h) { sm[2 * h] = sm2[h].x; sm[2 * h + 1] = sm2[h].y; }
+#pragma unroll
+  for (int v = 0; v < V; ++v) cn[v] = (float)(nt[v] + CNT_POS * np[v]);
+}
+
+// The loop form: every k, with or without a ReLU; also the dense (G = false) variants.
 template <int V, bool G>
 __global__ __launch_bounds__(256) void bn_act_kreduce_kernel(
     Src src, int64_t R, int k, int F, const float* __restrict__ mean,
@@ -239,6 +315,40 @@ __global__ __launch_bounds__(256) void bn_act_kreduce_kernel(
 #pragma unroll
       for (int v = 0; v < V; ++v) cn[v] += np[v];
     }
+    if (cnt_out) Vec<V>::st(cnt_out + r * F + f, cn);
+    if (mean_out) {
+#pragma unroll
+      for (int v = 0; v < V; ++v) sm[v] *= invk;
+      Vec<V>::st(mean_out + r * ldmean + f, sm);
+    }
+  }
+}
+
+// The register-held form as a kernel of its own, one instance per group count: inside bn_act_kreduce_kernel<4, true> its 80 values
+// would set that kernel's register allocation (71 -> 135 VGPRs, 7 -> 3 waves / SIMD) for the loop form as well.  Same items, same
+// grid, same stores.
+template <int KC>
+__global__ __launch_bounds__(256) void bn_act_kreduce_held_kernel(
+    Src src, int64_t R, int k, int F, const float* __restrict__ mean,
+    const float* __restrict__ rstd, const float* __restrict__ beta,
+    float* __restrict__ max_out, int64_t ldmax, float* __restrict__ mean_out, int64_t ldmean,
+    float* __restrict__ out2, int64_t ldout2, float* __restrict__ cnt_out, int fv_shift) {
+  constexpr int V = 4;
+  const int FV = F / V;
+  const Items its = items_of<true>(R, FV);
+  const float invk = 1.0f / (float)k;
+  for (int64_t q = its.first; q < its.count; q += its.step) {
+    int64_t r;
+    int fq;
+    split_item(its.base + q, FV, fv_shift, r, fq);
+    const int f = fq * V;
+    float mu[V], rs[V], be[V], mx[V], sm[V], cn[V];
+    Vec<V>::ld(mean + f, mu); Vec<V>::ld(rstd + f, rs); Vec<V>::ld(beta + f, be);
+    Rows<V, true> rows;
+    rows.init(src, r, k, F, f);
+    kreduce_held<KC>(rows, k, mu, rs, be, mx, sm, cn);
+    Vec<V>::st(max_out + r * ldmax + f, mx);
+    if (out2) Vec<V>::st(out2 + r * ldout2 + f, mx);
     if (cnt_out) Vec<V>::st(cnt_out + r * F + f, cn);
     if (mean_out) {
 #pragma unroll
@@ -434,8 +544,10 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
 // the folded form are not needed.  A thread owns one channel quad for its whole life (items_of<true>: the item stride is a
 // multiple of F / 4), accumulates 2 C x 4 partial sums in registers, the block reduces them through LDS into
 // partial[block][2 C][F]; reduce_partials_kernel (gemm.hip) adds the blocks up in fixed order.
-template <int CC>
-__global__ __launch_bounds__(256) void edge_bwd_apply_wgrad_kernel(
+// EXACT = false: C <= CC at run time (a padded channel contributes fmaf(0, o, .) to sums nobody reads).  EXACT = true: C == CC, the
+// form of edge_bwd_apply_wgrad_exact_kernel below.
+template <int CC, bool EXACT>
+__device__ __forceinline__ void edge_bwd_apply_wgrad_body(
     Src src, int64_t R, int k, int F, const float* __restrict__ mean, const float* __restrict__ rstd,
     const float* __restrict__ beta, const float* __restrict__ dmax, int64_t lddmax, const float* __restrict__ dmean,
     int64_t lddmean, const float* __restrict__ mx_in, int64_t ldmx, const float* __restrict__ cnt_in,
@@ -474,31 +586,90 @@ __global__ __launch_bounds__(256) void edge_bwd_apply_wgrad_kernel(
     for (int v = 0; v < V; ++v) st.cnt[v] -= (float)CNT_POS * floorf(st.cnt[v] * (1.0f / CNT_POS));
     float xi[CC];
 #pragma unroll
-    for (int c = 0; c < CC; ++c) xi[c] = (c < C) ? x[r * ldx + c] : 0.f;
+    for (int c = 0; c < CC; ++c) xi[c] = (EXACT || c < C) ? x[r * ldx + c] : 0.f;
     const int64_t cloud0 = (int64_t)((unsigned)r / src.npts) * src.npts;
     float acc[V] = {0.f, 0.f, 0.f, 0.f};
-    for (int m = 0; m < k; m += NB) {
-      float yv[NB][V];
-      rows.load(m, k, yv);
+    if constexpr (EXACT) {
+      // C == CC: a group's NB neighbour rows of x are fetched like its rows of V -- no branch on the channel, one
+      // 24-bit multiply per row offset inside the cloud (unsigned 32-bit element offsets; host: N * ldv, N * ldx < 2^32), the channels at constant offsets from it -- so all
+      // of a group's loads are in flight together; the loop of the other form issues them one channel at a time behind a branch
+      // and a wait each.  Whole groups (m + NB <= k) take their indices from constant offsets and test no row; the last, partial
+      // group repeats row k - 1 and skips the repeats.  Same x_j[c] - x_i[c], same dz / o / fmaf chains in m order; no fmaf on a
+      // padded channel when CC == 3.
+      const float* xc = x + cloud0 * ldx;
+      float q1[V], q2[V];                          // loop-invariant operands of dz, formed once: the same division, the same product
 #pragma unroll
-      for (int b = 0; b < NB; ++b)
-        if (m + b < k) {
-          const float* xj = x + (cloud0 + rows.ip[m + b]) * ldx;
-          float dx[CC];
+      for (int v = 0; v < V; ++v) { q1[v] = dmx[v] / st.cnt[v]; q2[v] = dmn[v] * invk; }
+      auto group = [&](int m, auto tail) {
+        constexpr bool TAIL = decltype(tail)::value;
+        float yv[NB][V], dx[NB][CC];
+        unsigned j[NB];
 #pragma unroll
-          for (int c = 0; c < CC; ++c) dx[c] = (c < C) ? xj[c] - xi[c] : 0.f;
+        for (int b = 0; b < NB; ++b) j[b] = (unsigned)rows.ip[(!TAIL || m + b < k) ? (m + b) : (k - 1)];
 #pragma unroll
-          for (int v = 0; v < V; ++v) {
-            float xh;
-            const float z = bn_z(yv[b][v], mu[v], rs[v], be[v], 1, xh);
-            float dz = ((z == st.mx[v]) ? dmx[v] / st.cnt[v] : 0.f) + dmn[v] * invk;
-            if (!(z > 0.f)) dz = 0.f;
-            const float o = rs[v] * (dz - c1[v] - xh * c2[v]);
-            acc[v] += o;
+        for (int b = 0; b < NB; ++b) {
+          // (__umul24 returns int: the product goes through an unsigned, as in Rows::load, so that an offset of 2^31 elements
+          // or more is zero-extended into the pointer sum, not sign-extended)
+          const unsigned xo = __umul24(j[b], (unsigned)ldx);
+          const float* xj = xc + xo;
 #pragma unroll
-            for (int c = 0; c < CC; ++c) wd[c][v] = fmaf(dx[c], o, wd[c][v]);
-          }
+          for (int c = 0; c < CC; ++c) dx[b][c] = xj[c];
         }
+        unsigned vo[NB];
+#pragma unroll
+        for (int b = 0; b < NB; ++b) vo[b] = __umul24(j[b], (unsigned)rows.ld);
+#pragma unroll
+        for (int b = 0; b < NB; ++b) Vec<V>::ld(rows.base + vo[b], yv[b]);      // Rows::load
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+#pragma unroll
+          for (int v = 0; v < V; ++v) yv[b][v] += rows.u[v];
+#pragma unroll
+          for (int c = 0; c < CC; ++c) dx[b][c] -= xi[c];
+        }
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+          if (!TAIL || m + b < k) {
+#pragma unroll
+            for (int v = 0; v < V; ++v) {
+              float xh;
+              const float z = bn_z(yv[b][v], mu[v], rs[v], be[v], 1, xh);
+              float dz = ((z == st.mx[v]) ? q1[v] : 0.f) + q2[v];
+              if (!(z > 0.f)) dz = 0.f;
+              const float o = rs[v] * (dz - c1[v] - xh * c2[v]);
+              acc[v] += o;
+#pragma unroll
+              for (int c = 0; c < CC; ++c) wd[c][v] = fmaf(dx[b][c], o, wd[c][v]);
+            }
+          }
+      };
+      int m = 0;
+      for (; m + NB <= k; m += NB) group(m, std::false_type{});
+      if (m < k) group(m, std::true_type{});
+    } else {
+      for (int m = 0; m < k; m += NB) {
+        float yv[NB][V];
+        rows.load(m, k, yv);
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+          if (m + b < k) {
+            const float* xj = x + (cloud0 + rows.ip[m + b]) * ldx;
+            float dx[CC];
+#pragma unroll
+            for (int c = 0; c < CC; ++c) dx[c] = (c < C) ? xj[c] - xi[c] : 0.f;
+#pragma unroll
+            for (int v = 0; v < V; ++v) {
+              float xh;
+              const float z = bn_z(yv[b][v], mu[v], rs[v], be[v], 1, xh);
+              float dz = ((z == st.mx[v]) ? dmx[v] / st.cnt[v] : 0.f) + dmn[v] * invk;
+              if (!(z > 0.f)) dz = 0.f;
+              const float o = rs[v] * (dz - c1[v] - xh * c2[v]);
+              acc[v] += o;
+#pragma unroll
+              for (int c = 0; c < CC; ++c) wd[c][v] = fmaf(dx[c], o, wd[c][v]);
+            }
+          }
+      }
     }
 #pragma unroll
     for (int c = 0; c < CC; ++c)
@@ -525,6 +696,29 @@ __global__ __launch_bounds__(256) void edge_bwd_apply_wgrad_kernel(
     for (int l = 0; l < lanes; ++l) s += sh[(l * 2 * CC + cr) * F + ff];
     out[(int64_t)(cr < CC ? c : C + c) * F + ff] = s;
   }
+}
+
+template <int CC>
+__global__ __launch_bounds__(256) void edge_bwd_apply_wgrad_kernel(
+    Src src, int64_t R, int k, int F, const float* __restrict__ mean, const float* __restrict__ rstd,
+    const float* __restrict__ beta, const float* __restrict__ dmax, int64_t lddmax, const float* __restrict__ dmean,
+    int64_t lddmean, const float* __restrict__ mx_in, int64_t ldmx, const float* __restrict__ cnt_in,
+    const double* __restrict__ red, const float* __restrict__ x, int64_t ldx, int C, float* __restrict__ partial, int fv_shift) {
+  edge_bwd_apply_wgrad_body<CC, false>(src, R, k, F, mean, rstd, beta, dmax, lddmax, dmean, lddmean, mx_in, ldmx, cnt_in, red,
+                                       x, ldx, C, partial, fv_shift);
+}
+
+// C == CC exactly (3: raw coordinates; 4: the reference's other input width), a kernel of its own so that the run-time-C kernel
+// above keeps its code and registers as the fallback (DGCNN_EDGE_VALU=0; C = 1, 2; an ldx the 24-bit row offset cannot hold).
+template <int CC>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CC == 3 ? 3 : 2, CC == 3 ? 3 : 2))) void
+edge_bwd_apply_wgrad_exact_kernel(
+    Src src, int64_t R, int k, int F, const float* __restrict__ mean, const float* __restrict__ rstd,
+    const float* __restrict__ beta, const float* __restrict__ dmax, int64_t lddmax, const float* __restrict__ dmean,
+    int64_t lddmean, const float* __restrict__ mx_in, int64_t ldmx, const float* __restrict__ cnt_in,
+    const double* __restrict__ red, const float* __restrict__ x, int64_t ldx, float* __restrict__ partial, int fv_shift) {
+  edge_bwd_apply_wgrad_body<CC, true>(src, R, k, F, mean, rstd, beta, dmax, lddmax, dmean, lddmean, mx_in, ldmx, cnt_in, red,
+                                      x, ldx, CC, partial, fv_shift);
 }
 
 // ---- k = 1 (per-point layers: conv1, shortcut, merged, FC, Final): column-fixed streaming kernels -------------
@@ -998,6 +1192,18 @@ inline Src edge_src(const float* V, int64_t ldv, const float* U, int64_t ldu, co
   return s;
 }
 
+// DGCNN_EDGE_VALU=0 (dgcnn_edge_valu(0) in-process): the edge-level passes as they were before the instruction-count forms of
+// DESIGN 9.8 -- the loop of bn_act_kreduce_kernel<4, true> for every k, edge_bwd_apply_wgrad_kernel<4> with its run-time C.  Same bits
+// either way (tests/test_gpu_edge_valu.py); the old forms also serve the shapes the new ones do not take.
+int g_edge_valu = -1;
+bool edge_valu_on() {
+  if (g_edge_valu < 0) {
+    const char* e = getenv("DGCNN_EDGE_VALU");
+    g_edge_valu = (e && e[0] == '0') ? 0 : 1;
+  }
+  return g_edge_valu == 1;
+}
+
 inline unsigned grid8(unsigned g) { return (g + 7u) & ~7u; }     // XCD-aware item mapping needs a multiple of 8
 
 // shared argument checks of the gather-sourced (edge) variants
@@ -1026,8 +1232,23 @@ int launch_act_kreduce(const char* what, Src src, int64_t R, int k, int F, const
                    (!out2 || ((ldout2 % 4 == 0) && a16(out2))) && (!cnt_out || a16(cnt_out));
   if (G) {
     DG_REQUIRE(vec, DGCNN_EINVAL, "%s: outputs must be 16-byte aligned with leading dimensions %% 4 == 0", what);
-    dg::launch((bn_act_kreduce_kernel<4, true>), dim3(grid8(grid_for(R * (F / 4)))), dim3(256), 0, st, src, R, k, F,
-                       mean, rstd, beta, relu, max_out, ldmax, mean_out, ldmean, out2, ldout2, cnt_out, shift_of(F / 4));
+    const dim3 grid(grid8(grid_for(R * (F / 4))));
+    const int held = (edge_valu_on() && relu == 1 && k <= HELD_K) ? (k + NB - 1) / NB : 0;     // groups of NB rows held in registers
+#define DG_HELD(G_)                                                                                                              \
+  dg::launch((bn_act_kreduce_held_kernel<(G_) * NB>), grid, dim3(256), 0, st, src, R, k, F, mean, rstd, beta, max_out, ldmax,    \
+             mean_out, ldmean, out2, ldout2, cnt_out, shift_of(F / 4))
+    static_assert(HELD_GROUPS == 5, "one case per group count");
+    switch (held) {
+      case 1: DG_HELD(1); break;
+      case 2: DG_HELD(2); break;
+      case 3: DG_HELD(3); break;
+      case 4: DG_HELD(4); break;
+      case 5: DG_HELD(5); break;
+      default:
+        dg::launch((bn_act_kreduce_kernel<4, true>), grid, dim3(256), 0, st, src, R, k, F, mean, rstd, beta, relu, max_out, ldmax,
+                   mean_out, ldmean, out2, ldout2, cnt_out, shift_of(F / 4));
+    }
+#undef DG_HELD
   } else if (vec && k == 1 && !mean_out) {
     const K1Grid g = k1_grid(R, F, 4096);
     dg::launch(bn1_act_kernel, g.grid, dim3(256), 0, st, src.Y, R, F, g.FVB, g.RP, mean, rstd, beta, relu, max_out,
@@ -1330,6 +1551,12 @@ extern "C" int dgcnn_bn1_bwd_class_f32(const float* T, int64_t R, int F, const f
   return dg::check_launch("dgcnn_bn1_bwd_class_f32");
 }
 
+extern "C" int dgcnn_edge_valu(int on) {
+  const int prev = edge_valu_on() ? 1 : 0;
+  if (on >= 0) g_edge_valu = on ? 1 : 0;
+  return prev;
+}
+
 namespace dg {
 void launch_reduce_partials(const float* part, int splits, int M, int N, float* C, int64_t ldc, float beta, hipStream_t st);
 // slots of a backward reduction -> slot 0 (+ d(beta)); edge_mlp_bf16.hip
@@ -1361,9 +1588,20 @@ extern "C" int dgcnn_edge_bn_bwd_apply_wgrad_f32(const float* V, int64_t ldv, co
   const size_t need = (size_t)grid * 2 * C * F * sizeof(float);
   DG_REQUIRE(ws_bytes >= need, DGCNN_ENOSPC, "dgcnn_edge_bn_bwd_apply_wgrad_f32: workspace too small (%zu < %zu)", ws_bytes, need);
   const size_t shb = (size_t)(256 / FV) * 2 * 4 * F * sizeof(float);
-  dg::launch((edge_bwd_apply_wgrad_kernel<4>), dim3(grid), dim3(256), shb, st, edge_src(V, ldv, U, ldu, idx, N), R, k, F,
-                     mean, rstd, beta, dmax, lddmax, dmean, lddmean, mx_in, ldmx, cnt_in, red, x, ldx, C,
-                     reinterpret_cast<float*>(ws), shift_of(FV));
+  // the exact-width form takes row offsets inside a cloud as unsigned 32-bit element counts from one 24-bit multiply: index < N < 2^24,
+  // ldx < 2^24 and N * ldx < 2^32 (N * ldv < 2^32: check_edge); anything else keeps the run-time-C kernel and its 64-bit x offsets
+  const bool exact = edge_valu_on() && (C == 3 || C == 4) && ldx >= C && ldx < (1 << 24) && (int64_t)N * ldx < (1ll << 32);
+  const Src src = edge_src(V, ldv, U, ldu, idx, N);
+  float* part = reinterpret_cast<float*>(ws);
+  if (exact && C == 3)
+    dg::launch((edge_bwd_apply_wgrad_exact_kernel<3>), dim3(grid), dim3(256), shb / 4 * 3, st, src, R, k, F, mean, rstd, beta, dmax,
+               lddmax, dmean, lddmean, mx_in, ldmx, cnt_in, red, x, ldx, part, shift_of(FV));
+  else if (exact)
+    dg::launch((edge_bwd_apply_wgrad_exact_kernel<4>), dim3(grid), dim3(256), shb, st, src, R, k, F, mean, rstd, beta, dmax,
+               lddmax, dmean, lddmean, mx_in, ldmx, cnt_in, red, x, ldx, part, shift_of(FV));
+  else
+    dg::launch((edge_bwd_apply_wgrad_kernel<4>), dim3(grid), dim3(256), shb, st, src, R, k, F, mean, rstd, beta, dmax, lddmax,
+               dmean, lddmean, mx_in, ldmx, cnt_in, red, x, ldx, C, part, shift_of(FV));
   rc = dg::check_launch("dgcnn_edge_bn_bwd_apply_wgrad_f32");
   if (rc) return rc;
   dg::launch_reduce_partials(reinterpret_cast<const float*>(ws), (int)grid, 2 * C, F, dW0, (int64_t)F, 1.0f, st);

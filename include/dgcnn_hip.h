@@ -373,6 +373,11 @@ int dgcnn_edge_bn_bwd_apply_wgrad_f32(const float* V, int64_t ldv, const float* 
                                       const float* mx_in, int64_t ldmx, const float* cnt_in, double* red,
                                       const float* x, int64_t ldx, int C, float* dW0, float* dbeta, float dbeta_beta,
                                       void* ws, size_t ws_bytes, void* stream);
+/* Process switch of the instruction-count forms of the edge-level passes: the register-held max / mean / count walk of
+ * dgcnn_edge_bn_act_kreduce_f32 (ReLU, k <= 20) and the exact-width first-layer pass of dgcnn_edge_bn_bwd_apply_wgrad_f32 (C = 3, 4).
+ * on = 0: the earlier kernels' code for every shape; on > 0: the new forms where they apply; on < 0 only queries.  Returns the
+ * previous value.  Initialised once from $DGCNN_EDGE_VALU (0 = off), else on.  Results are bit-identical either way. */
+int dgcnn_edge_valu(int on);
 
 /* ---- plain fp32 MFMA GEMM: every other slim.conv2d 1x1 (ops.py:62-70,125-133,153-160;
  * model.py:46-53,65-72,94-101) and their dgrad / wgrad --------------------------------------

@@ -8,7 +8,8 @@ import collections
 import csv
 import sys
 
-KEEP = ("bn_act_kreduce_kernel<4, true>", "bn_bwd_apply_kernel<4, true>", "edge_bwd_apply_wgrad_kernel", "edge_gather_add_kernel",
+KEEP = ("bn_act_kreduce_kernel<4, true>", "bn_act_kreduce_held_kernel", "bn_bwd_apply_kernel<4, true>", "edge_bwd_apply_wgrad_kernel",
+        "edge_bwd_apply_wgrad_exact_kernel", "edge_gather_add_kernel",
         "csr_gather_sum_kernel", "edge_mlp_bf16_kernel", "bn1_act_kernel", "bn1_bwd_kernel<true>")
 d = collections.defaultdict(lambda: collections.defaultdict(list))
 seen = set()
