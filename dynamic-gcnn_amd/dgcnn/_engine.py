@@ -812,6 +812,65 @@ def knn_cross(q2d, p2d, B, M, N, k, qseg=None, pseg=None, want_dist=False):
     return (idx, dist) if want_dist else idx
 
 
+INTERP_MAX_K = KNN_CROSS_MAX_K               # interp.hip reads what the search between two sets returns
+INTERP_MIN_EPS = 1e-30                       # k / eps must not overflow
+
+
+def check_interp_eps(eps):
+    eps = float(eps)
+    if not (INTERP_MIN_EPS <= eps < float("inf")):
+        raise ValueError("interpolate: eps=%r must be finite and at least %g" % (eps, INTERP_MIN_EPS))
+    return eps
+
+
+def interpolate(f2d, idx, dist, B, M, N, k, packed, eps, out=None):
+    """Feature interpolation between two point sets (dgcnn_interp_f32, include/dgcnn_hip.h K6): y (B*M, F) -- every query row the
+    inverse-distance-weighted mean of the rows of f2d (B*N, F) that idx (B,M,k) int32 names, weights from dist (B,M,k) float32,
+    both as knn_cross returns them.  packed: B = 1, M / N = the towers' rows and idx holds rows of the candidate tower.
+    out: a 2-D (B*M, F) view with its own leading dimension (a column slice of a wider buffer) to write into.
+    Recorded: d(f2d) += the weighted sums over the transposed graph (dgcnn_interp_bwd_f32: fixed order, no float atomics); the
+    coordinates and the weights get no gradient."""
+    c = ctx()
+    eps = check_interp_eps(eps)
+    p_rows, F = f2d.shape
+    q_rows = B * M
+    if p_rows != B * N:
+        raise ValueError("interpolate: features have %d rows, the candidate set %d" % (p_rows, B * N))
+    if not 1 <= k <= INTERP_MAX_K:
+        raise ValueError("interpolate: k=%d must be in [1, %d]" % (k, INTERP_MAX_K))
+    if F % 4 or F > 1024 or F <= 0:
+        raise ValueError("interpolate: features need F %% 4 == 0 and F <= 1024, got F=%d" % F)
+    if tuple(idx.shape) != (B, M, k) or tuple(dist.shape) != (B, M, k):
+        raise ValueError("interpolate: graph must be idx, dist of shape %s, got %s and %s" % ((B, M, k), tuple(idx.shape),
+                                                                                           tuple(dist.shape)))
+    if idx.dtype != torch.int32 or dist.dtype != torch.float32:
+        raise TypeError("interpolate: graph must be (int32 idx, float32 dist), got %s and %s" % (idx.dtype, dist.dtype))
+    H.require_gpu(f2d, idx, dist, out)
+    idx, dist = idx.contiguous(), dist.contiguous()
+    y = c.new_buffer(q_rows, F) if out is None else out
+    if tuple(y.shape) != (q_rows, F):
+        raise ValueError("interpolate: out must be %s, got %s" % ((q_rows, F), tuple(y.shape)))
+    a = torch.empty((q_rows, k), dtype=torch.float32, device=f2d.device) if c.recording else None
+    Md, Nd = (0, 0) if packed else (M, N)
+    edges = float(q_rows) * k
+    H.call("dgcnn_interp_f32", f2d.data_ptr(), H.ld2(f2d), idx.data_ptr(), dist.data_ptr(), q_rows, p_rows, Md, Nd, k, F, eps,
+           H._p(a), y.data_ptr(), H.ld2(y), tag="interp_fwd_kernel", work=4.0 * (edges * F + q_rows * F + 2 * edges),
+           nbytes=4.0 * (float(p_rows) * F + q_rows * F + 2 * edges))
+    if c.recording:
+        def bwd():
+            dy, df = c.grad(y), c.grad(f2d)
+            if dy is None or df is None:
+                return
+            ws, nws = _knn_workspace(f2d, "dgcnn_interp_bwd_workspace_bytes", q_rows, p_rows, k)
+            H.call("dgcnn_interp_bwd_f32", dy.data_ptr(), H.ld2(dy), idx.data_ptr(), a.data_ptr(), q_rows, p_rows, Md, Nd, k, F,
+                   df.data_ptr(), H.ld2(df), 1, ws.data_ptr(), nws,
+                   tag="interp_bwd[count+scan+fill+rank+interp_bwd_gather_kernel]",
+                   work=4.0 * (edges * F + 2 * float(p_rows) * F + 6 * edges),
+                   nbytes=4.0 * (q_rows * F + 2 * float(p_rows) * F + 2 * edges))
+        c.tape.append(bwd)
+    return y
+
+
 def _tile_m(M, N):
     """Mirror of gemm.hip:tile_m (only used to name the kernel instance in bench.py's roofline tags)."""
     return 128

@@ -122,6 +122,108 @@ def k_nn(points, k, offsets=None, queries=None, query_offsets=None, return_dist=
 knn = k_nn
 
 
+def _interp_rows(t, what, packed, rank4=False):
+    """(clouds, rows per cloud, channels) of an argument of `interpolate`, from its shape alone: dense (B,N,C) [(B,N,1,C) with rank4],
+    packed (R,C) or (1,R,C) [(1,R,1,C) with rank4]"""
+    shp = tuple(t.shape)
+    if rank4 and len(shp) == 4:
+        if shp[2] != 1:
+            raise ValueError("interpolate: a rank-4 %s has a singleton axis -2, got %s" % (what, shp))
+        shp = (shp[0], shp[1], shp[3])
+    if packed:
+        if len(shp) == 2:
+            return 1, shp[0], shp[1]
+        if len(shp) == 3 and shp[0] == 1:
+            return 1, shp[1], shp[2]
+        raise ValueError("interpolate: a packed %s tower is (R,C) or (1,R,C), got %s" % (what, tuple(t.shape)))
+    if len(shp) != 3:
+        raise ValueError("interpolate: %s must be (B,N,C), got %s" % (what, tuple(t.shape)))
+    return shp
+
+
+def interpolate(features, points, queries, k=3, offsets=None, query_offsets=None, eps=1e-16, graph=None, skip=None):
+    """Carry features from one point set to another (PointNet++ feature propagation, PyG's knn_interpolate): every query row receives
+    the inverse-distance-weighted mean of the features of its k nearest `points`, weights 1 / max(d, eps) over the squared distances
+    k_nn returns, normalised to sum 1 (include/dgcnn_hip.h K6 states the arithmetic bit for bit).
+    features (B,N,F) or (B,N,1,F) live on `points` (B,N,C); queries (B,M,C); the result is (B,M,1,F).  Packed towers: features (R,F),
+    (1,R,F) or (1,R,1,F), points (R,C) or (1,R,C) with offsets, queries (Rq,C) or (1,Rq,C) with query_offsets (the rules of k_nn's
+    search between two sets); the result is (1,Rq,1,F).
+    graph=(idx, dist): a graph the caller already has from k_nn(points, k, queries=..., return_dist=True); points and queries may
+    then be None.  skip (B,M,Cs) [packed: (Rq,Cs) or (1,Rq,Cs)]: the skip connection of a feature-propagation block -- the result
+    is (B,M,1,F+Cs) = [interpolated | skip] in one buffer, without a concat pass.
+    Recorded, the features and skip receive gradients (fixed order, the same bits run to run); the coordinates and the weights do
+    not -- k_nn has no backward.  The weights of near-coincident points inherit the absolute error of k_nn's distances."""
+    k = int(k)
+    if k < 1 or k > E.INTERP_MAX_K:
+        raise ValueError("interpolate: k=%d must be in [1, %d], the limit of k_nn between two sets" % (k, E.INTERP_MAX_K))
+    eps = E.check_interp_eps(eps)
+    if (offsets is None) != (query_offsets is None):
+        raise ValueError("interpolate: packed towers need offsets (points, features) AND query_offsets (queries); got only %s"
+                         % ("offsets" if query_offsets is None else "query_offsets"))
+    packed = offsets is not None
+    B, N, F = _interp_rows(features, "features", packed, rank4=True)
+    if F % 4 or F > 1024 or F < 1:
+        raise ValueError("interpolate: features need F %% 4 == 0 and F <= 1024 channels, got F=%d" % F)
+    C = None
+    if points is not None:
+        Bp, Np, C = _interp_rows(points, "points", packed)
+        if (Bp, Np) != (B, N):
+            raise ValueError("interpolate: features cover %d clouds of %d rows, points %d of %d" % (B, N, Bp, Np))
+    M = None
+    if queries is not None:
+        Bq, M, Cq = _interp_rows(queries, "queries", packed)
+        if Bq != B:
+            raise ValueError("interpolate: %d clouds of queries, %d of points" % (Bq, B))
+        if C is not None and Cq != C:
+            raise ValueError("interpolate: queries have %d channels, points %d" % (Cq, C))
+    if graph is not None:
+        if not (isinstance(graph, (tuple, list)) and len(graph) == 2):
+            raise ValueError("interpolate: graph must be the (idx, dist) pair of k_nn(..., return_dist=True)")
+        gi, gd = tuple(graph[0].shape), tuple(graph[1].shape)
+        if len(gi) != 3 or gi != gd or gi[0] != B or gi[2] != k or (M is not None and gi[1] != M):
+            raise ValueError("interpolate: graph must hold idx and dist of shape (%d, %s, %d), got %s and %s"
+                             % (B, "M" if M is None else M, k, gi, gd))
+        M = gi[1]
+    elif points is None or queries is None:
+        raise ValueError("interpolate: points and queries are needed when no graph is given")
+    pseg = qseg = None
+    if packed:
+        pseg = offsets if isinstance(offsets, E.Segments) else E.Segments(offsets)
+        if pseg.rows != N:
+            raise ValueError("interpolate: offsets end at %d, the features have %d rows" % (pseg.rows, N))
+        qseg = query_offsets if isinstance(query_offsets, E.Segments) else E.Segments(query_offsets)
+        if qseg.rows != M:
+            raise ValueError("interpolate: query_offsets end at %d, the query tower has %d rows" % (qseg.rows, M))
+        if qseg.nseg != pseg.nseg:
+            raise ValueError("interpolate: query_offsets name %d clouds, offsets %d" % (qseg.nseg, pseg.nseg))
+        if k > pseg.min_n:
+            raise ValueError("interpolate: k=%d exceeds the smallest candidate cloud (%d rows)" % (k, pseg.min_n))
+    elif k > N:
+        raise ValueError("interpolate: k=%d exceeds the N=%d points of a cloud" % (k, N))
+    Cs = 0
+    if skip is not None:
+        Bs, Ms, Cs = _interp_rows(skip, "skip", packed, rank4=True)
+        if (Bs, Ms) != (B, M):
+            raise ValueError("interpolate: skip covers %d clouds of %d rows, the queries %d of %d" % (Bs, Ms, B, M))
+        if Cs % 4 or Cs < 1:
+            raise ValueError("interpolate: skip needs Cs %% 4 == 0 channels, got Cs=%d" % Cs)
+    # ---- device work from here on
+    if graph is None:
+        idx, dist = k_nn(points, k, offsets=pseg, queries=queries, query_offsets=qseg, return_dist=True)
+    else:
+        idx, dist = graph
+    f2d = E.as2d(features)[0]
+    if skip is None:
+        return E.rank4(E.interpolate(f2d, idx, dist, B, M, N, k, packed, eps), B, M)
+    s2d = E.as2d(skip)[0]
+    buf = E.ctx().new_buffer(B * M, F + Cs)
+    E.interpolate(f2d, idx, dist, B, M, N, k, packed, eps, out=buf[:, :F])
+    tail = buf[:, F:]
+    H.call("dgcnn_copy2d_f32", s2d.data_ptr(), H.ld2(s2d), tail.data_ptr(), H.ld2(tail), B * M, Cs, 0)
+    E_copy_grad(s2d, tail)
+    return E.rank4(buf, B, M)
+
+
 def edges(points, k=20, offsets=None):
     """dgcnn/ops.py:21-40.  (B,N,C) -> edge features (B,N,k,2C) = concat[x_i, x_j - x_i].  offsets: a packed tower (k_nn), (1,R,k,2C)."""
     idx = k_nn(points, k, offsets=offsets)

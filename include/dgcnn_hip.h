@@ -198,6 +198,45 @@ int dgcnn_knn_cross_f32(const float* q, int64_t ldq, const float* p, int64_t ldp
                         const int32_t* p_off, int q_rows, int p_rows, int max_m, int min_n, int max_n, int32_t* idx, float* dist,
                         void* ws, size_t ws_bytes, void* stream);
 
+/* ---- K6: feature interpolation between two point sets (csrc/interp.hip) -- PointNet++ feature propagation, PyG's knn_interpolate:
+ * y(query i) = the inverse-distance-weighted mean of the feature rows of its k nearest candidates, from the (idx, dist) pair that
+ * dgcnn_knn_cross_f32 returns.  NORMATIVE arithmetic: row i has the entries (j_m, D_m), m = 0 ... k-1, in the order the search
+ * returned them; every product, sum and quotient below is rounded to fp32 once, nothing is fused or reassociated, `/` is the
+ * correctly rounded division:
+ *     w_m = (D_m < +inf) ? 1.0f / fmaxf(D_m, eps) : 0.0f      +inf and NaN give 0; D_m <= eps (also negative, -inf) gives 1 / eps
+ *     W   = w_0;  W = W + w_m                      for m = 1 ... k-1, ascending
+ *     a_m = (W > 0) ? w_m / W : 0.0f               a row whose k distances are all +inf: every a_m = 0, y_i = 0, no gradient
+ *     y_i[f] = a_0 * feat[j_0][f];  y_i[f] = y_i[f] + a_m * feat[j_m][f]     for m = 1 ... k-1, ascending
+ *   backward, with the edge id e = i * k + m (the gradient of the FEATURES only: coordinates and weights carry none, as the k-NN has
+ *   no backward here and PyG takes the weights under no_grad):
+ *     g_j[f] = 0;  g_j[f] = g_j[f] + a_e * dy_i[f]            over the edges e whose candidate row is j, in ASCENDING e
+ *     dfeat_j[f] = g_j[f] (beta = 0; a row nobody interpolates from gets 0)   or   dfeat_j[f] + g_j[f] (beta = 1)
+ *   No float atomics: one form, the same bits run to run, in every mode.  Non-finite features propagate as the expressions say
+ *   (0 * inf = NaN).  The distances carry K1's absolute error of about 2^-23 (s_i + s_j), so the weights of near-coincident points
+ *   are noisy: inherited from the search, not corrected here.
+ * feat (p_rows, F; row stride ldf), idx / dist (q_rows, k) dense, y (q_rows, F; row stride ldy: a column slice of a wider buffer is
+ *   fine).  M > 0: dense towers -- the candidate row of entry (i, m) is (i / M) * N + idx[i][m] (idx cloud-local; q_rows = B M and
+ *   p_rows = B N).  M == 0 (then N == 0): idx holds rows of the candidate tower, what the packed search returns.  The contents of idx
+ *   are trusted (the search guarantees k distinct rows of the query's own cloud).
+ * a: NULL, or (q_rows, k) floats that receive the normalised weights a_m -- what the backward reads.
+ * eps: the clamp of the distance (PyG: 1e-16); finite and at least 1e-30, so that k / eps cannot overflow.
+ * 1 <= k <= 64; F % 4 == 0, F <= 1024; 16-byte aligned feat, y, dy, dfeat, ws; leading dimensions % 4 == 0 and >= F;
+ *   q_rows k < 2^31.  The forward works the k weights of a row out once (not once per channel lane) and writes no (q_rows, k, F) tensor.
+ * Backward workspace, dgcnn_interp_bwd_workspace_bytes(q_rows, p_rows, k) (0 for sizes the entry refuses) =
+ *   [off: p_rows + 1 int32 | counts: p_rows int32 | rev: q_rows k int32 | rev in ascending order: q_rows k int32],
+ *   each part rounded up to 256 bytes: the transposed adjacency of the bipartite graph by integer counting sort (integer atomics
+ *   only); every edge is then placed by the number of smaller edge ids in its bucket, which reads deg_j words per edge -- sum of
+ *   deg_j^2 in all, q_rows k * (q_rows k / p_rows) on average, quadratic in the heaviest bucket.
+ * DGCNN_EUNSUP for k > 64, F % 4 != 0, F > 1024 or q_rows k >= 2^31; DGCNN_ENOSPC for a workspace that is too small; DGCNN_EINVAL for
+ *   a null pointer (a excepted in the forward), k < 1, F < 1, rows < 1, a leading dimension below F or not a multiple of 4, a
+ *   misaligned base, eps outside [1e-30, +inf), M > 0 with q_rows % M != 0 or p_rows != (q_rows / M) N, M == 0 with N != 0, beta
+ *   outside {0, 1}.  Every refusal happens before any launch, with the reason in dgcnn_last_error. */
+int dgcnn_interp_f32(const float* feat, int64_t ldf, const int32_t* idx, const float* dist, int q_rows, int p_rows, int M, int N,
+                     int k, int F, float eps, float* a, float* y, int64_t ldy, void* stream);
+int64_t dgcnn_interp_bwd_workspace_bytes(int q_rows, int p_rows, int k);
+int dgcnn_interp_bwd_f32(const float* dy, int64_t lddy, const int32_t* idx, const float* a, int q_rows, int p_rows, int M, int N,
+                         int k, int F, float* dfeat, int64_t lddf, int beta, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- K3 in its bf16-operand form (BASELINE configs[2] "bf16 edge-MLP MFMA"): conv0 of an EdgeConv layer, ops.py:21-52 ------
  * E[e] = [x_i, x_j - x_i] formed in fp32 and rounded to bf16 once (RNE), W0 (2C x F, row-major) rounded to bf16 once,
  * y = E W0 on v_mfma_f32_32x32x16_bf16 with fp32 accumulation; neither E nor y is written by the two forward passes:
