@@ -158,7 +158,7 @@ struct Rows {
       // time of the forward max/mean pass (profiles/r03/kreduce_probe.txt)
       unsigned row[NB];
 #pragma unroll
-      for (int b = 0; b < NB; ++b) row[b] = __umul24((unsigned)ip[(m + b < k) ? (m + b) : (k - 1)], (unsigned)ld);
+      for (int b = 0; b < NB; ++b) row[b] = row_offset24((unsigned)ip[(m + b < k) ? (m + b) : (k - 1)], (unsigned)ld);
 #pragma unroll
       for (int b = 0; b < NB; ++b) Vec<V>::ld(base + row[b], y[b]);
 #pragma unroll
@@ -226,7 +226,7 @@ __device__ __forceinline__ void kreduce_held(const Rows<4, true>& rows, int k, c
   for (int m = 0; m < KC; ++m) {
     // Rows::load's gather; only the last group can reach past k - 1 (KC - NB < k), the rows before it take their index from a
     // constant offset
-    const unsigned row = __umul24((unsigned)rows.ip[(m < KC - NB + 1 || m < k) ? m : (k - 1)], (unsigned)rows.ld);
+    const unsigned row = row_offset24((unsigned)rows.ip[(m < KC - NB + 1 || m < k) ? m : (k - 1)], (unsigned)rows.ld);
     float yv[V];
     Vec<V>::ld(rows.base + row, yv);
 #pragma unroll
@@ -608,16 +608,16 @@ __device__ __forceinline__ void edge_bwd_apply_wgrad_body(
         for (int b = 0; b < NB; ++b) j[b] = (unsigned)rows.ip[(!TAIL || m + b < k) ? (m + b) : (k - 1)];
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
-          // (__umul24 returns int: the product goes through an unsigned, as in Rows::load, so that an offset of 2^31 elements
-          // or more is zero-extended into the pointer sum, not sign-extended)
-          const unsigned xo = __umul24(j[b], (unsigned)ldx);
+          // (row_offset24's unsigned product, as in Rows::load: an offset of 2^31 elements or more is zero-extended into the
+          // pointer sum, not sign-extended)
+          const unsigned xo = row_offset24(j[b], (unsigned)ldx);
           const float* xj = xc + xo;
 #pragma unroll
           for (int c = 0; c < CC; ++c) dx[b][c] = xj[c];
         }
         unsigned vo[NB];
 #pragma unroll
-        for (int b = 0; b < NB; ++b) vo[b] = __umul24(j[b], (unsigned)rows.ld);
+        for (int b = 0; b < NB; ++b) vo[b] = row_offset24(j[b], (unsigned)rows.ld);
 #pragma unroll
         for (int b = 0; b < NB; ++b) Vec<V>::ld(rows.base + vo[b], yv[b]);      // Rows::load
 #pragma unroll

@@ -98,6 +98,13 @@ __device__ __forceinline__ uint32_t dropout_threshold(float keep) {
   return (keep >= 1.f) ? 0xffffffffu : (uint32_t)((double)keep * 4294967296.0);
 }
 
+// ---- element offset of a gathered row: j * ld in ONE full-rate multiply (v_mul_u32_u24) -- the only caller of __umul24.
+// Contract (the host checks of the gathering entries: check_edge, check_seg_edge, dgcnn_edge_gather_add_f32): j < 2^24, ld < 2^24,
+// j * ld < 2^32.  The product may be 2^31 or more, and HIP declares __umul24 as returning int: the UNSIGNED result must enter the
+// address zero-extended (`p + row_offset24(j, ld)`, or through an `unsigned` variable).  Never cast it to int or add it to a signed
+// offset first -- a sign-extended product addresses 2^32 elements before the intended row.
+__device__ __forceinline__ unsigned row_offset24(unsigned j, unsigned ld) { return (unsigned)__umul24(j, ld); }
+
 // fp32 -> the nearest bf16 value (ties to even), kept as fp32 bits.  The carry of the rounding add would run a NaN whose upper
 // mantissa bits are all ones into the exponent and sign (0x7fffffff -> -0.0): a NaN stays a (quiet) NaN of the same sign instead,
 // as v_cvt_pk_bf16_f32 keeps it.

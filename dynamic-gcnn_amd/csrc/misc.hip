@@ -260,7 +260,7 @@ __global__ __launch_bounds__(256) void edge_gather_add_kernel(const float* __res
 #pragma unroll
         for (int q = 0; q < 4; ++q) row[q] = ip[(m + q < knn) ? (m + q) : (knn - 1)];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = *reinterpret_cast<const float4*>(vb + __umul24((unsigned)row[q], (unsigned)ldv));   // (full-rate 24-bit multiply: N, ldv < 2^24, N * ldv < 2^32: host check)
+        for (int q = 0; q < 4; ++q) v[q] = *reinterpret_cast<const float4*>(vb + row_offset24((unsigned)row[q], (unsigned)ldv));   // (N, ldv < 2^24, N * ldv < 2^32: host check; offsets of 2^31 and more zero-extended)
 #pragma unroll
         for (int q = 0; q < 4; ++q)
           if (m + q < knn) {

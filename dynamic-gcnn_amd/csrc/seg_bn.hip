@@ -162,8 +162,8 @@ __global__ __launch_bounds__(256) void seg_edge_stats_partial_kernel(const float
 #pragma unroll
           for (int j = 0; j < 4; ++j) row[j] = ip[(m + j < knn) ? (m + j) : (knn - 1)];
 #pragma unroll
-          for (int j = 0; j < 4; ++j)   // (full-rate 24-bit multiply: rows, ldv < 2^24, rows * ldv < 2^32: host check)
-            v[j] = *reinterpret_cast<const float4*>(V + f + __umul24((unsigned)row[j], (unsigned)ldv));
+          for (int j = 0; j < 4; ++j)   // (rows, ldv < 2^24, rows * ldv < 2^32: host check; offsets of 2^31 and more zero-extended)
+            v[j] = *reinterpret_cast<const float4*>(V + f + row_offset24((unsigned)row[j], (unsigned)ldv));
 #pragma unroll
           for (int j = 0; j < 4; ++j)
             if (m + j < knn) {
@@ -284,7 +284,7 @@ __global__ __launch_bounds__(256) void seg_edge_bn_act_kreduce_kernel(const floa
       unsigned row[4];
       float y[4][4];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) row[j] = __umul24((unsigned)ip[(m + j < k) ? (m + j) : (k - 1)], (unsigned)ldv);
+      for (int j = 0; j < 4; ++j) row[j] = row_offset24((unsigned)ip[(m + j < k) ? (m + j) : (k - 1)], (unsigned)ldv);
 #pragma unroll
       for (int j = 0; j < 4; ++j) Vec<4>::ld(vb + row[j], y[j]);
 #pragma unroll
@@ -674,7 +674,7 @@ __global__ __launch_bounds__(256) void seg_edge_bn_bwd_apply_kernel(const float*
       unsigned row[4];
       float y[4][4];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) row[j] = __umul24((unsigned)ip[(m + j < k) ? (m + j) : (k - 1)], (unsigned)ldv);
+      for (int j = 0; j < 4; ++j) row[j] = row_offset24((unsigned)ip[(m + j < k) ? (m + j) : (k - 1)], (unsigned)ldv);
 #pragma unroll
       for (int j = 0; j < 4; ++j) Vec<4>::ld(vb + row[j], y[j]);
 #pragma unroll

@@ -330,7 +330,11 @@ int dgcnn_edge_gather_sum_f32(const float* dY, const int32_t* off, const int32_t
  * backward: dU = sum_m dY (dgcnn_bn_bwd_apply_f32's dYsum), dV = dgcnn_edge_gather_sum_f32(dY);
  *   dWcat = X^T [dU | dV], dX += [dU | dV] Wcat^T (dgcnn_gemm_f32), then
  *   dW0[:C] += dWcat[:, :F] ; dW0[C:] += dWcat[:, F:] - dWcat[:, :F]     dgcnn_edge_wgrad_combine_f32
- * F %% 4 == 0, F <= 1024, 16-byte aligned rows.                                                  */
+ * F %% 4 == 0, F <= 1024, 16-byte aligned rows.
+ * dgcnn_edge_gather_add_f32 and the dgcnn_edge_bn_* entries below address row idx of a cloud as V + idx * ldv with one 24-bit multiply
+ * and a 32-bit unsigned element offset: N < 2^24, ldv < 2^24 and N * ldv < 2^32 (DGCNN_EUNSUP otherwise; nothing is written).  Within
+ * that, a row may start 2^31 elements or more past its cloud's first row.  (dgcnn_edge_bn_bwd_apply_wgrad_f32 takes the same range
+ * for x and ldx in its exact-width form and falls back to 64-bit offsets outside it.)                                              */
 int dgcnn_edge_weight_split_f32(const float* W0, int C, int F, float* Wcat, void* stream);
 int dgcnn_edge_gather_add_f32(const float* V, int64_t ldv, const float* U, int64_t ldu, const int32_t* idx,
                               int B, int N, int k, int F, float* Y, double* stats, void* stream);

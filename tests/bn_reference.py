@@ -269,19 +269,22 @@ def lattice_edge(rng, B, N, k, F, relu):
     return V, U, idx
 
 
-def lattice_precondition(fw, dmax, dmean):
+def lattice_precondition(fw, dmax, dmean, p_xh=1, p_term=LATTICE_P, p_z=2, tie_counts=(1, 2, 4)):
     """Asserts, in float64 / integer arithmetic, that every term lies on the lattice and that no partial sum can leave the
-    exactly representable range: max_f sum |dz xh| 2^p < 2^24 (and the same for sum |dz| and the forward's sum |z| 4).
+    exactly representable range: max_f sum |dz xh| 2^p < 2^24 (and the same for sum |dz| and the forward's sum |z| 2^p_z).
+    The defaults are the lattice above; a finer one names its spacings 2^-p_xh (xh), 2^-p_term (dz xh), 2^-p_z (z), and
+    tie_counts=None where dz is an integer for every tie count that can occur (the lattice assertion on dz then stands for it).
     -> the float64 sums (exact)."""
     dz = dz64(fw, dmax, dmean)
     xh, z = fw.xh.astype(np.float64), fw.z.astype(np.float64)
-    for a, p in ((dz, 0), (xh, 1), (dz * xh, LATTICE_P), (z, 2)):
+    for a, p in ((dz, 0), (xh, p_xh), (dz * xh, p_term), (z, p_z)):
         assert np.array_equal(a * 2 ** p, np.round(a * 2 ** p)), "off the lattice"
-    live = np.abs(dz).sum(1) > 0
-    tl = fw.ties[live]
-    assert np.isin(tl, (1, 2, 4)).all(), "a live point has a tie count outside {1, 2, 4}"
+    if tie_counts is not None:
+        live = np.abs(dz).sum(1) > 0
+        tl = fw.ties[live]
+        assert np.isin(tl, tie_counts).all(), "a live point has a tie count outside %s" % (tie_counts,)
     s = Sums(dz, xh)
-    assert s.abs1.max() * 2 ** LATTICE_P < 2 ** 24 and s.abs0.max() < 2 ** 24
-    assert np.abs(z).sum(1).max() * 4 < 2 ** 24
+    assert s.abs1.max() * 2 ** p_term < 2 ** 24 and s.abs0.max() < 2 ** 24
+    assert np.abs(z).sum(1).max() * 2 ** p_z < 2 ** 24
     assert np.array_equal(dz32(fw, dmax, dmean).astype(np.float64), dz)       # the fp32 dz is the float64 dz
     return s

@@ -122,6 +122,11 @@ KNN_DENSE = [
     # launch_seed_bound takes C = 16, 32, 64 only: any other width gets no bound, and without a bound there is no append-form scan
     knn_row("seeded_c20", 300, 20, 20, [SQ, _mfma(64, 20, "true")], seed="own", sw=dict(seed_min_n=0)),
     knn_row("seeded_c48", 300, 48, 20, [SQ, _mfma(64, 20, "true")], seed="own", sw=dict(seed_min_n=0)),
+    # knn_seeds_used_dense: the seeded probe forms 32-bit element offsets inside a cloud, so seeds are used only while N * ld < 2^31.
+    # ld = 2^20 - 4: N * ld = 2^31 - 8192, the list of seeded_n300; ld = 2^20: N * ld = 2^31, the seeds are dropped (the call does not
+    # fail) and the list is the unseeded one.  The view is built on the device inside an 8.6 GB buffer that is never filled.
+    knn_row("seeded_n2048_ld_below_2_31", 2048, 64, 20, _APPEND("true", 1), B=1, ld=(1 << 20) - 4, seed="own"),
+    knn_row("seeded_n2048_ld_at_2_31", 2048, 64, 20, [SQ, _mfma(64, 20, "true")], B=1, ld=1 << 20, seed="own"),
 ]
 
 

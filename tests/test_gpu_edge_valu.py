@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from far_rows import quarter
 from gpu_helpers import Guard, host
 from launch_trace import launches, names
 
@@ -53,10 +54,6 @@ def same_bits(a, b, what):
     bad = np.argwhere(a != b)
     assert not len(bad), "%s: %d of %d words differ, first at %s: %08x != %08x" % (
         what, len(bad), a.size, tuple(bad[0]), a[tuple(bad[0])], b[tuple(bad[0])])
-
-
-def quarter(rng, shape, lo=-8, hi=9):
-    return (rng.integers(lo, hi, shape) / 4.0).astype(np.float32)
 
 
 def inputs(kind, seed, B, N, k, F):
@@ -275,9 +272,10 @@ def test_first_layer_backward_with_non_finite_rows(H):
 
 
 def test_row_offsets_of_two_to_the_31_elements_and_more(H):
-    """One cloud of 160 rows whose V and x are views into matrices with a leading dimension of 2^24 - 4: rows 128.. start 2^31
-    elements or more past the cloud's first row, inside the N * ld < 2^32 the entries accept.  The 24-bit product must enter the
-    address zero-extended (HIP's __umul24 returns int); forward and backward against the loop kernels, which take this range."""
+    """One cloud of 160 rows whose V and x are views into matrices with a leading dimension of 2^24 - 4: rows 129.. start 2^31
+    elements or more past the cloud's first row (128 * (2^24 - 4) = 2^31 - 512), inside the N * ld < 2^32 the entries accept.  The
+    24-bit product must enter the address zero-extended (HIP's __umul24 returns int); forward and backward against the loop
+    kernels, which take this range.  Every other gathering entry in this range: tests/test_gpu_far_rows.py."""
     B, N, k, F, C = 1, 160, 5, 16, 3
     LD = (1 << 24) - 4
     assert (N - 1) * LD >= 1 << 31 and N * LD < 1 << 32

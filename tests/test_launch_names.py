@@ -92,3 +92,27 @@ def test_row_ids_are_unique_and_rows_are_literal():
         assert len(ids) == len(set(ids))
         for r in table:
             assert r["expect"] and all(isinstance(n, str) and all(isinstance(a, str) for a in a_) for n, a_ in r["expect"]), r["id"]
+
+
+# ------------------------------------------------------------------------------------------------------
+def test_the_24_bit_multiply_has_one_caller():
+    """HIP declares __umul24 as returning int; a gathered row's offset may be 2^31 elements or more and must enter its address
+    zero-extended.  common.h:row_offset24 is the one place that calls it (and returns unsigned) and whose comment carries the
+    contract: nowhere else in csrc does the name occur, in code or in a comment that would invite a copy."""
+    name = "__umul24"
+    hits = []
+    for f in sorted(glob.glob(os.path.join(CSRC, "*"))):
+        if os.path.isfile(f):
+            for n, line in enumerate(open(f, errors="replace").read().split("\n"), 1):
+                if name in line:
+                    hits.append((os.path.basename(f), n, line))
+    assert hits and {h[0] for h in hits} == {"common.h"}, [h[:2] for h in hits]
+    lines = open(os.path.join(CSRC, "common.h")).read().split("\n")
+    code = [h for h in hits if name in h[2].split("//")[0]]
+    assert len(code) == 1 and re.search(r"\bunsigned\s+row_offset24\s*\(\s*unsigned\s+\w+\s*,\s*unsigned\s+\w+\s*\)", code[0][2]), code
+    # the other occurrences: the comment block that ends at the definition
+    assert max(h[1] for h in hits) == code[0][1]
+    first = min(h[1] for h in hits)
+    block = lines[first - 1:code[0][1] - 1]
+    assert all(l.startswith("//") for l in block), "the name occurs outside row_offset24 and its comment"
+    assert any("row_offset24(" in open(os.path.join(CSRC, f)).read() for f in ("bn.hip", "seg_bn.hip", "misc.hip"))
