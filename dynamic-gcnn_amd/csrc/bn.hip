@@ -1195,14 +1195,7 @@ inline Src edge_src(const float* V, int64_t ldv, const float* U, int64_t ldu, co
 // DGCNN_EDGE_VALU=0 (dgcnn_edge_valu(0) in-process): the edge-level passes as they were before the instruction-count forms of
 // DESIGN 9.8 -- the loop of bn_act_kreduce_kernel<4, true> for every k, edge_bwd_apply_wgrad_kernel<4> with its run-time C.  Same bits
 // either way (tests/test_gpu_edge_valu.py); the old forms also serve the shapes the new ones do not take.
-int g_edge_valu = -1;
-bool edge_valu_on() {
-  if (g_edge_valu < 0) {
-    const char* e = getenv("DGCNN_EDGE_VALU");
-    g_edge_valu = (e && e[0] == '0') ? 0 : 1;
-  }
-  return g_edge_valu == 1;
-}
+bool edge_valu_on() { return dg::sw_get(dg::SW_EDGE_VALU) == 1; }
 
 inline unsigned grid8(unsigned g) { return (g + 7u) & ~7u; }     // XCD-aware item mapping needs a multiple of 8
 
@@ -1552,9 +1545,7 @@ extern "C" int dgcnn_bn1_bwd_class_f32(const float* T, int64_t R, int F, const f
 }
 
 extern "C" int dgcnn_edge_valu(int on) {
-  const int prev = edge_valu_on() ? 1 : 0;
-  if (on >= 0) g_edge_valu = on ? 1 : 0;
-  return prev;
+  return dg::sw_set_or_query(dg::SW_EDGE_VALU, on >= 0, on ? 1 : 0);
 }
 
 namespace dg {

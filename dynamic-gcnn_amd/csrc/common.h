@@ -7,6 +7,7 @@
 #include <tuple>
 #include <utility>
 #include "../../include/dgcnn_hip.h"
+#include "switches.h"
 
 namespace dg {
 
@@ -71,10 +72,10 @@ static inline int64_t cap_writers(int64_t g) {
   return (n > DGCNN_STAT_SLOTS && g > n) ? n : g;
 }
 
-// gemm_x3.hip: arithmetic of the plain GEMMs (0 native fp32 MFMA, 6 / 9 = partial products of the exact
-// three-way bf16 split on the bf16 matrix pipe) and its launcher (pv = GemmP*, tiles already planned)
-int gemm_arith();
-void set_gemm_arith(int v);
+// arithmetic of the plain GEMMs (0 native fp32 MFMA, 6 / 9 = partial products of the exact three-way bf16 split on the bf16
+// matrix pipe), and gemm_x3.hip's launcher (pv = GemmP*, tiles already planned)
+inline int gemm_arith() { return sw_get(SW_GEMM_ARITH); }
+inline void set_gemm_arith(int v) { sw_exchange(SW_GEMM_ARITH, v); }
 int x3_tile_m(int M, int N, int K);
 int x3_tile_n(int M, int N, int K);      // 256: the 256 x 256 kernel takes this product; 0: column tile from gemm.hip:tile_n
 void launch_gemm_x3(int asrc, int bsrc, void* pv, hipStream_t st, int bn, int np);

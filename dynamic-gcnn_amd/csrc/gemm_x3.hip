@@ -26,11 +26,6 @@
 #include "gemm_common.h"
 #include <type_traits>
 
-
-#ifndef DGCNN_GEMM_ARITH_DEFAULT
-#define DGCNN_GEMM_ARITH_DEFAULT 6
-#endif
-
 namespace {
 
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
@@ -741,8 +736,6 @@ __global__ __launch_bounds__(512, 2) void gemm_x3q_kernel(GemmP p) {
   gemm_epilogue<E_STORE, BM, BN, true, TM, TN, WR, 512, WCN>(p, acc, reinterpret_cast<float*>(smem_raw), m0, n0, mt, z, t, wr, wc, l31, lh);
 }
 
-int g_arith = -1;      // -1: not resolved yet; 0 native fp32 MFMA; 6 / 9 partial products on the bf16 pipe
-
 template <int AKIND, int BKIND>
 void launch_kind(GemmP& p, hipStream_t st, int bn, int np, dim3 grid) {
   if (bn == 256) {              // the 256-column kernels run the default arithmetic only (other arithmetics: measurements, 256 x 128)
@@ -776,22 +769,10 @@ void launch_kind(GemmP& p, hipStream_t st, int bn, int np, dim3 grid) {
 
 namespace dg {
 
-int gemm_arith() {
-  if (g_arith < 0) {
-    const char* e = getenv("DGCNN_GEMM_ARITH");      // f32 | bf16x6 | bf16x9
-    int v = DGCNN_GEMM_ARITH_DEFAULT;
-    if (e) v = (e[0] == 'f' || e[0] == '0') ? 0 : ((e[0] == '9' || (e[0] == 'b' && e[5] == '9')) ? 9 : ((e[0] == '1' || (e[0] == 'b' && e[5] == '1')) ? 1 : 6));
-    g_arith = v;
-  }
-  return g_arith;
-}
-
-void set_gemm_arith(int v) { g_arith = v; }
-
 // asrc in {A_ROW, A_COL}, bsrc in {B_ROW, B_COL}; operands float4-loadable (checked by the caller).
 // p.mtiles / ntiles / xcd_group / splits / kchunk (multiple of 32 when splits > 1) are set.
-int g_x3_tile_override = 0;      // dgcnn_gemm_x3_tile_override (tools): 0 = the rule below, 128 / 256 = that row tile where legal,
-                                 // 512 = the 256 x 256 kernel where legal
+// dgcnn_gemm_x3_tile_override (tools): 0 = the rule below, 128 / 256 = that row tile where legal, 512 = the 256 x 256 kernel where legal
+static int x3_tile_override() { return sw_get(SW_GEMM_X3_TILE); }
 
 // Tile choice among the three big kernels (all give bit-identical outputs: the per-element k order is the same):
 //   256 x 128 wave-specialised (gemm_x3w2_kernel), 256 x 256 and 192 x 256 unspecialised (gemm_x3q_kernel).
@@ -818,8 +799,9 @@ static void x3_pick(int M, int N, int K, int& bm, int& bn) {
   bm = 256;
   bn = 0;
   if (dg::gemm_arith() != 6 || M <= 128 || N <= 128) return;
-  if (g_x3_tile_override == 512 || g_x3_tile_override == 448) { bm = g_x3_tile_override == 448 ? 192 : 256; bn = 256; return; }
-  if (g_x3_tile_override != 0) return;
+  const int over = x3_tile_override();
+  if (over == 512 || over == 448) { bm = over == 448 ? 192 : 256; bn = 256; return; }
+  if (over != 0) return;
   const bool split = cdiv(M, 256) * cdiv(N, 128) < 128;          // few output tiles: the caller splits the reduction
   double best = x3_cost(M, N, K, 256, 128, split) * 0.98;      // (ties go to the wave-specialised kernel)
   const int cand[2] = {256, 192};
@@ -837,8 +819,9 @@ int x3_tile_n(int M, int N, int K) {
 }
 
 static int x3_tile_m_base(int M, int N, int K) {
-  if (g_x3_tile_override == 128) return 128;
-  if ((g_x3_tile_override == 256 || g_x3_tile_override == 512 || g_x3_tile_override == 448) && M > 128 && N > 64) return 256;
+  const int over = x3_tile_override();
+  if (over == 128) return 128;
+  if ((over == 256 || over == 512 || over == 448) && M > 128 && N > 64) return 256;
   // short reduction, many rows, one or two column tiles: the kernel is bound by the latency of its few slabs -- 64-row tiles put
   // twice the workgroups (and loads in flight) on a CU
   if (dg::gemm_arith() == 6 && K <= 256 && N <= 256 && M >= 8192 && cdiv(M, 128) * cdiv(N, 128) <= 1024) return 64;
@@ -879,7 +862,5 @@ extern "C" int dgcnn_gemm_x3_tile_rows(int M, int N, int K) { return dg::x3_tile
 extern "C" int dgcnn_gemm_x3_tile_cols(int M, int N, int K) { return dg::x3_tile_n(M, N, K); }
 
 extern "C" int dgcnn_gemm_x3_tile_override(int bm) {      // tools: force the 128- or 256-row tile (0 = automatic); returns the previous value
-  const int prev = dg::g_x3_tile_override;
-  dg::g_x3_tile_override = (bm == 128 || bm == 256 || bm == 512 || bm == 448) ? bm : 0;      // 512: 256 x 256, 448: 192 x 256
-  return prev;
+  return dg::sw_exchange(dg::SW_GEMM_X3_TILE, dg::sw_valid(dg::SW_GEMM_X3_TILE, bm) ? bm : 0);      // 512: 256 x 256, 448: 192 x 256
 }

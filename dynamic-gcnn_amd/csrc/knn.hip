@@ -1127,17 +1127,9 @@ __global__ __launch_bounds__(256) void knn_select_kernel(const unsigned long lon
 // Dispatch threshold: with the pipelined re-check the kernel also wins in isolation at (24,2048,64,20) (0.253 vs 0.272 ms), but
 // inside the training step it LOSES there (5.19 vs 5.05 ms/step with the side stream on, 5.06 vs 5.11 with it off): its 54 KB x 3
 // workgroups leave no LDS for the transposed-adjacency build that runs on the side stream.  So: N >= 8192 only.
-int g_knn_bf16f = -1;      // -1: not resolved; 0 never; 1 always (where applicable); 2 auto (N >= 8192)
-int knn_bf16f_mode() {
-  if (g_knn_bf16f < 0) {
-    const char* e = getenv("DGCNN_KNN_BF16F");   // A/B switch: 0 | 1 | auto
-    g_knn_bf16f = e ? ((e[0] == 'a') ? 2 : atoi(e)) : 2;
-  }
-  return g_knn_bf16f;
-}
+int knn_bf16f_mode() { return dg::sw_get(dg::SW_KNN_BF16F); }      // 0 never; 1 always (where applicable); 2 auto (N >= 8192)
 
-int g_knn_valu = 0;            // dgcnn_knn_force_valu (tests): VALU fmaf distances for every C
-bool knn_force_valu() { return g_knn_valu == 1; }
+bool knn_force_valu() { return dg::sw_get(dg::SW_KNN_FORCE_VALU) == 1; }      // dgcnn_knn_force_valu (tests): VALU fmaf distances for every C
 
 // tau0[row] >= max over the row's first k seed candidates j of D(row, j), D in the normative arithmetic of the scan kernels.
 // One wave per query row; LP = C / 4 lanes per pair (lane = LP * slot + channel quad, 64 / LP pairs per step), every pair's
@@ -1269,15 +1261,11 @@ bool launch_seed_bound(const float* x, const float* sq, int64_t rows, Clouds cl,
 }  // namespace
 
 extern "C" int dgcnn_knn_force_valu(int on) {   // A/B switch (tests): 1 = VALU fmaf distances for every C, 0 = MFMA for C > 4
-  const int prev = knn_force_valu() ? 1 : 0;
-  g_knn_valu = on ? 1 : 0;
-  return prev;
+  return dg::sw_exchange(dg::SW_KNN_FORCE_VALU, on ? 1 : 0);
 }
 
 extern "C" int dgcnn_knn_bf16_filter(int mode) {   // A/B switch (tests): 0 never, 1 whenever applicable, 2 auto (N >= 8192); returns the previous mode
-  const int prev = knn_bf16f_mode();
-  g_knn_bf16f = mode;
-  return prev;
+  return dg::sw_exchange(dg::SW_KNN_BF16F, mode < 0 ? dg::sw_initial(dg::SW_KNN_BF16F) : mode);      // (negative: back to what the environment gave)
 }
 
 namespace dg {
@@ -1316,8 +1304,7 @@ static int knn_append_cap(int k, int N) {    // entries per row buffer: >= k + s
 }
 static bool knn_append_shape(int C, int k) { return C > 16 && C <= 64 && C % 4 == 0 && k <= 64; }
 static int knn_append_tighten_mask(bool lx) {
-  static int tight = -1;                     // DGCNN_KNN_TIGHTEN_EVERY (power of two; A/B switch): bound tightening every n-th tile
-  if (tight < 0) { const char* e = getenv("DGCNN_KNN_TIGHTEN_EVERY"); tight = e ? atoi(e) : 0; if (tight < 0 || (tight & (tight - 1))) tight = 1; }
+  const int tight = dg::sw_get(dg::SW_KNN_TIGHTEN_EVERY);      // DGCNN_KNN_TIGHTEN_EVERY (power of two; A/B switch): bound tightening every n-th tile
   // default: every 4th tile below N = 8192, every 8th above (profiles/r06/knn_tight.txt: 175 -> 168 us, 1.83 -> 1.70 ms, 19.2 -> 17.6 ms per call)
   return (tight ? tight : (lx ? 4 : 8)) - 1;
 }
@@ -1325,20 +1312,10 @@ static int knn_append_tighten_mask(bool lx) {
 // Smallest k that the large-k scan of knn_bigk.hip takes (dense and packed, any C): 1 ... 65, default 65 = only the neighbour counts no
 // other kernel has an instance for, so every k <= 64 launches what it always launched.  k > 64 goes there whatever the value.
 // DGCNN_KNN_BIG_K_MIN=<1 ... 65>
-constexpr int KNN_MAX_K = 256, KNN_BIG_ONLY_K = 65;
-static int g_knn_big_k_min = -1;
-static int knn_big_k_min() {
-  if (g_knn_big_k_min < 0) {
-    const char* e = getenv("DGCNN_KNN_BIG_K_MIN");
-    g_knn_big_k_min = e ? atoi(e) : KNN_BIG_ONLY_K;
-    if (g_knn_big_k_min < 1 || g_knn_big_k_min > KNN_BIG_ONLY_K) g_knn_big_k_min = KNN_BIG_ONLY_K;
-  }
-  return g_knn_big_k_min;
-}
+constexpr int KNN_MAX_K = 256, KNN_BIG_ONLY_K = dg::SW_KNN_BIG_ONLY_K;
+static int knn_big_k_min() { return dg::sw_get(dg::SW_KNN_BIG_K_MIN); }
 extern "C" int dgcnn_knn_big_k_min(int k) {             // tools / tests: 1 ... 65; any other value only queries; returns the previous value
-  const int prev = knn_big_k_min();
-  if (k >= 1 && k <= KNN_BIG_ONLY_K) g_knn_big_k_min = k;
-  return prev;
+  return dg::sw_set_or_query(dg::SW_KNN_BIG_K_MIN, k >= 1 && k <= KNN_BIG_ONLY_K, k);
 }
 // the large-k scan takes this k (the VALU switch keeps every k it has an instance for)
 static bool knn_bigk_takes(int k) { return k >= KNN_BIG_ONLY_K || (k >= knn_big_k_min() && !knn_force_valu()); }
@@ -1386,87 +1363,38 @@ static KnnWorkspace knn_ws_seg_mix(void* ws, size_t n, int rows, int n_grid) {  
 // Seeds are used (a) whenever the append-form scan takes the shape (C in {32, 64}: the bound is what makes it possible) and (b) by
 // the list-keeping kernels from N ~ 4096 on: at (24,2048,64,20) the bound kernel (33 us: 252 MB of gathered rows) costs them what
 // the scan saves; at (8,16384,64,40) the step goes 39.0 -> 35.8 ms, at (8,65536,64,20) 101 -> 97 (profiles/r05/knn_seed.txt).
-static int g_knn_seed_min_n = -2;            // -2: not resolved; -1: auto (the rule above); >= 0: explicit
-static int knn_seed_min_n() {
-  if (g_knn_seed_min_n == -2) {
-    const char* e = getenv("DGCNN_KNN_SEED_MIN_N");       // A/B switch
-    g_knn_seed_min_n = e ? atoi(e) : -1;
-  }
-  return g_knn_seed_min_n;
-}
+static int knn_seed_min_n() { return dg::sw_get(dg::SW_KNN_SEED_MIN_N); }      // DGCNN_KNN_SEED_MIN_N (A/B switch); below 0: auto (the rule above)
 extern "C" int dgcnn_knn_seed_min_n(int n) {            // tools / tests: smallest N for which seeds are used (-1: the rule); returns the previous value
-  const int prev = knn_seed_min_n();
-  if (n >= -1) g_knn_seed_min_n = n;
-  return prev;
+  return dg::sw_set_or_query(dg::SW_KNN_SEED_MIN_N, n >= -1, n);
 }
 
-static int g_knn_append = -1;                // DGCNN_KNN_APPEND=0: seeded searches keep per-lane lists (A/B switch)
-static bool knn_append_on() {
-  if (g_knn_append < 0) {
-    const char* e = getenv("DGCNN_KNN_APPEND");
-    g_knn_append = e ? atoi(e) : 1;
-  }
-  return g_knn_append != 0;
-}
+static bool knn_append_on() { return dg::sw_get(dg::SW_KNN_APPEND) != 0; }      // DGCNN_KNN_APPEND=0: seeded searches keep per-lane lists (A/B switch)
 extern "C" int dgcnn_knn_append(int on) {               // tools / tests; returns the previous setting
-  const int prev = knn_append_on() ? 1 : 0;
-  if (on >= 0) g_knn_append = on ? 1 : 0;
-  return prev;
+  return dg::sw_set_or_query(dg::SW_KNN_APPEND, on >= 0, on ? 1 : 0);
 }
 
 // products of the append-form scan's filter per form (LX: N < 8192): 1 since round 6 (profiles/r06/knn_npr.txt: 187 -> 176 us per call
 // at (24,2048,64,20), 2.05 -> 1.82 ms at (8,16384,64,40), 22.3 -> 18.9 ms at (8,65536,64,20)); DGCNN_KNN_APPEND_NPR="<lx>,<big>"
 // (A/B switch; tests run both)
-static int g_knn_npr[2] = {-1, -1};
-static int knn_append_products(bool lx) {
-  if (g_knn_npr[0] < 0) {
-    int a = 1, b = 1;
-    const char* e = getenv("DGCNN_KNN_APPEND_NPR");
-    if (e) sscanf(e, "%d,%d", &a, &b);
-    g_knn_npr[0] = (a == 3) ? 3 : 1;
-    g_knn_npr[1] = (b == 3) ? 3 : 1;
-  }
-  return g_knn_npr[lx ? 0 : 1];
-}
+static int knn_append_products(bool lx) { return dg::sw_get(lx ? dg::SW_KNN_APPEND_NPR_LX : dg::SW_KNN_APPEND_NPR_BIG); }
 extern "C" int dgcnn_knn_append_products(int n) {       // tools / tests: 1 or 3 for both forms (other values: query only); returns the previous setting of the N < 8192 form
-  const int prev = knn_append_products(true);
-  if (n == 1 || n == 3) g_knn_npr[0] = g_knn_npr[1] = n;
-  return prev;
+  dg::sw_set_or_query(dg::SW_KNN_APPEND_NPR_BIG, n == 1 || n == 3, n);
+  return dg::sw_set_or_query(dg::SW_KNN_APPEND_NPR_LX, n == 1 || n == 3, n);
 }
 
 // raw-coordinate layer (C <= 4): sample stride of the histogram bound (knn_hist_bound_kernel); 0 = no bound.  DGCNN_KNN_HIST=<0|1|2|4>
-static int g_knn_hist = -1;
-static int knn_hist_stride(int N) {
-  if (g_knn_hist < 0) {
-    const char* e = getenv("DGCNN_KNN_HIST");
-    g_knn_hist = e ? atoi(e) : 2;
-    if (g_knn_hist != 0 && g_knn_hist != 1 && g_knn_hist != 2 && g_knn_hist != 4) g_knn_hist = 2;
-  }
-  return N >= 256 ? g_knn_hist : 0;
-}
+static int knn_hist_stride(int N) { return N >= 256 ? dg::sw_get(dg::SW_KNN_HIST) : 0; }
 extern "C" int dgcnn_knn_hist(int stride) {              // tools / tests: 0 off, 1 / 2 / 4 = sample stride; other values only query; returns the previous setting
-  const int prev = knn_hist_stride(1 << 20);
-  if (stride == 0 || stride == 1 || stride == 2 || stride == 4) g_knn_hist = stride;
-  return prev;
+  return dg::sw_set_or_query(dg::SW_KNN_HIST, dg::sw_valid(dg::SW_KNN_HIST, stride), stride);
 }
 
 // Smallest C that the channel-slab scan of knn_wide.hip takes (dense and packed, any k <= 64): 5 ... 129, default 129 = only the widths
 // no other kernel has an instance for, so every narrower shape launches what it always launched.  C > 128 goes there whatever the
 // value.  DGCNN_KNN_WIDE_MIN_C=<5 ... 129>
-constexpr int KNN_MAX_C = 1024, KNN_WIDE_ONLY_C = 129;
-static int g_knn_wide_min_c = -1;
-static int knn_wide_min_c() {
-  if (g_knn_wide_min_c < 0) {
-    const char* e = getenv("DGCNN_KNN_WIDE_MIN_C");
-    g_knn_wide_min_c = e ? atoi(e) : KNN_WIDE_ONLY_C;
-    if (g_knn_wide_min_c < 5 || g_knn_wide_min_c > KNN_WIDE_ONLY_C) g_knn_wide_min_c = KNN_WIDE_ONLY_C;
-  }
-  return g_knn_wide_min_c;
-}
+constexpr int KNN_MAX_C = 1024, KNN_WIDE_ONLY_C = dg::SW_KNN_WIDE_ONLY_C;
+static int knn_wide_min_c() { return dg::sw_get(dg::SW_KNN_WIDE_MIN_C); }
 extern "C" int dgcnn_knn_wide_min_c(int c) {            // tools / tests: 5 ... 129; any other value only queries; returns the previous value
-  const int prev = knn_wide_min_c();
-  if (c >= 5 && c <= KNN_WIDE_ONLY_C) g_knn_wide_min_c = c;
-  return prev;
+  return dg::sw_set_or_query(dg::SW_KNN_WIDE_MIN_C, c >= 5 && c <= KNN_WIDE_ONLY_C, c);
 }
 // the channel-slab scan takes this width (the VALU switch keeps every width it has an instance for)
 static bool knn_wide_takes(int C) { return C >= KNN_WIDE_ONLY_C || (C >= knn_wide_min_c() && !knn_force_valu()); }
@@ -1600,7 +1528,7 @@ bool knn_append_usable(const KnnCall& a) {
 // The two seeding rules.  Both need kseed >= k seeds per row and 32-bit element offsets within a cloud; dgcnn_knn_seed_min_n overrides
 // the cloud size from which either applies.
 // Dense: seeds are used by the list-keeping and matrix-pipe scans (4 < C <= 64, float4-loadable rows) from N >= 4096 without the append
-// form, and from any N with it (the measurements: at g_knn_seed_min_n).
+// form, and from any N with it (the measurements: at DGCNN_KNN_SEED_MIN_N).
 bool knn_seeds_used_dense(const KnnCall& a, const int32_t* seed, int kseed, int N, bool append) {
   const int min_n = knn_seed_min_n() >= 0 ? knn_seed_min_n() : (append ? 0 : 4096);
   return seed && kseed >= a.k && kseed <= 64 && a.C > 4 && a.C <= 64 && a.C % 4 == 0 && a.vec_ok && !knn_force_valu() && N >= min_n &&

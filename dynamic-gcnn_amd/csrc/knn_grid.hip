@@ -26,7 +26,6 @@
 // Work per query at uniform density: the grid is sized for ~0.8 k points per cell, so ring 1 (27 cells, ~22 k candidates) decides
 // almost every query: 432 pair evaluations instead of 2048 at (24, 2048, 3, 20), 864 instead of 16384 / 65536 at k = 40.
 #include "knn_common.h"
-#include <limits.h>
 #include <stdlib.h>
 
 namespace {
@@ -401,15 +400,9 @@ __global__ __launch_bounds__(64 * QW) void knn_grid_query_kernel(const float4* _
   }
 }
 
-bool g_knn_grid_all = false;
-int g_knn_grid = -1;
-bool knn_grid_on() {
-  if (g_knn_grid < 0) {
-    const char* e = getenv("DGCNN_KNN_GRID");      // A/B switch: 0 = brute-force kernel for C <= 4 as well
-    g_knn_grid = (e && e[0] == '0') ? 0 : 1;
-  }
-  return g_knn_grid == 1;
-}
+// DGCNN_KNN_GRID / dgcnn_knn_grid: 0 = brute-force kernel for C <= 4 as well, 1 = where it pays, 2 = whenever applicable
+bool knn_grid_on() { return dg::sw_get(dg::SW_KNN_GRID) != 0; }
+bool knn_grid_all() { return dg::sw_get(dg::SW_KNN_GRID) == 2; }
 
 // Both towers share one layout: [records float4 rows][s_j float rows][order int rows] | 64-byte aligned: [GridInfo B][cell table B];
 // a packed tower's cloud b owns the tower rows [off[b], off[b + 1]) of the three row arrays.
@@ -491,16 +484,11 @@ bool knn_grid_applicable(int C, int k) { return knn_grid_on() && C <= 4 && k <= 
 // Measured cross-over between N = 2048 (all pairs 155 us, grid 207 us at B = 24: one 64-query wave per SIMD, bound by its own
 // dependent instruction chain) and N = 4096; at N = 16384 / 65536 the grid is 3.1x / 14x faster.  $DGCNN_KNN_GRID_MIN_N moves it
 // (tests run the grid at every N).
-static int grid_min_env() {              // $DGCNN_KNN_GRID_MIN_N, or INT_MIN when it is not set
-  static int v = 0;
-  static bool read = false;
-  if (!read) { const char* e = getenv("DGCNN_KNN_GRID_MIN_N"); v = e ? atoi(e) : INT_MIN; read = true; }
-  return v;
+static int grid_min_or(int def) {        // 0 in mode 2, else $DGCNN_KNN_GRID_MIN_N, or `def` when it is not set
+  const int e = sw_get(SW_KNN_GRID_MIN_N);
+  return knn_grid_all() ? 0 : (e == SW_UNSET ? def : e);
 }
-int knn_grid_min_n() {
-  const int e = grid_min_env();
-  return g_knn_grid_all ? 0 : (e == INT_MIN ? 4096 : e);
-}
+int knn_grid_min_n() { return grid_min_or(4096); }
 // Packed towers: the smallest row-weighted mean cloud size (sum n_b^2 / rows = candidates per row of the all-pairs scan) from which
 // the grid is used.  Higher than the dense N: a packed tower never takes the LDS-copy form and its all-pairs scan is ONE launch with
 // the histogram bound.  Measured (profiles/packed/grid_bench.txt, grid_sweep.txt; C = 4, k = 20 / 40): the grid LOSES at k = 40 on 24
@@ -509,10 +497,7 @@ int knn_grid_min_n() {
 // 18.2 k: 1.5x / 1.08x).  The lopsided towers set the constant: between their losing and winning mean, at the k = 40 end.
 // $DGCNN_KNN_GRID_MIN_N overrides this value too.
 constexpr int GRID_SEG_MIN_MEAN = 16384;
-int knn_grid_seg_min_mean() {
-  const int e = grid_min_env();
-  return g_knn_grid_all ? 0 : (e == INT_MIN ? GRID_SEG_MIN_MEAN : e);
-}
+int knn_grid_seg_min_mean() { return grid_min_or(GRID_SEG_MIN_MEAN); }
 
 int launch_knn_grid(const float* x, const float* sq, int B, int N, int C, int64_t ldx, int k, int32_t* idx, void* ws, hipStream_t st) {
   return launch_grid("dgcnn_knn_f32 (grid)", x, sq, DenseClouds(N), B, N, (size_t)B * (size_t)N, C, ldx, k, idx, ws, st);
@@ -545,27 +530,13 @@ extern "C" int dgcnn_knn_seg_grid_use(int C, int k, int nseg, int rows, int min_
 
 // 0 = never, 1 = where it pays (N >= knn_grid_min_n), 2 = whenever applicable (tests)
 extern "C" int dgcnn_knn_grid(int mode) {
-  const int prev = knn_grid_on() ? (g_knn_grid_all ? 2 : 1) : 0;
-  g_knn_grid = mode ? 1 : 0;
-  g_knn_grid_all = mode == 2;
-  return prev;
+  return dg::sw_exchange(dg::SW_KNN_GRID, mode == 2 ? 2 : (mode ? 1 : 0));
 }
 
 // Packed towers, mode 1: the per-cloud size from which a cloud goes to the cell grid while the smaller clouds of the same tower keep
 // the all-pairs scan (dgcnn_knn_seg_mix_f32; dgcnn/_engine.py:knn_packed splits the tower).  0 = no split: the whole tower follows
-// dgcnn_knn_seg_grid_use.  $DGCNN_KNN_MIX_MIN_N is read once, at the first call.
+// dgcnn_knn_seg_grid_use.  ($DGCNN_KNN_MIX_MIN_N; n < 0 only queries; returns the previous value)
 // The default is 0 by measurement (profiles/packed/mix_bench.txt; T = 4096 ... 16384, C = 4, k = 20 / 40): the two sub-searches run one
 // after the other on one stream and neither fills the GPU, so the mix costs about their sum -- one 16384 / 32768 / 65536-point cloud
 // among 23 small ones 0.80x / 0.83x / 0.88x of what the mean rule picks at k = 20 (0.63x / 0.99x / 0.98x at k = 40) at every T.
-constexpr int GRID_SEG_MIX_MIN_N = 0;
-extern "C" int dgcnn_knn_seg_mix_min_n(int n) {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("DGCNN_KNN_MIX_MIN_N");
-    v = e ? atoi(e) : GRID_SEG_MIX_MIN_N;
-    if (v < 0) v = 0;
-  }
-  const int prev = v;
-  if (n >= 0) v = n;
-  return prev;
-}
+extern "C" int dgcnn_knn_seg_mix_min_n(int n) { return dg::sw_set_or_query(dg::SW_KNN_MIX_MIN_N, n >= 0, n); }

@@ -65,14 +65,8 @@ int g_ring_n = 0, g_ring_i = 0;
 // Events of cross-stream waits order kernels of ONE device and are never looked at by the host (or by another device: RCCL's kernels
 // fence their own transfers), so the system-scope fence of a record is skipped: 4.45 -> 4.43 ms per step at configs[1] with 15 waits
 // (hipEventReleaseToDevice: no difference).  DGCNN_EVENT_FLAGS overrides (A/B switch).
-unsigned event_flags() {
-  static long f = -1;
-  if (f < 0) {
-    const char* e = getenv("DGCNN_EVENT_FLAGS");
-    f = e ? (long)strtoul(e, nullptr, 0) : (long)(hipEventDisableTiming | hipEventDisableSystemFence);
-  }
-  return (unsigned)f;
-}
+static_assert((hipEventDisableTiming | hipEventDisableSystemFence) == 0x20000002, "switches.cc: the default of DGCNN_EVENT_FLAGS");
+unsigned event_flags() { return (unsigned)dg::sw_get(dg::SW_EVENT_FLAGS); }
 
 hipEvent_t ring_event() {
   if (g_ring_n < EVRING) {

@@ -168,8 +168,9 @@ class Context(object):
 
     def stats(self, F):
         """Zeroed double[SLOTS][2][F] carved from one arena that is memset once per step."""
-        n = H.STAT_SLOTS * 2 * F
-        want = self.arena_want()
+        slots = H.stat_slots()
+        n = slots * 2 * F
+        want = self.arena_want(slots)
         if self.stat_arena is None or self.stat_arena.device != self.device or self.stat_arena.numel() < want:
             # a captured HIP graph has the arena's address (and the slot count) baked into its launches: trainval keys its
             # graphs on arena_key() and drops those recorded against an arena that no longer exists
@@ -182,16 +183,17 @@ class Context(object):
         self.stat_off += n
         return s
 
-    def arena_want(self):
+    def arena_want(self, slots=None):
         """Doubles of the statistics arena a step may use at its slot count: 8 MB at 32 slots, 96 MB at 768.  The arena itself may
-        be larger (an earlier, larger cloud grew it): a step carves from -- and a captured step zeroes -- at most this much."""
-        n = max(self.step_slots, H.STAT_SLOTS)
+        be larger (an earlier, larger cloud grew it): a step carves from -- and a captured step zeroes -- at most this much.
+        slots: the calling thread's count where the caller has just read it."""
+        n = max(self.step_slots, H.stat_slots() if slots is None else slots)
         return (1 << 20) if n <= 32 else (1 << 19) * -(-n // 32)
 
     def arena_key(self):
         """What a captured step depends on besides its inputs: the statistics arena it zeroes / writes and the slot count its
         launches carry as arguments."""
-        return (self.arena_gen, H.STAT_SLOTS, 0 if self.stat_arena is None else self.stat_arena.data_ptr())
+        return (self.arena_gen, H.stat_slots(), 0 if self.stat_arena is None else self.stat_arena.data_ptr())
 
     def ensure_arena(self, rows):
         """Slot count and arena for a step over `rows` points, settled OUTSIDE a capture (so that the capture neither allocates
@@ -214,20 +216,21 @@ class Context(object):
         else:
             n = 32
         self.step_slots = n
-        if n != H.STAT_SLOTS:
+        if n != H.stat_slots():
             H.set_stat_slots(n)
 
     def push_slots(self, writers=0):
         """op_slots() as a pair of calls (the producer and its finalize sit far apart in the block functions)."""
-        self._slot_stack.append(H.STAT_SLOTS)
+        prev = H.stat_slots()
+        self._slot_stack.append(prev)
         if DETERMINISTIC:
             n = max(256, -(-int(writers) // 64) * 64)
-            if n != H.STAT_SLOTS:
+            if n != prev:
                 H.set_stat_slots(n)
 
     def pop_slots(self):
         prev = self._slot_stack.pop()
-        if H.STAT_SLOTS != prev:
+        if H.stat_slots() != prev:
             H.set_stat_slots(prev)
 
     @contextlib.contextmanager
@@ -316,9 +319,10 @@ class Context(object):
         self.wprep_event = None
         self._slot_stack = []
         self.class_tail = self.loss_tail = None
-        if not DETERMINISTIC and H.STAT_SLOTS != 32:
+        slots = H.stat_slots()
+        if not DETERMINISTIC and slots != 32:
             H.set_stat_slots(32)
-        elif DETERMINISTIC and H.STAT_SLOTS < 256:
+        elif DETERMINISTIC and slots < 256:
             self.configure_slots(0)           # (stand-alone ops; a model step sets its own count in model.build)
         if self.stat_arena is not None:
             if self.capturing:
@@ -466,7 +470,7 @@ def reset():
     """Forget all variables / state (tf.reset_default_graph analogue)."""
     global _CTX
     _CTX = Context()
-    if H.STAT_SLOTS != 32:
+    if H.stat_slots() != 32:
         H.set_stat_slots(32)                 # (the first step picks the count of its mode and shape)
     return _CTX
 
@@ -612,13 +616,9 @@ def knn(x2d, B, N, k, seed=None, seg=None):
 
 
 def _knn_switches():
-    """The k-NN switches of the library as they stand, each through its own setter's query form (include/dgcnn_hip.h).  The VALU and
-    bf16-filter setters have none: they are set to a value and put back."""
-    lib = H.load()
-    bf16f = int(lib.dgcnn_knn_bf16_filter(2))
-    lib.dgcnn_knn_bf16_filter(bf16f)
-    return dict(valu=_knn_valu(), bf16f=bf16f, append=bool(lib.dgcnn_knn_append(-1)), seed_min_n=int(lib.dgcnn_knn_seed_min_n(-2)),
-                hist=int(lib.dgcnn_knn_hist(-1)))
+    """The k-NN switches of the library as they stand (include/dgcnn_hip.h lists them); reading changes none."""
+    return dict(valu=_knn_valu(), bf16f=H.switch("DGCNN_KNN_BF16F"), append=bool(H.switch("DGCNN_KNN_APPEND")),
+                seed_min_n=H.switch("DGCNN_KNN_SEED_MIN_N"), hist=H.switch("DGCNN_KNN_HIST"))
 
 
 def _knn_call_kernels(x2d, C, k, min_n, max_n, kseed, dense):
@@ -627,10 +627,10 @@ def _knn_call_kernels(x2d, C, k, min_n, max_n, kseed, dense):
     kseed: the seeds per row the call passes (0: none).  dense: B clouds of min_n = max_n points; else a packed tower.
     tests/test_gpu_knn_dispatch.py holds every tag against the launches recorded from the same call.
     This restates knn.hip:knn_impl / knn_scan / launch_scan because the library has no host query that answers "which kernels would
-    this call launch": its queries give the workspace size, the packed grid rule (dgcnn_knn_seg_grid_use) and each switch, and
-    those are what is asked here; the rest of the rule needs the call's pointer, leading dimension and seed, which only the entry
-    sees.  The dense cell grid's smallest N (4096; $DGCNN_KNN_GRID_MIN_N moves it inside the library) has no query either.  The
-    names come from here only while a timer is set, never on the training path."""
+    this call launch": its queries give the workspace size, the packed grid rule (dgcnn_knn_seg_grid_use) and each switch
+    (dgcnn_switch_get: reading changes nothing), and those are what is asked here; the rest of the rule needs the call's pointer,
+    leading dimension and seed, which only the entry sees.  The dense cell grid's smallest N is the switch DGCNN_KNN_GRID_MIN_N
+    (unset: 4096; knn_grid.hip:knn_grid_min_n).  The names come from here only while a timer is set, never on the training path."""
     sw = _knn_switches()
     valu = sw["valu"]
     vec_ok = H.ld2(x2d) % 4 == 0 and x2d.data_ptr() % 16 == 0                  # knn.hip:knn_vec_ok
@@ -642,7 +642,8 @@ def _knn_call_kernels(x2d, C, k, min_n, max_n, kseed, dense):
     if dense:                                                                   # knn_seeds_used_dense / knn_seeds_used_packed
         seed_min = sw["seed_min_n"] if sw["seed_min_n"] >= 0 else (0 if append else 4096)
         seeded = k <= kseed <= 64 and 4 < C <= 64 and C % 4 == 0 and vec_ok and not valu and min_n >= seed_min and in_range
-        if _knn_grid_mode(H.load(), C, k) == 2 or (_knn_grid_mode(H.load(), C, k) == 1 and max_n >= 4096):
+        grid, grid_min_n = _knn_grid_mode(C, k), H.switch("DGCNN_KNN_GRID_MIN_N")
+        if grid == 2 or (grid == 1 and max_n >= (4096 if grid_min_n == H.SWITCH_UNSET else grid_min_n)):
             if not valu:
                 return names + ["knn_grid_*"]
     else:
@@ -665,17 +666,14 @@ def _knn_call_kernels(x2d, C, k, min_n, max_n, kseed, dense):
 
 
 def _knn_valu():
-    """dgcnn_knn_force_valu as it stands (the setter has no query form: it is set to 0 and put back; the host is single threaded)"""
-    lib = H.load()
-    valu = int(lib.dgcnn_knn_force_valu(0))
-    lib.dgcnn_knn_force_valu(valu)
-    return bool(valu)
+    """dgcnn_knn_force_valu as it stands"""
+    return bool(H.switch("DGCNN_KNN_FORCE_VALU"))
 
 
 def _knn_big(k):
     """the library gives this k to the large-k scan (knn_bigk.hip; knn.hip:knn_bigk_takes): k > 64 always, smaller k from
     dgcnn_knn_big_k_min on unless the VALU scan is forced"""
-    return k >= 65 or (k >= int(H.load().dgcnn_knn_big_k_min(-1)) and not _knn_valu())
+    return k >= 65 or (k >= H.switch("DGCNN_KNN_BIG_K_MIN") and not _knn_valu())
 
 
 def _sqnorm_name(C):
@@ -685,7 +683,7 @@ def _sqnorm_name(C):
 def _knn_wide(C):
     """the library gives this width to the channel-slab scan (knn_wide.hip; knn.hip:knn_wide_takes): C > 128 always, narrower rows
     from dgcnn_knn_wide_min_c on unless the VALU scan is forced"""
-    return C >= 129 or (C >= int(H.load().dgcnn_knn_wide_min_c(-1)) and not _knn_valu())
+    return C >= 129 or (C >= H.switch("DGCNN_KNN_WIDE_MIN_C") and not _knn_valu())
 
 
 def _knn_instance(C, k):
@@ -712,12 +710,10 @@ def _knn_seed_ok(seed, B, N, k):
             and seed.dtype == torch.int32 and seed.is_contiguous())
 
 
-def _knn_grid_mode(lib, C, k):
-    """dgcnn_knn_grid's mode for this shape, as dgcnn_knn_seg_grid_use answers for a one-point tower: 0 = never (switched off, or C > 4
-    or k > 40), 2 = whenever applicable (its threshold on the mean cloud size is 0), 1 = where the library's rule says it pays."""
-    if not lib.dgcnn_knn_seg_grid_use(C, k, 1, 1, 1, 1, 1 << 62):
-        return 0
-    return 2 if lib.dgcnn_knn_seg_grid_use(C, k, 1, 1, 1, 1, 0) else 1
+def _knn_grid_mode(C, k):
+    """dgcnn_knn_grid's mode for this shape (knn_grid.hip:knn_grid_applicable): 0 = never (switched off, or C > 4 or k > 40),
+    2 = whenever applicable, 1 = where the library's rule says it pays."""
+    return H.switch("DGCNN_KNN_GRID") if C <= 4 and k <= 40 else 0
 
 
 def knn_packed(x2d, k, seg, seed=None):
@@ -734,7 +730,7 @@ def knn_packed(x2d, k, seg, seed=None):
     # with a per-cloud threshold T > 0: the clouds of at least T points through the grid, the others through the scan, in one call
     lib = H.load()
     big = _knn_big(k)                        # the large-k scan: dgcnn_knn_seg_f32 whatever the width
-    T = int(lib.dgcnn_knn_seg_mix_min_n(-1)) if C <= 4 and not big and _knn_grid_mode(lib, C, k) == 1 else 0
+    T = H.switch("DGCNN_KNN_MIX_MIN_N") if C <= 4 and not big and _knn_grid_mode(C, k) == 1 else 0
     if T > 0:
         lst, n_grid, grid_max, scan_min, scan_max = seg.mix(T, x2d.device)
         use_grid = n_grid == seg.nseg
@@ -1041,13 +1037,13 @@ def _launch_bn1_act_dropout(h):
 
 def _launch_loss_tail(lt):
     """The Final layer's BatchNorm finalize + activation on their own (lt: the record conv_bn_act holds them back in)."""
-    prev = H.STAT_SLOTS
+    prev = H.stat_slots()
     if lt["nslots"] != prev:
         H.set_stat_slots(lt["nslots"])
     try:
         H.call("dgcnn_bn_finalize_f32", lt["st"].data_ptr(), lt["F"], float(lt["R"]), BN_EPS, lt["mean"].data_ptr(), lt["rstd"].data_ptr())
     finally:
-        if H.STAT_SLOTS != prev:
+        if lt["nslots"] != prev:
             H.set_stat_slots(prev)
     H.call("dgcnn_bn_act_kreduce_f32", lt["T"].data_ptr(), lt["R"], 1, lt["F"], lt["mean"].data_ptr(), lt["rstd"].data_ptr(),
            lt["beta"].data_ptr(), int(lt["relu"]), lt["out"].data_ptr(), H.ld2(lt["out"]), 0, 0, 0, 0, 0,
@@ -1244,7 +1240,7 @@ def _conv_tail_class(c, L, tail, st):
     if L.out is None:
         L.out = c.new_buffer(R, F)
     c.loss_tail = dict(T=T, st=st, F=F, R=R, beta=L.beta, relu=L.relu, mean=L.mean, rstd=L.rstd, out=L.out, scal=scal,
-                       nslots=H.STAT_SLOTS)
+                       nslots=H.stat_slots())
     c.pop_slots()
     if c.recording:
         _record(c, _conv_plain_bwd, L, tail)
@@ -2220,7 +2216,7 @@ def softmax_loss(logits2d, labels, weight, want_grad, seg=None, per_cloud=False)
     if lt is not None:
         # F2: folds the Final layer's statistics slots (mean / rstd for the backward), applies its BatchNorm + ReLU -> logits2d,
         # then softmax / seed / loss / accuracy as below; [loss, accuracy] were zeroed by F1
-        prev = H.STAT_SLOTS
+        prev = H.stat_slots()
         if lt["nslots"] != prev:
             H.set_stat_slots(lt["nslots"])
         try:
@@ -2228,7 +2224,7 @@ def softmax_loss(logits2d, labels, weight, want_grad, seg=None, per_cloud=False)
                    int(lt["relu"]), R, ncls, lt["mean"].data_ptr(), lt["rstd"].data_ptr(), logits2d.data_ptr(), H._p(labels),
                    H._p(weight), sm.data_ptr(), H._p(dl), lt["scal"].data_ptr(), tag="bn_softmax_xent_kernel", work=4.0 * R * ncls * 4)
         finally:
-            if H.STAT_SLOTS != prev:
+            if lt["nslots"] != prev:
                 H.set_stat_slots(prev)
         return sm, lt["scal"]
     scal = H.zeros(2, torch.float32, dev)      # (its own tensor: the caller reads it after later towers' begin_step)

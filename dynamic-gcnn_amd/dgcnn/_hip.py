@@ -14,7 +14,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DGCNN_HIP_LIB") or os.path.join(_HERE, "libdgcnn_hip.so")   # env override: experiments
-STAT_SLOTS = 32
+SWITCH_UNSET = -2 ** 31                      # DGCNN_SWITCH_UNSET: DGCNN_KNN_GRID_MIN_N was not given
 
 c_int, c_i64, c_f32, c_f64, c_vp, c_sz, c_u64 = (ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double,
                                                   ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64)
@@ -86,6 +86,8 @@ PROTOTYPES = {
                                 c_vp, c_vp, c_f32, c_vp, c_i64, c_vp, c_vp, c_vp, c_f32, c_int, c_vp],
     "dgcnn_set_stat_slots": [c_int],
     "dgcnn_get_stat_slots": [],
+    "dgcnn_switch_get": [ctypes.c_char_p, c_vp],
+    "dgcnn_switch_set": [ctypes.c_char_p, c_int],
     "dgcnn_gemm_set_arith": [c_int],
     "dgcnn_gemm_get_arith": [],
     "dgcnn_gemm_stat_writers": [c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp, c_i64],
@@ -226,12 +228,38 @@ def set_gemm_arith(mode):
 
 
 def set_stat_slots(n):
-    """Slots of every stats / red buffer from now on (include/dgcnn_hip.h: dgcnn_set_stat_slots); mirrored in STAT_SLOTS."""
-    global STAT_SLOTS
+    """Slots of every stats / red buffer the calling thread prepares from now on (include/dgcnn_hip.h: dgcnn_set_stat_slots)."""
     lib = load()
     if lib.dgcnn_set_stat_slots(int(n)) != 0:
         raise ValueError(lib.dgcnn_last_error().decode())
-    STAT_SLOTS = int(n)
+
+
+def stat_slots():
+    """The calling thread's slot count, from the library (it is thread-local there: no copy is kept here)."""
+    return (_lib or load()).dgcnn_get_stat_slots()
+
+
+def __getattr__(name):
+    """`_hip.STAT_SLOTS`, the earlier spelling of stat_slots(): no stored value, evaluated at every access for the calling thread."""
+    if name == "STAT_SLOTS":
+        return stat_slots()
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
+
+
+def switch(name):
+    """A process-wide switch of the library as it stands (include/dgcnn_hip.h lists the names); reading changes nothing."""
+    lib = load()
+    v = c_int(0)
+    if lib.dgcnn_switch_get(name.encode(), ctypes.byref(v)) != 0:
+        raise ValueError(lib.dgcnn_last_error().decode())
+    return int(v.value)
+
+
+def set_switch(name, v):
+    """Set a process-wide switch; ValueError for an unknown name or a value the switch's environment parse would have replaced."""
+    lib = load()
+    if lib.dgcnn_switch_set(name.encode(), int(v)) != 0:
+        raise ValueError(lib.dgcnn_last_error().decode())
 
 
 def gemm_arith():

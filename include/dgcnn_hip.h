@@ -44,6 +44,36 @@ extern "C" {
 int dgcnn_set_stat_slots(int n);
 int dgcnn_get_stat_slots(void);
 
+/* ---- process-wide switches (csrc/switches.cc): A/B and test switches of the dispatch rules, one table.  Where a row has an
+ * environment variable of its own name it is read ONCE, when the table is first touched; afterwards only the calls below and the
+ * switch's own setter (documented with the kernels it steers) change a value.  Unlike the slot count above they are shared by all
+ * threads; values are atomic ints, so any thread may read or set at any time (a call in flight sees the old or the new value).
+ *   DGCNN_KNN_BF16F            0 | 1 | 2 (env: "auto" = 2)            dgcnn_knn_bf16_filter
+ *   DGCNN_KNN_FORCE_VALU       0 | 1 (no env)                         dgcnn_knn_force_valu
+ *   DGCNN_KNN_TIGHTEN_EVERY    0 (per-form default: 4 / 8) or a power of two: the append-form scan tightens its bound every n-th tile
+ *   DGCNN_KNN_BIG_K_MIN        1 ... 65                               dgcnn_knn_big_k_min
+ *   DGCNN_KNN_SEED_MIN_N       -1 (the rule) or a cloud size          dgcnn_knn_seed_min_n
+ *   DGCNN_KNN_APPEND           0 | 1                                  dgcnn_knn_append
+ *   DGCNN_KNN_APPEND_NPR_LX    1 | 3, the N < 8192 form               dgcnn_knn_append_products (env DGCNN_KNN_APPEND_NPR="<lx>,<big>")
+ *   DGCNN_KNN_APPEND_NPR_BIG   1 | 3, the N >= 8192 form              (the same setter and variable)
+ *   DGCNN_KNN_HIST             0 | 1 | 2 | 4                          dgcnn_knn_hist
+ *   DGCNN_KNN_WIDE_MIN_C       5 ... 129                              dgcnn_knn_wide_min_c
+ *   DGCNN_KNN_GRID             0 | 1 | 2 (env: only a leading 0 = 0)  dgcnn_knn_grid
+ *   DGCNN_KNN_GRID_MIN_N       DGCNN_SWITCH_UNSET or a size: the dense cell grid's smallest N (unset: 4096) and the packed towers'
+ *                              smallest mean cloud size (unset: 16384)
+ *   DGCNN_KNN_MIX_MIN_N        >= 0                                   dgcnn_knn_seg_mix_min_n
+ *   DGCNN_EDGE_VALU            0 | 1 (env: only a leading 0 = 0)      dgcnn_edge_valu
+ *   DGCNN_GEMM_ARITH           0 | 1 | 6 | 9 (env: f32 | bf16x1 ...)  dgcnn_gemm_set_arith / dgcnn_gemm_get_arith
+ *   DGCNN_GEMM_X3_TILE         0 | 128 | 256 | 448 | 512 (no env)     dgcnn_gemm_x3_tile_override
+ *   DGCNN_EVENT_FLAGS          hipEventCreateWithFlags flags (as the int of the same bits) of the cross-stream wait events; a new
+ *                              value only affects events created afterwards (the eager ring of 16 and the waits of plans recorded later)
+ * dgcnn_switch_get: *value = the value in force; nothing is changed.  dgcnn_switch_set: the validation of the row's environment
+ * parse -- a value the parse would have replaced (BIG_K_MIN = 99 reads as 65 from the environment) is refused, not replaced.  Both:
+ * DGCNN_EINVAL for an unknown name (dgcnn_last_error lists the known ones). */
+#define DGCNN_SWITCH_UNSET (-2147483647 - 1)
+int dgcnn_switch_get(const char* name, int* value);
+int dgcnn_switch_set(const char* name, int value);
+
 int dgcnn_version(void);
 const char* dgcnn_last_error(void);
 

@@ -34,7 +34,7 @@ for C, F in [(3, 64), (64, 64), (64, 128)]:
     x = torch.from_numpy(np.maximum(rng.normal(size=(R, C)), 0).astype(np.float32) if C > 4 else rng.random((R, C), dtype=np.float32)).cuda()
     W0 = torch.from_numpy(rng.normal(0, 0.2, (2 * C, F)).astype(np.float32)).cuda()
     idx = E.knn(x, B, N, k)
-    st = torch.zeros(H.STAT_SLOTS * 2 * F, dtype=torch.float64, device="cuda")
+    st = torch.zeros(H.stat_slots() * 2 * F, dtype=torch.float64, device="cuda")
     Y = torch.empty((R * k, F), device="cuda")
 
     def literal():

@@ -30,7 +30,7 @@ for name, N, K, c0, F in (("FC0 dgrad (1728 <- 512), MergedEdgeConv sums", 1728,
     dX = torch.empty(R, N, device="cuda")
     T = torch.randn(R, F, device="cuda")
     mean, rstd, beta = torch.zeros(F, device="cuda"), torch.ones(F, device="cuda"), torch.zeros(F, device="cuda")
-    red = torch.zeros(E.H.STAT_SLOTS * 2 * F, dtype=torch.float64, device="cuda")
+    red = torch.zeros(E.H.stat_slots() * 2 * F, dtype=torch.float64, device="cuda")
     t0 = timeit(lambda: E.gemm(dT, W, dX, transB=True))
     t1 = timeit(lambda: E.H.call("dgcnn_gemm_bn_bwd_f32", R, N, K, dT.data_ptr(), K, W.data_ptr(), K, dX.data_ptr(), N, 0.0, T.data_ptr(), F,
                                  mean.data_ptr(), rstd.data_ptr(), beta.data_ptr(), 1, c0, F, red.data_ptr()))

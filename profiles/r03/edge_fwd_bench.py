@@ -28,7 +28,7 @@ def timeit(fn, n=40, warm=5):
 for F in (64, 128):
     UV = torch.randn(R, 2 * F, device="cuda")
     idx = torch.randint(0, N, (B, N, k), device="cuda", dtype=torch.int32)
-    st = torch.zeros(H.STAT_SLOTS * 2 * F, dtype=torch.float64, device="cuda")
+    st = torch.zeros(H.stat_slots() * 2 * F, dtype=torch.float64, device="cuda")
     mean, rstd, beta = torch.zeros(F, device="cuda"), torch.ones(F, device="cuda"), torch.zeros(F, device="cuda")
     mm = torch.empty(R, 2 * F, device="cuda")
     cnt = torch.empty(R, F, device="cuda")

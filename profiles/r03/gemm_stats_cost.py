@@ -27,7 +27,7 @@ for name, Cin, Cout in (("FC0 1728->512", 1728, 512), ("Merged 192->1024", 192, 
     X = torch.randn(R, Cin, device="cuda").relu_()
     W = torch.randn(Cin, Cout, device="cuda") * 0.05
     Y = torch.empty(R, Cout, device="cuda")
-    st = torch.zeros(H.STAT_SLOTS * 2 * Cout, dtype=torch.float64, device="cuda")
+    st = torch.zeros(H.stat_slots() * 2 * Cout, dtype=torch.float64, device="cuda")
     t0 = timeit(lambda: E.gemm(X, W, Y))
     t1 = timeit(lambda: E.gemm(X, W, Y, stats=st))
     print("%-18s plain %7.1f us | with BatchNorm column sums %7.1f us (+%.0f %%)" % (name, t0 * 1e6, t1 * 1e6, 100 * (t1 - t0) / t0))

@@ -30,6 +30,6 @@ for F in (64, 128):
     print("F=%d random idx  max only                             %6.1f us" % (F, run(idx, V, U, 2 * F, mm, 2 * F, None, 0, None)))
     print("F=%d random idx  dense V/U (ld = F), dense outputs     %6.1f us" % (F, run(idx, Vd, Ud, F, mxd, F, mnd, F, cnt)))
     print("F=%d local idx   all outputs                          %6.1f us" % (F, run(idx_local, V, U, 2 * F, mm, 2 * F, mm[:, F:], 2 * F, cnt)))
-    st = torch.zeros(H.STAT_SLOTS * 2 * F, dtype=torch.float64, device="cuda")
+    st = torch.zeros(H.stat_slots() * 2 * F, dtype=torch.float64, device="cuda")
     t0 = timeit(lambda: H.call("dgcnn_edge_gather_add_f32", V.data_ptr(), 2 * F, U.data_ptr(), 2 * F, idx_local.data_ptr(), B, N, k, F, 0, st.data_ptr()))
     print("F=%d local idx   statistics pass                      %6.1f us" % (F, t0))

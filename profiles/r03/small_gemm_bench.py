@@ -32,7 +32,7 @@ for name, Cin, Cout in (("conv1 128->64", 128, 64), ("conv1 256->64", 256, 64), 
     dT = torch.randn(R, Cout, device="cuda") * 1e-3
     Y = torch.empty(R, Cout, device="cuda")
     dX = torch.empty(R, Cin, device="cuda")
-    st = torch.zeros(E.H.STAT_SLOTS * 2 * Cout, dtype=torch.float64, device="cuda")
+    st = torch.zeros(E.H.stat_slots() * 2 * Cout, dtype=torch.float64, device="cuda")
     by = 4.0 * R * (Cin + Cout)
     t = [timeit(lambda: E.gemm(X, W, Y)), timeit(lambda: E.gemm(X, W, Y, stats=st)), timeit(lambda: E.gemm(dT, W, dX, transB=True))]
     tot += t[1] + t[2]

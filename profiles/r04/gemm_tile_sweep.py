@@ -35,7 +35,7 @@ for bm in (256, 128):
         Y = torch.empty(R, Cout, device="cuda")
         dX = torch.empty(R, Cin, device="cuda")
         dW = torch.zeros(Cin, Cout, device="cuda")
-        st = torch.zeros(H.STAT_SLOTS * 2 * Cout, dtype=torch.float64, device="cuda")
+        st = torch.zeros(H.stat_slots() * 2 * Cout, dtype=torch.float64, device="cuda")
         keys = torch.zeros(24 * Cout, dtype=torch.int64, device="cuda") if colmax else None
         fl = 2.0 * R * Cin * Cout
         t = [timeit(lambda: E.gemm(X, W, Y)), timeit(lambda: E.gemm(X, W, Y, stats=st, colmax=keys, colmax_rpg=2048 if colmax else 0)),

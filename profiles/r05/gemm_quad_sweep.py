@@ -40,7 +40,7 @@ for rnd in range(2):
         Y = torch.empty(R, Cout, device="cuda")
         dX = torch.empty(R, Cin, device="cuda")
         dW = torch.zeros(Cin, Cout, device="cuda")
-        st = torch.zeros(H.STAT_SLOTS * 2 * Cout, dtype=torch.float64, device="cuda")
+        st = torch.zeros(H.stat_slots() * 2 * Cout, dtype=torch.float64, device="cuda")
         keys = torch.zeros(24 * Cout, dtype=torch.int64, device="cuda") if colmax else None
         fl = 2.0 * R * Cin * Cout
         t = [timeit(lambda: E.gemm(X, W, Y)), timeit(lambda: E.gemm(X, W, Y, stats=st, colmax=keys, colmax_rpg=2048 if colmax else 0)),
@@ -50,7 +50,7 @@ for rnd in range(2):
             t[3] * 1e6, fl / t[3] / 1e12))
         st.zero_()
         E.gemm(X, W, Y, stats=st)
-        cur = (Y.clone(), dX.clone(), dW.clone(), st.view(H.STAT_SLOTS, 2, Cout).sum(0).clone())
+        cur = (Y.clone(), dX.clone(), dW.clone(), st.view(H.stat_slots(), 2, Cout).sum(0).clone())
         if (name, 256) in outs and bm != 256:
             ref = outs[(name, 256)]
             print("   vs 256 x 128: Y %s  dX %s  dW %s (split-K partials differ in grouping)  column sums rel %.1e" % (

@@ -14,18 +14,21 @@ D, P, L = "DenseClouds", "PackedClouds", "ListedClouds"
 # every k-NN switch at the library's default; a row's `sw` overrides some (all are restored after the row)
 KNN_DEFAULTS = dict(grid=1, force_valu=0, wide_min_c=129, big_k_min=65, bf16_filter=2, seed_min_n=-1, append=1, append_products=1,
                     hist=2)
+# the switches without a setter of their own, by their names in dgcnn_switch_set; a row's `table` overrides some (restored likewise)
+GRID_MIN_N_UNSET = -2 ** 31                  # DGCNN_SWITCH_UNSET
+TABLE_DEFAULTS = dict(DGCNN_KNN_GRID_MIN_N=GRID_MIN_N_UNSET)
 
 SQ = ("sqnorm_kernel", [])
 SQW = ("sqnorm_wide_kernel", [])
 GRID = lambda kc, c4, cl: [("knn_grid_build_kernel", [cl]), ("knn_grid_query_kernel", [str(kc), c4, "*", cl])]
 
 
-def knn_row(id, N, C, k, expect, B=2, ld=None, sw=None, seed=None, ws="full", engine=True):
+def knn_row(id, N, C, k, expect, B=2, ld=None, sw=None, seed=None, ws="full", engine=True, table=None):
     """One dense call.  ld: leading dimension of the view the call reads (None: C, contiguous).  seed: None, "own" (the row's own
     oracle graph, k columns) or "short" (k - 1 columns: kseed < k).  ws: "full" = dgcnn_knn_workspace_bytes, "s_i" = room for the norms
     only.  engine: the call can be issued through dgcnn._engine.knn as well (its tag is then held against the launches)."""
     return dict(id=id, B=B, N=N, C=C, k=k, ld=ld, sw=sw or {}, seed=seed, ws=ws, engine=engine and ws == "full" and seed != "short",
-                expect=expect)
+                expect=expect, table=table or {})
 
 
 def _valu(cp, kc, cl=D):
@@ -59,6 +62,9 @@ KNN_DENSE = [
     knn_row("c3_n4096_k64_scan", 4096, 3, 64, [SQ, _hist(2), _valu(4, 64)], B=1),         # the grid keeps k <= 40
     knn_row("c3_n300_grid_mode2", 300, 3, 20, [SQ] + GRID(20, "false", D), sw=dict(grid=2)),
     knn_row("c3_n4096_grid_mode0", 4096, 3, 20, [SQ, _hist(2), _valu(4, 20)], B=1, sw=dict(grid=0)),
+    # DGCNN_KNN_GRID_MIN_N moves the smallest N of mode 1, in the library and in the engine's tag alike
+    knn_row("c3_n1024_grid_min_n_1024", 1024, 3, 20, [SQ] + GRID(20, "false", D), table=dict(DGCNN_KNN_GRID_MIN_N=1024)),
+    knn_row("c3_n1024_grid_min_n_unset", 1024, 3, 20, [SQ, _hist(2), _valu(4, 20)]),
     knn_row("c4_n4096_grid", 4096, 4, 8, [SQ] + GRID(8, "true", D), B=1),
     knn_row("c1_n4096_grid", 4096, 1, 40, [SQ] + GRID(40, "false", D), B=1),
     # ---- C <= 16: fp32 distances on the matrix pipe, float4 or scalar loader

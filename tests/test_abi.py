@@ -68,10 +68,10 @@ def test_stat_slots_setter_and_gemm_tile_query_work_without_a_gpu():
     one writer per slot) and the tile the bf16-split GEMM picks for a shape (tools name kernel instances with it)."""
     from dgcnn import _hip as H
     lib = H.load()
-    assert lib.dgcnn_get_stat_slots() == H.STAT_SLOTS
+    assert lib.dgcnn_get_stat_slots() == H.stat_slots()
     try:
         H.set_stat_slots(768)
-        assert lib.dgcnn_get_stat_slots() == 768 and H.STAT_SLOTS == 768
+        assert lib.dgcnn_get_stat_slots() == 768 and H.stat_slots() == 768 and H.STAT_SLOTS == 768      # (the earlier spelling reads the same)
         with pytest.raises(ValueError):
             H.set_stat_slots(8)                                   # fewer than DGCNN_STAT_SLOTS: buffers of the plane kernels assume 32
         assert lib.dgcnn_get_stat_slots() == 768
@@ -80,6 +80,60 @@ def test_stat_slots_setter_and_gemm_tile_query_work_without_a_gpu():
     assert lib.dgcnn_gemm_x3_tile_rows(49152, 512, 1728) == 256     # FC0 forward: the wave-specialised 256 x 128 kernel
     assert lib.dgcnn_gemm_x3_tile_rows(49152, 64, 128) == 64        # conv1: short reduction over many rows
     assert lib.dgcnn_gemm_x3_tile_rows(1024, 512, 192) == 128       # configs[0]-sized problems
+
+
+def test_stat_slots_are_per_thread_in_python_as_in_the_library():
+    """The slot count is thread-local in the library, and Python keeps no copy of it: thread A at 256 slots does not make thread B
+    believe it is at 256 too.  B's Context.configure_slots for a deterministic step that needs 256 must issue the C call (a
+    process-wide mirror equal to 256 would skip it and leave B's launches at 32 slots against buffers sized for 256), and neither
+    thread's later changes reach the other."""
+    import threading
+    from dgcnn import _engine as E
+    from dgcnn import _hip as H
+    lib = H.load()
+    a_set, b_done = threading.Event(), threading.Event()
+    seen, errors = {}, []
+
+    def guarded(fn):
+        def run():
+            try:
+                fn()
+            except BaseException as e:                            # (a failed thread must not leave the other waiting)
+                errors.append(e)
+                a_set.set()
+                b_done.set()
+        return run
+
+    def thread_a():
+        H.set_stat_slots(256)
+        seen["a_after_set"] = H.stat_slots()
+        a_set.set()
+        assert b_done.wait(30)
+        seen["a_after_b"] = H.stat_slots()
+
+    def thread_b():
+        assert a_set.wait(30)
+        seen["b_start"] = H.stat_slots()
+        c = E.Context()
+        c.configure_slots(16384)                                  # 16384 / 64 = 256 row tiles: 256 slots
+        seen["b_256"] = (c.step_slots, H.stat_slots(), lib.dgcnn_get_stat_slots())
+        c.configure_slots(20000)                                  # 313 row tiles, rounded up to whole 64s
+        seen["b_320"] = (c.step_slots, H.stat_slots())
+        b_done.set()
+
+    prev = E.DETERMINISTIC
+    E.DETERMINISTIC = True
+    try:
+        ta, tb = threading.Thread(target=guarded(thread_a)), threading.Thread(target=guarded(thread_b))
+        ta.start()
+        tb.start()
+        ta.join(60)
+        tb.join(60)
+    finally:
+        E.DETERMINISTIC = prev
+    assert not errors, errors
+    assert seen == dict(a_after_set=256, b_start=32, b_256=(256, 256, 256), b_320=(320, 320), a_after_b=256), seen
+    assert H.stat_slots() == 32                                   # this thread was never touched
 
 
 def test_knn_workspace_sizes_and_switches_are_plain_host_state():

@@ -172,14 +172,14 @@ def test_forward_passes(dg, case, tier, lay):
     B, N, C, k, F, kind = case
     geo = EB.geometry(case)
     R, Me = geo["R"], geo["Me"]
-    assert H.STAT_SLOTS == EB.DEFAULT_SLOTS
+    assert H.stat_slots() == EB.DEFAULT_SLOTS
     o = EB.forward_case(case, tier)
     what = "%s %s %s" % (case, tier, lay)
     g = Guard()
     src, keep = source(g, o, lay)
     Yh = write_y(H, g, o, src, what)
 
-    st = g.zeros((H.STAT_SLOTS, 2, F), torch.float64)
+    st = g.zeros((H.stat_slots(), 2, F), torch.float64)
     H.call("dgcnn_edge_mlp_bf16_stats", *src, st.data_ptr())
     check_stats(what, host(st).sum(0), o, Yh)
     if case in EB.FWD_MULTI_TILE:           # the tile loops loop: a change of the caps must not silently undo that
@@ -288,9 +288,9 @@ def test_backward_pass(dg, case, tier, lay):
     same_bits(what + " packed counts", host(cnt), fw.packed)
     dmx, dmn, ldd = halves(g, R, F, lay, o.dmax, o.dmean)
     if o.lattice:
-        red0 = np.zeros((H.STAT_SLOTS, 2, F))
+        red0 = np.zeros((H.stat_slots(), 2, F))
     else:
-        red = g.zeros((H.STAT_SLOTS, 2, F), torch.float64)
+        red = g.zeros((H.stat_slots(), 2, F), torch.float64)
         H.call("dgcnn_edge_bn_bwd_reduce_points_f32", mx.data_ptr(), ldm, mn.data_ptr(), ldm, cnt.data_ptr(), dmx.data_ptr(), ldd,
                dmn.data_ptr(), ldd, par[2], R, k, F, red.data_ptr())
         red0 = host(red).copy()
@@ -360,7 +360,7 @@ def test_refusals(dg):
     mxv, mnv, cntv = g.new((R, 128)), g.new((R, 128)), g.new((R, 128))
     H.call("dgcnn_edge_mlp_bf16_bn_kreduce", *src, *pp, mxv.data_ptr(), F, mnv.data_ptr(), F, cntv.data_ptr(), 1)
     dm = g.put(rng.normal(size=(R, 128)).astype(np.float32))
-    red0 = rng.normal(size=(H.STAT_SLOTS, 2, 128))
+    red0 = rng.normal(size=(H.stat_slots(), 2, 128))
     red = g.put(red0)
     need = int(lib.dgcnn_edge_mlp_bf16_bwd_workspace_bytes(B, N, C, k, 128))
     ws = g.new((need,), torch.uint8, fill=7)
@@ -369,7 +369,7 @@ def test_refusals(dg):
     mx, mn, cnt, dsum = (g.new((R, 128)) for _ in range(4))
     for t in (Y, mx, mn, cnt, dsum):
         t.fill_(NAN)
-    st = g.zeros((H.STAT_SLOTS, 2, 128), torch.float64)
+    st = g.zeros((H.stat_slots(), 2, 128), torch.float64)
     dYb = g.new((R * 129, 128), torch.int16, fill=NAN_BF16)
     dW, db = g.new((128, 128)), g.new((128,))
     dW.fill_(5.0)

@@ -238,9 +238,9 @@ def test_fused_passes_agree_with_each_other_and_with_the_rounded_product(dg, B, 
     scale = np.abs(O.bf16_round(E.astype(np.float32)).astype(np.float64)) @ np.abs(O.bf16_round(W0).astype(np.float64))
     assert (np.abs(got - ref) <= 2e-6 * scale + 1e-30).all(), float((np.abs(got - ref) / np.maximum(scale, 1e-30)).max())
     # statistics pass == column sums of the written-out y (fp32 partial sums in a different grouping: 1e-5 relative)
-    st = torch.zeros(H.STAT_SLOTS * 2 * F, dtype=torch.float64, device="cuda")
+    st = torch.zeros(H.stat_slots() * 2 * F, dtype=torch.float64, device="cuda")
     H.call("dgcnn_edge_mlp_bf16_stats", *src, st.data_ptr())
-    s = host(st).reshape(H.STAT_SLOTS, 2, F).sum(0)
+    s = host(st).reshape(H.stat_slots(), 2, F).sum(0)
     np.testing.assert_allclose(s[0], got.sum(0), rtol=1e-5, atol=1e-3)
     np.testing.assert_allclose(s[1], (got * got).sum(0), rtol=1e-5, atol=1e-3)
     # BN + ReLU + k-reduce pass == the dense kernel on the written-out y, bit for bit
@@ -293,7 +293,7 @@ def test_fused_backward_pass_against_the_dense_kernels(dg, B, N, C, k, F):
     z = np.maximum((host(Y).reshape(R, k, F) - host(mean)) * host(rstd) + host(beta), 0)
     np.testing.assert_array_equal(npos, (z > 0).sum(1))                                   # the packed half the forward adds
     dmx, dmn = dev(rng.normal(size=(R, F)).astype(np.float32)), dev(rng.normal(size=(R, F)).astype(np.float32))
-    red = torch.zeros((H.STAT_SLOTS, 2, F), dtype=torch.float64, device="cuda")
+    red = torch.zeros((H.stat_slots(), 2, F), dtype=torch.float64, device="cuda")
     H.call("dgcnn_edge_bn_bwd_reduce_points_f32", mx.data_ptr(), F, mn.data_ptr(), F, cntp.data_ptr(), dmx.data_ptr(), F, dmn.data_ptr(), F,
            beta.data_ptr(), R, k, F, red.data_ptr())
     redA, redB = red.clone(), red.clone()

@@ -38,7 +38,7 @@ def _error_table():
 
 
 def slots(H):
-    return H.STAT_SLOTS
+    return H.stat_slots()
 
 
 class Dense(object):
@@ -548,7 +548,7 @@ def test_every_stat_slot_is_reduced(dg, nslots):
     """`red` / `stats` pre-filled in several slots with integer-valued doubles (exact in any order): the apply pass must reduce all
     stat_slots of them into slot 0, dgcnn_bn_finalize_f32 must use all of them; at 32 and at 256 slots."""
     from dgcnn import _hip as H
-    old = H.STAT_SLOTS
+    old = H.stat_slots()
     H.set_stat_slots(nslots)
     try:
         rng = np.random.default_rng(nslots)

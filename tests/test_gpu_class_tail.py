@@ -112,7 +112,7 @@ class _slots(object):
         self.n = n
 
     def __enter__(self):
-        self.prev = H.STAT_SLOTS
+        self.prev = H.stat_slots()
         H.set_stat_slots(self.n)
 
     def __exit__(self, *exc):

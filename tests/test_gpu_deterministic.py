@@ -86,9 +86,9 @@ def test_det_kernels_against_numpy(det):
     R, F = 5000, 70
     wide = rng.normal(size=(R, 100)).astype(np.float32)
     T = dev(wide)[:, 10:10 + F]
-    st = torch.zeros(H.STAT_SLOTS * 2 * F, dtype=torch.float64, device="cuda")
+    st = torch.zeros(H.stat_slots() * 2 * F, dtype=torch.float64, device="cuda")
     E.colstats_det(T, st)
-    s = host(st).reshape(H.STAT_SLOTS, 2, F)
+    s = host(st).reshape(H.stat_slots(), 2, F)
     assert np.abs(s[1:]).max() == 0
     np.testing.assert_allclose(s[0, 0], wide[:, 10:10 + F].astype(np.float64).sum(0), rtol=1e-12, atol=1e-9)
     np.testing.assert_allclose(s[0, 1], (wide[:, 10:10 + F].astype(np.float64) ** 2).sum(0), rtol=1e-12, atol=1e-9)
@@ -153,14 +153,14 @@ def test_deterministic_mode_runs_the_default_kernels(det):
         _run(1, pts, lab)
     finally:
         E.H.call = orig
-    assert H.STAT_SLOTS >= 256
+    assert H.stat_slots() >= 256
     assert "dgcnn_colstats_det_f32" not in calls
     assert calls.count("dgcnn_bn_bwd_reduce_det_f32") == 1                 # the Final layer (3 classes)
     assert "dgcnn_edge_bn_act_kreduce_f32" in calls and "dgcnn_edge_csr_sort" in calls
     dgcnn.reset()
     E.DETERMINISTIC = False
     dgcnn.reset()
-    assert H.STAT_SLOTS == 32
+    assert H.stat_slots() == 32
 
 
 def test_two_full_size_steps_are_bit_identical(det):
@@ -183,7 +183,7 @@ def test_two_full_size_steps_are_bit_identical(det):
             tv.accum_gradient(None, [pts[s]], [lab[s]])
             grads.append(c.flat_grad.clone())
             tv.apply_gradient(None)
-        return c.flat_param.clone(), grads, H.STAT_SLOTS
+        return c.flat_param.clone(), grads, H.stat_slots()
     p1, g1, slots = run()
     p2, g2, _ = run()
     assert slots == 768

@@ -141,7 +141,7 @@ def test_forward_forms(dg, case, lay):
                 what = "%s %s %s lattice=%d stats=%d" % (form, case, lay, o.lattice, with_stats)
                 Y = g.new((Me, F))
                 Y.fill_(NAN)                                                     # beta = 0: the kernel must not read Y
-                st = g.zeros((H.STAT_SLOTS, 2, F), torch.float64) if with_stats else None
+                st = g.zeros((H.stat_slots(), 2, F), torch.float64) if with_stats else None
                 if form == "edge_mlp_f32":
                     H.call("dgcnn_edge_mlp_f32", x.data_ptr(), ldx, idx.data_ptr(), W0.data_ptr(), B, N, C, k, F, Y.data_ptr(), ptr(st))
                 else:

@@ -118,7 +118,7 @@ class Case(object):
     def backward(self, H, x, ldx, C, dmax, dmean, mx, cnt, red0):
         """-> host partial sums of the blocks, dW0 (on zeros), dbeta."""
         g, R, F = self.g, self.R, self.F
-        red = g.zeros((H.STAT_SLOTS, 2, F), torch.float64)
+        red = g.zeros((H.stat_slots(), 2, F), torch.float64)
         red[0] = torch.from_numpy(red0).cuda()
         xd = g.new((R, ldx))
         xd[:, :C] = torch.from_numpy(x).cuda()
@@ -302,7 +302,7 @@ def test_row_offsets_of_two_to_the_31_elements_and_more(H):
         with switch(H, sw):
             mx, mn, cnt = g.new((N, F)), g.new((N, F)), g.new((N, F))
             H.call("dgcnn_edge_bn_act_kreduce_f32", *head, *pp, 1, mx.data_ptr(), F, mn.data_ptr(), F, cnt.data_ptr())
-            red = g.zeros((H.STAT_SLOTS, 2, F), torch.float64)
+            red = g.zeros((H.stat_slots(), 2, F), torch.float64)
             red[0] = torch.from_numpy(red0).cuda()
             ws, dW, dbeta = g.new((need // 4,)), g.zeros((2 * C, F)), g.zeros((F,))
             H.call("dgcnn_edge_bn_bwd_apply_wgrad_f32", *head, *pp, dmax.data_ptr(), F, dmean.data_ptr(), F, mx.data_ptr(), F,

@@ -109,7 +109,7 @@ class PackedDev(object):
 def dense_gather_add(H, d, V, want_y=True):
     c, g = d.c, d.g
     Y = g.new((c.R * c.k, c.F)) if want_y else None
-    st = g.zeros((H.STAT_SLOTS, 2, c.F), torch.float64)
+    st = g.zeros((H.stat_slots(), 2, c.F), torch.float64)
     H.call("dgcnn_edge_gather_add_f32", *d.head(V), p(Y), st.data_ptr())
     return (host(Y).reshape(c.R, c.k, c.F) if want_y else None), host(st).sum(0)
 
@@ -117,7 +117,7 @@ def dense_gather_add(H, d, V, want_y=True):
 def dense_apply(H, d, V, ref, relu):
     """-> dY (R, k, F), dYsum with the exact float64 sums in slot 0 of red, max / packed count given."""
     c, g = d.c, d.g
-    red = g.zeros((H.STAT_SLOTS, 2, c.F), torch.float64)
+    red = g.zeros((H.stat_slots(), 2, c.F), torch.float64)
     red[0] = torch.from_numpy(ref["red"]).cuda()
     mx, cnt = put(g, ref["max"]), put(g, ref["packed"])
     dY, ds, dbeta = g.new((c.R * c.k, c.F)), g.new((c.R, c.F)), g.zeros((c.F,))
@@ -152,7 +152,7 @@ def test_dense_bwd_reduce(H):
     mx, cnt = put(g, ref["max"]), put(g, ref["packed"])
     with far_view(c.V, c.ld) as V:
         for m, n in ((mx, cnt), (None, None)):
-            red = g.zeros((H.STAT_SLOTS, 2, c.F), torch.float64)
+            red = g.zeros((H.stat_slots(), 2, c.F), torch.float64)
             H.call("dgcnn_edge_bn_bwd_reduce_f32", *d.head(V), *d.par, 1, d.dmax.data_ptr(), c.F, d.dmean.data_ptr(), c.F, p(m),
                    c.F if m is not None else 0, p(n), red.data_ptr())
             np.testing.assert_array_equal(host(red).sum(0), ref["red"], err_msg="red (%s)" % ("mx_in" if m is not None else "recomputed"))
@@ -302,7 +302,7 @@ def test_shape_r_dense_statistics(H):
     c = FR.r_case()
     g = Guard()
     U, idx = _r_device(c, g)
-    st = g.zeros((H.STAT_SLOTS, 2, c.F), torch.float64)
+    st = g.zeros((H.stat_slots(), 2, c.F), torch.float64)
     with far_view(c.V, c.ld) as V:
         H.call("dgcnn_edge_gather_add_f32", V, c.ld, U.data_ptr(), c.F, idx.data_ptr(), 1, c.N, c.k, c.F, 0, st.data_ptr())
         got = host(st).sum(0)
@@ -344,7 +344,7 @@ def _entries(H, g, V, ldv, N, F=FR.W_F, k=FR.W_K, rows_out=256):
     v, db = g.zeros((F,)), g.zeros((F,))
     a, b, cnt = g.new((rows_out, F)), g.new((rows_out, F)), g.new((rows_out, F))
     big = g.new((rows_out * k, F))
-    red = g.new((H.STAT_SLOTS, 2, F), torch.float64)
+    red = g.new((H.stat_slots(), 2, F), torch.float64)
     seg = g.put(np.array([0, min(N, rows_out)], np.int32))
     rg = g.zeros((rows_out,), torch.int32)
     nb = 4 * 1024 * 1024

@@ -213,11 +213,11 @@ def test_arith1_layouts_and_epilogues(dg, M, N, K, tier):
                 kname = instance(M, N, K, layout, A, Bm)
                 what = "%s %s override %d (%d, %d, %d) %s gbias/stats/slice" % (layout, kname, override, M, N, K, tier)
                 outw, C, lo = out_slice(M, N, aligned)
-                st = torch.zeros(E.H.STAT_SLOTS * 2 * N, dtype=torch.float64, device="cuda")
+                st = torch.zeros(E.H.stat_slots() * 2 * N, dtype=torch.float64, device="cuda")
                 E.gemm(A, Bm, C, gbias=gbuf[aligned], rpg=RPG, stats=st, **tr)
                 P.check(C, kname, what, bias)
                 assert outside_untouched(outw, lo, N), (what, "wrote outside its columns")
-                P.check_stats(st, C, E.H.STAT_SLOTS, kname, what)
+                P.check_stats(st, C, E.H.stat_slots(), kname, what)
 
 
 @pytest.mark.parametrize("tier", ["lattice", "ties", "random"])
@@ -395,7 +395,7 @@ def test_planes_kc_epilogues_on_a_ragged_last_row_tile(dg, M, N, K):
     tb, tg = bias_of(T, 7)
     twant = R.product_int(T.hA, T.hB).astype(np.float64) + host(tb)
     Tx, Tw = planes(T.hA), planes(T.hB, transpose=True)
-    prev = H.STAT_SLOTS
+    prev = H.stat_slots()
     try:
         for slots in (32, 256):
             H.set_stat_slots(slots)
@@ -496,7 +496,7 @@ def test_planes_refusals_leave_c_alone(dg):
     ps = lambda rows, cols: planes(R.random(rng, (rows, cols)))
     a64, b64, a40 = ps(64, 64), ps(64, 64), ps(64, 40)
     gb = torch.zeros((1, 64), device="cuda")
-    st = torch.zeros(H.STAT_SLOTS * 2 * 64, dtype=torch.float64, device="cuda")
+    st = torch.zeros(H.stat_slots() * 2 * 64, dtype=torch.float64, device="cuda")
     keys = torch.zeros(64, dtype=torch.int64, device="cuda")
 
     def view(p, **kw):

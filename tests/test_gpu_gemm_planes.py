@@ -67,12 +67,12 @@ def test_kc_epilogue_options_beta_bias_stats_and_channel_views():
     Xp = allp.cols_view(64, 64 + K)                           # a channel range of a wider plane set
     Wp = P.from_f32(torch.from_numpy(W).cuda(), transpose=True)
     C = torch.from_numpy(C0.copy()).cuda()
-    st = torch.zeros(H.STAT_SLOTS * 2 * N, dtype=torch.float64, device="cuda")
+    st = torch.zeros(H.stat_slots() * 2 * N, dtype=torch.float64, device="cuda")
     P.gemm(P.KC, Xp, Wp, C, beta=1.0, gbias=torch.from_numpy(gb).cuda(), rpg=M // 8, stats=st)
     ref = C0 + X.astype(np.float64) @ W.astype(np.float64) + np.repeat(gb, M // 8, axis=0)
     got = C.cpu().numpy().astype(np.float64)
     np.testing.assert_allclose(got, ref, rtol=0, atol=2e-5)
-    s = st.cpu().numpy().reshape(H.STAT_SLOTS, 2, N).sum(0)
+    s = st.cpu().numpy().reshape(H.stat_slots(), 2, N).sum(0)
     np.testing.assert_allclose(s[0], got.sum(0), rtol=1e-6, atol=1e-3)
     np.testing.assert_allclose(s[1], (got * got).sum(0), rtol=1e-6, atol=1e-3)
 

@@ -167,12 +167,12 @@ def test_column_maximum_on_every_tile(dg, B, N, Cin, F, override):
         what = "%s (B=%d N=%d Cin=%d, override %d)" % (kernel_name(R, F, Cin), B, N, Cin, override)
         T = torch.empty((R, F), device="cuda")
         keys = torch.zeros(B * F, dtype=torch.int64, device="cuda")
-        st = torch.zeros(E.H.STAT_SLOTS * 2 * F, dtype=torch.float64, device="cuda")
+        st = torch.zeros(E.H.stat_slots() * 2 * F, dtype=torch.float64, device="cuda")
         recorded_gemm(dev(X), dev(W), T, expect=COLMAX_LAUNCHED[override], stats=st, colmax=keys, colmax_rpg=N)
         vals, arg = decode(keys, B, F)
     Th = host(T)
     assert_colmax(vals, arg, Th, B, N, F, what)
-    assert_colsums(st, Th.astype(np.float64), E.H.STAT_SLOTS, what)
+    assert_colsums(st, Th.astype(np.float64), E.H.stat_slots(), what)
     ref = X.astype(np.float64) @ W.astype(np.float64)
     err = np.abs(Th - ref) / (np.abs(X) @ np.abs(W) + 1e-30)
     assert err.max() < REL_BAR, (what, float(err.max()))
@@ -325,12 +325,12 @@ def test_tiles_layouts_epilogues_against_float64(dg, M, N, K):
                 outw = torch.zeros((M, N + pad), device="cuda")
                 C = outw[:, lo:lo + N]
                 gb = gbuf[aligned][:, :N]
-                st = torch.zeros(E.H.STAT_SLOTS * 2 * N, dtype=torch.float64, device="cuda")
+                st = torch.zeros(E.H.stat_slots() * 2 * N, dtype=torch.float64, device="cuda")
                 recorded_gemm(A, Bm, C, expect=kname, gbias=gb, rpg=RPG, stats=st, **tr)
                 e = P.rel_err(C, bias)
                 assert e < REL_BAR, (what, e)
                 assert not bool(outw[:, :lo].any()) and not bool(outw[:, lo + N:].any()), (what, "wrote outside its columns")
-                assert_colsums(st, host(C).astype(np.float64), E.H.STAT_SLOTS, what)
+                assert_colsums(st, host(C).astype(np.float64), E.H.stat_slots(), what)
     # gemm_x3.hip: the 256 x 128 wave-specialised kernel and both 256-column kernels keep the same per-element k order
     for layout, outs in big.items():
         if layout == "TN" and K >= 512:
@@ -401,7 +401,7 @@ def test_stat_writers_cover_the_row_tiles(dg, M, N, K, transB, colmax_rpg):
     P = Problem(M, N, K, M + K)
     A, Bm, tr = P.operands("NT" if transB else "NN")
     B = M // colmax_rpg if colmax_rpg else 0
-    prev_slots = H.STAT_SLOTS
+    prev_slots = H.stat_slots()
     try:
         for arith, override in CONFIGS:
             with tile(override, arith):

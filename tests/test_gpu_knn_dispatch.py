@@ -17,7 +17,7 @@ import torch
 
 from oracle import dgcnn_oracle as O
 from gpu_helpers import dev, host
-from launch_trace import launches, timed, check_kernels
+from launch_trace import launches, timed, check_kernels, assert_launched
 import dispatch_tables as T
 
 pytestmark = pytest.mark.gpu
@@ -66,19 +66,26 @@ def view(x, ld):
 
 
 @contextlib.contextmanager
-def switches(sw, mix_t=None):
+def switches(sw, mix_t=None, table=None):
     from dgcnn import _hip as H
     lib = H.load()
     want = dict(T.KNN_DEFAULTS)
     want.update(sw)
-    prev = []
+    named = dict(T.TABLE_DEFAULTS)
+    named.update(table or {})
+    prev, prev_named = [], []
     try:
         for name, value in want.items():
             prev.append((name, getattr(lib, "dgcnn_knn_" + name)(value)))
         if mix_t is not None:
             prev.append(("seg_mix_min_n", lib.dgcnn_knn_seg_mix_min_n(mix_t)))
+        for name, value in named.items():
+            prev_named.append((name, H.switch(name)))
+            H.set_switch(name, value)
         yield lib
     finally:
+        for name, value in reversed(prev_named):
+            H.set_switch(name, value)
         for name, value in reversed(prev):
             getattr(lib, "dgcnn_knn_" + name)(value)
 
@@ -172,7 +179,7 @@ def test_dense_row(r):
     xd = view(cloud(B * N, C), r["ld"])
     assert H.ld2(xd) == (r["ld"] or C)
     seed_d, kseed = None, 0
-    with switches(r["sw"]):
+    with switches(r["sw"], table=r["table"]):
         if r["seed"] is not None:
             # the row's own graph: the oracle's, or above N = 4096 (where only sampled rows have one) the library's unseeded lists,
             # which the check below holds against the oracle on the sampled rows like every other result
@@ -196,6 +203,36 @@ def test_dense_row(r):
         del xd
         torch.cuda.empty_cache()
     same(got.reshape(B * N, k) if rows is None else got[0][rows], want.reshape(-1, k), r["id"])
+
+
+@pytest.mark.parametrize("N", [2048, 8192], ids=["lx", "carried_queue"])
+def test_tighten_every_gives_the_same_indices(N):
+    """DGCNN_KNN_TIGHTEN_EVERY = 1, 2 and 8 against the default (0: every 4th tile below N = 8192, every 8th from there on): one
+    seeded append-form call of each form, (B, C, k) = (1, 64, 20), seeded by the k = 20 graph of the same cloud, gives bit-equal
+    indices.  A row meets N / 64 candidate tiles (knn.hip:knn_bf16a_kernel: TJM = 64) and the first 8 are tightened at every
+    setting, so a setting only shows from the 9th tile on: N = 2048 has 32 tiles, N = 8192 (the first N of the other form) 128."""
+    from dgcnn import _engine as E
+    from dgcnn import _hip as H
+    B, C, k = 1, 64, 20
+    assert N // 64 >= 16
+    xd = dev(np.array(cloud(N, C)))
+    out = {}
+    with switches({}):
+        seed = E.knn(xd, B, N, k)
+        prev = H.switch("DGCNN_KNN_TIGHTEN_EVERY")
+        try:
+            for every in (0, 1, 2, 8):
+                H.set_switch("DGCNN_KNN_TIGHTEN_EVERY", every)
+                with launches() as L:
+                    idx = E.knn(xd, B, N, k, seed=seed)
+                print(N, every, [(e[0], e[1]) for e in L])
+                assert_launched(L, "knn_bf16a_kernel", ["true" if N < 8192 else "false"])
+                out[every] = host(idx)
+        finally:
+            H.set_switch("DGCNN_KNN_TIGHTEN_EVERY", prev)
+    assert np.array_equal(out[0], host(seed)), "the seeded call differs from the unseeded graph of the same cloud"
+    for every in (1, 2, 8):
+        assert np.array_equal(out[every], out[0]), "DGCNN_KNN_TIGHTEN_EVERY=%d differs from the default" % every
 
 
 # ------------------------------------------------------------------------------------------------------

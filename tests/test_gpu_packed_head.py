@@ -266,14 +266,14 @@ def test_gemm_seg_bias_on_every_tile(dg, arith, override, forced, sizes, N, K):
                 gbuf[:, :N] = dev(gb)
                 outw = torch.zeros((M, N + 8), device="cuda")
                 C1 = outw[:, 4:4 + N]
-                st = torch.zeros(E.H.STAT_SLOTS * 2 * N, dtype=torch.float64, device="cuda")
+                st = torch.zeros(E.H.stat_slots() * 2 * N, dtype=torch.float64, device="cuda")
                 E.gemm(dev(A), Bd, C1, gbias=gbuf[:, :N], stats=st, row_group=rgd, **tr)
                 got = host(C1)
                 bad = np.argwhere(got != want)
                 assert len(bad) == 0, "%s: %d elements differ from product + bias, first %s: %r vs %r" % (
                     what, len(bad), bad[0], got[tuple(bad[0])], want[tuple(bad[0])])
                 assert not bool(outw[:, :4].any()) and not bool(outw[:, 4 + N:].any()), (what, "wrote outside its columns")
-                assert_colsums(st, got.astype(np.float64), E.H.STAT_SLOTS, what)
+                assert_colsums(st, got.astype(np.float64), E.H.stat_slots(), what)
 
 
 @pytest.mark.parametrize("arith,override", [(6, 128), (6, 256), (6, 512), (6, 448), (0, 0)])

@@ -219,10 +219,10 @@ def test_gemm_skinny_class_dimension(dg, M, N, K):
     ref = A.astype(np.float64) @ W
     tol = dict(rtol=1e-5, atol=2e-6 * K ** 0.5 * 4 + 1e-5)
     C = dev(np.full((M, N), 0.5, np.float32))
-    st = torch.zeros(E.H.STAT_SLOTS * 2 * N, dtype=torch.float64, device="cuda")
+    st = torch.zeros(E.H.stat_slots() * 2 * N, dtype=torch.float64, device="cuda")
     E.gemm(dev(A), dev(W), C, beta=2.0, stats=st)
     np.testing.assert_allclose(host(C), ref + 1.0, **tol)
-    s = host(st).reshape(E.H.STAT_SLOTS, 2, N).sum(0)
+    s = host(st).reshape(E.H.stat_slots(), 2, N).sum(0)
     np.testing.assert_allclose(s[0], (ref + 1.0).sum(0), rtol=1e-5, atol=1e-2)
     np.testing.assert_allclose(s[1], ((ref + 1.0) ** 2).sum(0), rtol=1e-5, atol=1e-2)
     # weight gradient: dW (K x N) += A^T dT
@@ -284,12 +284,12 @@ def test_gemm_strided_stats_and_group_bias(dg, arith):
     gb = rng.normal(size=(G, F)).astype(np.float32)
     outw = torch.zeros((R, 200), device="cuda")
     C = outw[:, 40:40 + F]
-    st = torch.zeros(E.H.STAT_SLOTS * 2 * F, dtype=torch.float64, device="cuda")
+    st = torch.zeros(E.H.stat_slots() * 2 * F, dtype=torch.float64, device="cuda")
     E.gemm(A, dev(W), C, gbias=dev(gb), rpg=R // G, stats=st)
     ref = wide[:, 100:100 + Cin].astype(np.float64) @ W + np.repeat(gb, R // G, 0)
     np.testing.assert_allclose(host(C), ref, rtol=1e-5, atol=1e-4)
     assert host(outw)[:, :40].max() == 0 and host(outw)[:, 40 + F:].max() == 0     # nothing outside the slice
-    s = host(st).reshape(E.H.STAT_SLOTS, 2, F).sum(0)
+    s = host(st).reshape(E.H.stat_slots(), 2, F).sum(0)
     np.testing.assert_allclose(s[0], ref.sum(0), rtol=1e-5, atol=1e-3)
     np.testing.assert_allclose(s[1], (ref ** 2).sum(0), rtol=1e-5, atol=1e-3)
     mean, rstd = E.bn_finalize(st, F, R)
@@ -430,7 +430,7 @@ def test_edge_bn_passes_equal_dense_passes(dg, B, N, k, F):
     dmx, dmn = dev(rng.normal(size=(R, F)).astype(np.float32)), dev(rng.normal(size=(R, F)).astype(np.float32))
     reds, dys = [], []
     for edge in (False, True):
-        red = torch.zeros((H.STAT_SLOTS, 2, F), dtype=torch.float64, device="cuda")
+        red = torch.zeros((H.stat_slots(), 2, F), dtype=torch.float64, device="cuda")
         args = (mean.data_ptr(), rstd.data_ptr(), beta.data_ptr(), 1, dmx.data_ptr(), F, dmn.data_ptr(), F,
                 mx.data_ptr(), F, cnt.data_ptr())
         if edge:
@@ -441,12 +441,12 @@ def test_edge_bn_passes_equal_dense_passes(dg, B, N, k, F):
         reds.append(host(red).sum(0))
     np.testing.assert_allclose(reds[0], reds[1], rtol=1e-6, atol=1e-4)
     # the same two sums from per-point data only (no pass over the edges)
-    red = torch.zeros((H.STAT_SLOTS, 2, F), dtype=torch.float64, device="cuda")
+    red = torch.zeros((H.stat_slots(), 2, F), dtype=torch.float64, device="cuda")
     H.call("dgcnn_edge_bn_bwd_reduce_points_f32", mx.data_ptr(), F, mn.data_ptr(), F, cnt_packed.data_ptr(), dmx.data_ptr(), F,
            dmn.data_ptr(), F, beta.data_ptr(), R, k, F, red.data_ptr())
     rp = host(red).sum(0)
     np.testing.assert_allclose(rp, reds[0], rtol=2e-4, atol=2e-3 * max(1.0, float(np.abs(reds[0]).max()) * 1e-2))
-    red0 = torch.zeros((H.STAT_SLOTS, 2, F), dtype=torch.float64, device="cuda")
+    red0 = torch.zeros((H.stat_slots(), 2, F), dtype=torch.float64, device="cuda")
     red0[0] = dev(reds[0])
     for edge in (False, True):
         red = red0.clone()
@@ -510,7 +510,7 @@ def test_edge_gather_add_and_weight_fold(dg, B, N, k, F, ld):
     idx = rng.integers(0, N, (B, N, k)).astype(np.int32)
     d_uv, d_idx = dev(UV), dev(idx)
     Y = torch.full((B * N * k, F), float("nan"), device="cuda")
-    st = torch.zeros((H.STAT_SLOTS if hasattr(H, "STAT_SLOTS") else 32, 2, F), dtype=torch.float64, device="cuda")
+    st = torch.zeros((H.stat_slots() if hasattr(H, "stat_slots") else 32, 2, F), dtype=torch.float64, device="cuda")
     H.call("dgcnn_edge_gather_add_f32", d_uv[:, F:].data_ptr(), ld, d_uv.data_ptr(), ld, d_idx.data_ptr(), B, N, k, F,
            Y.data_ptr(), st.data_ptr())
     U, V = UV[:, :F].reshape(B, N, F), UV[:, F:2 * F].reshape(B, N, F)
@@ -1057,7 +1057,7 @@ def test_column_maximum_from_the_gemm_epilogue(dg, B, N, Cin, F):
     W[:, :3] = 0.0                                              # all-equal columns: every row ties, the first must win
     T = torch.empty((B * N, F), device="cuda")
     keys = torch.zeros(B * F, dtype=torch.int64, device="cuda")
-    st = torch.zeros(E.H.STAT_SLOTS * 2 * F, dtype=torch.float64, device="cuda")
+    st = torch.zeros(E.H.stat_slots() * 2 * F, dtype=torch.float64, device="cuda")
     E.gemm(dev(X), dev(W), T, stats=st, colmax=keys, colmax_rpg=N)
     vals = torch.empty((B, F), device="cuda")
     arg = torch.empty((B, F), dtype=torch.int32, device="cuda")
@@ -1065,7 +1065,7 @@ def test_column_maximum_from_the_gemm_epilogue(dg, B, N, Cin, F):
     Th = host(T).reshape(B, N, F)
     np.testing.assert_array_equal(host(vals), Th.max(1))
     np.testing.assert_array_equal(host(arg), Th.argmax(1))          # numpy's argmax is the first maximum too
-    s = host(st).reshape(E.H.STAT_SLOTS, 2, F).sum(0)               # the BatchNorm column sums of the same epilogue
+    s = host(st).reshape(E.H.stat_slots(), 2, F).sum(0)               # the BatchNorm column sums of the same epilogue
     np.testing.assert_allclose(s[0], Th.reshape(-1, F).astype(np.float64).sum(0), rtol=1e-5, atol=1e-2)
     np.testing.assert_allclose(s[1], (Th.reshape(-1, F).astype(np.float64) ** 2).sum(0), rtol=1e-5, atol=1e-2)
 
@@ -1084,10 +1084,10 @@ def test_short_reduction_gemms_of_the_edgeconv_blocks(dg, M, N, K, transB):
     tol = 2e-6 * K ** 0.5 * 4 + 1e-5
     Ad, Wd = dev(A), dev(W)
     C = torch.empty((M, N), device="cuda")
-    st = torch.zeros(E.H.STAT_SLOTS * 2 * N, dtype=torch.float64, device="cuda")
+    st = torch.zeros(E.H.stat_slots() * 2 * N, dtype=torch.float64, device="cuda")
     E.gemm(Ad, Wd, C, transB=transB, stats=st)
     np.testing.assert_allclose(host(C), ref, rtol=1e-5, atol=tol)
-    s = host(st).reshape(E.H.STAT_SLOTS, 2, N).sum(0)
+    s = host(st).reshape(E.H.stat_slots(), 2, N).sum(0)
     np.testing.assert_allclose(s[0], ref.sum(0), rtol=1e-5, atol=2e-2)
     np.testing.assert_allclose(s[1], (ref ** 2).sum(0), rtol=1e-5, atol=2e-2)
     old = rng.normal(size=(M, N)).astype(np.float32)

@@ -76,7 +76,7 @@ def param_scales(H, g, params, rows_max, act_mul):
 def stats_of(H, g, T):
     n, F = T.shape
     Td = T.astype(np.float64)
-    st = g.zeros((H.STAT_SLOTS, 2, F), torch.float64)
+    st = g.zeros((H.stat_slots(), 2, F), torch.float64)
     st[0, 0], st[0, 1] = torch.from_numpy(Td.sum(0)).cuda(), torch.from_numpy((Td * Td).sum(0)).cuda()
     mean, rstd = g.new((F,)), g.new((F,))
     H.call("dgcnn_bn_finalize_f32", st.data_ptr(), F, float(n), BR.EPS, mean.data_ptr(), rstd.data_ptr())
@@ -168,7 +168,7 @@ def _reduce_apply(H, g, T, mu, rs, be, relu, dout, rpg, want_dT=True):
     ldd = F + 4
     dd = g.new((R, ldd))
     dd[:, :F] = torch.from_numpy(dout).cuda()
-    red = g.zeros((max(H.STAT_SLOTS, 32), 2, F), torch.float64)
+    red = g.zeros((max(H.stat_slots(), 32), 2, F), torch.float64)
     mb = g.zeros((2 * F + 1,), torch.int32)
     H.call("dgcnn_bn1_bwd_reduce_max_f32", Td.data_ptr(), R, F, *par, relu, dd.data_ptr(), ldd, red.data_ptr(), mb.data_ptr())
     res = {"sums": host(red).sum(0), "maxima": host(mb)[:2 * F].view(F32).reshape(2, F).copy()}
@@ -198,7 +198,7 @@ def test_bn1_bwd_reduce_max_and_apply_planes(dg, R, F, rpg, adv, nslots):
     replay, decoded planes within the split bound, per-group column sums against float64; adversarial dout (one element 1e4, the
     rest 1e-3); F = 1032: a second blockIdx.y.  The plane kernels use 32 slots whatever the runtime slot count is."""
     from dgcnn import _hip as H
-    old = H.STAT_SLOTS
+    old = H.stat_slots()
     H.set_stat_slots(nslots)
     try:
         rng = np.random.default_rng(R + F)

@@ -250,7 +250,7 @@ def test_one_cloud_tower_is_the_dense_kernels(dg):
     from dgcnn import _hip as H
     rng = np.random.default_rng(8)
     g = Guard()
-    nslots = H.STAT_SLOTS
+    nslots = H.stat_slots()
     # ---- k = 1
     R, F = 333, 64
     T = rng.normal(0.4, 2.0, (R, F)).astype(np.float32)

@@ -304,7 +304,7 @@ def test_one_cloud_k1_apply_is_the_dense_kernel(dg, F):
     g = Guard()
     Td, d1d, d2d = g.put(T), g.put(d1), g.put(d2)
     mud, rsd, bed = g.put(mu[0]), g.put(rs[0]), g.put(be)
-    dense_red = g.zeros((H.STAT_SLOTS, 2, F), torch.float64)
+    dense_red = g.zeros((H.stat_slots(), 2, F), torch.float64)
     dense_red[0].copy_(torch.from_numpy(s.red))                                 # the totals in slot 0, zeros elsewhere
     dd, dbd = g.new((R, F)), g.zeros((F,))
     H.call("dgcnn_bn_bwd_apply_f32", Td.data_ptr(), R, 1, F, mud.data_ptr(), rsd.data_ptr(), bed.data_ptr(), relu, d1d.data_ptr(), F,
@@ -330,7 +330,7 @@ def test_one_cloud_edge_apply_is_the_dense_kernel(dg):
     UVd, idxd = g.put(UV), g.put(idx)
     mud, rsd, bed = g.put(mu[0]), g.put(rs[0]), g.put(be)
     mxd, cnd, dmxd, dmnd = g.put(fw.mx), g.put(fw.packed), g.put(dmax), g.put(dmean)
-    dense_red = g.zeros((H.STAT_SLOTS, 2, F), torch.float64)
+    dense_red = g.zeros((H.stat_slots(), 2, F), torch.float64)
     dense_red[0].copy_(torch.from_numpy(s.red))
     dYd, dsd, dbd = g.new((R * k, F)), g.new((R, F)), g.zeros((F,))
     H.call("dgcnn_edge_bn_bwd_apply_f32", UVd[:, F:].data_ptr(), 2 * F, UVd.data_ptr(), 2 * F, idxd.data_ptr(), 1, R, k, F, mud.data_ptr(),
