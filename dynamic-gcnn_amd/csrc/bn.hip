@@ -2,7 +2,7 @@
 // model.py:52,71,100) + activation + reduce_max / reduce_mean over k (ops.py:56-57), and their
 // backward.  All HBM-bound: one float4 column-quad per lane so that a
 // wave reads whole 256-B feature rows, k rows per point streamed with k independent loads.
-#include "common.h"
+#include "bn_common.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -70,15 +70,6 @@ __global__ __launch_bounds__(FIN_COLS * FIN_LANES) void bn_bwd_finalize_kernel(d
   if (dbeta) dbeta[f] = (dbeta_beta != 0.f) ? (float)s + dbeta_beta * dbeta[f] : (float)s;
 }
 
-// One definition of xhat and z for every kernel (file is built with -ffp-contract=off), so the
-// max recomputed in the backward compares equal to the values it was taken over.
-__device__ __forceinline__ float bn_z(float y, float mu, float rs, float be, int relu, float& xh) {
-  xh = (y - mu) * rs;
-  float z = xh + be;
-  if (relu) z = fmaxf(z, 0.f);
-  return z;
-}
-
 // item -> (row, first channel).  FV (channel quads per row) is a power of two for every width of the
 // model, so the 64-bit division that used to dominate the k = 1 kernels becomes a shift.
 __device__ __forceinline__ void split_item(int64_t it, int FV, int fv_shift, int64_t& r, int& fq) {
@@ -94,21 +85,6 @@ __device__ __forceinline__ void split_item(int64_t it, int FV, int fv_shift, int
     fq = (int)(it % FV);
   }
 }
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-template <int V> struct Vec;
-template <> struct Vec<4> {
-  using T = float4;
-  static __device__ __forceinline__ void ld(const float* p, float (&o)[4]) {
-    const float4 v = *reinterpret_cast<const float4*>(p); o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
-  static __device__ __forceinline__ void st(float* p, const float (&o)[4]) {
-    *reinterpret_cast<float4*>(p) = make_float4(o[0], o[1], o[2], o[3]); }
-};
-template <> struct Vec<1> {
-  static __device__ __forceinline__ void ld(const float* p, float (&o)[1]) { o[0] = *p; }
-  static __device__ __forceinline__ void st(float* p, const float (&o)[1]) { *p = o[0]; }
-};
 
 // ---- where the k rows of a point come from ------------------------------------------------------------
 // G = false: the materialised tensor Y[(r*k + m)*F + f].
@@ -127,7 +103,6 @@ struct Src {
 #ifndef BN_NB
 #define BN_NB 4
 #endif
-constexpr int CNT_POS = 256;   // edge variants pack (#ties of the max) + CNT_POS * (#rows with z > 0) into cnt_out (k <= 255)
 constexpr int NB = BN_NB;    // rows in flight per lane
 
 template <int V, bool G>
@@ -232,9 +207,8 @@ __device__ __forceinline__ void kreduce_held(const Rows<4, true>& rows, int k, c
 #pragma unroll
     for (int h = 0; h < H; ++h) {
       const f32x2 y = f32x2{yv[2 * h], yv[2 * h + 1]} + u2[h];           // Rows::load's add
-      const f32x2 xh = (y - mu2[h]) * rs2[h];                            // bn_z, relu = 1
-      const f32x2 t = xh + be2[h];
-      z[m][h] = f32x2{fmaxf(t.x, 0.f), fmaxf(t.y, 0.f)};
+      f32x2 xh;
+      z[m][h] = bn_z(y, mu2[h], rs2[h], be2[h], 1, xh);
     }
   }
   f32x2 sm2[H];
@@ -305,7 +279,7 @@ __global__ __launch_bounds__(256) void bn_act_kreduce_kernel(
             cn[v] = gt ? 1.f : ((z == mx[v]) ? cn[v] + 1.f : cn[v]);   // ties share the max gradient (A.5)
             mx[v] = gt ? z : mx[v];
             sm[v] += z;
-            if (G) np[v] += (z > 0.f) ? (float)CNT_POS : 0.f;
+            if (G) np[v] += cnt_pos_term(z);
           }
         }
     }
@@ -427,7 +401,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(
         Vec<V>::ld(cnt_in + r * F + f, st.cnt);
         if (G) {
 #pragma unroll
-          for (int v = 0; v < V; ++v) st.cnt[v] -= (float)CNT_POS * floorf(st.cnt[v] * (1.0f / CNT_POS));
+          for (int v = 0; v < V; ++v) st.cnt[v] = cnt_ties(st.cnt[v]);
         }
       } else {
         k_pass_max<V, G>(rows, k, mu, rs, be, relu, st);
@@ -443,10 +417,8 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(
           for (int v = 0; v < V; ++v) {
             float xh;
             const float z = bn_z(yv[b][v], mu[v], rs[v], be[v], relu, xh);
-            float dz;
-            if (dmean) dz = ((z == st.mx[v]) ? dmx[v] / st.cnt[v] : 0.f) + dmn[v] * invk;
-            else dz = dmx[v];
-            if (relu && !(z > 0.f)) dz = 0.f;
+            const float d = dmean ? bn_edge_dout(z, st.mx[v], dmx[v] / st.cnt[v], dmn[v] * invk) : dmx[v];
+            const float dz = bn_dz_row(z, d, relu);
             s0[v] += dz;
             s1[v] += dz * xh;
           }
@@ -503,7 +475,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
         Vec<V>::ld(cnt_in + r * F + f, st.cnt);
         if (G) {
 #pragma unroll
-          for (int v = 0; v < V; ++v) st.cnt[v] -= (float)CNT_POS * floorf(st.cnt[v] * (1.0f / CNT_POS));
+          for (int v = 0; v < V; ++v) st.cnt[v] = cnt_ties(st.cnt[v]);
         }
       } else {
         k_pass_max<V, G>(rows, k, mu, rs, be, relu, st);
@@ -520,11 +492,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
           for (int v = 0; v < V; ++v) {
             float xh;
             const float z = bn_z(yv[b][v], mu[v], rs[v], be[v], relu, xh);
-            float dz;
-            if (dmean) dz = ((z == st.mx[v]) ? dmx[v] / st.cnt[v] : 0.f) + dmn[v] * invk;
-            else dz = dmx[v];
-            if (relu && !(z > 0.f)) dz = 0.f;
-            o[v] = rs[v] * (dz - c1[v] - xh * c2[v]);
+            const float d = dmean ? bn_edge_dout(z, st.mx[v], dmx[v] / st.cnt[v], dmn[v] * invk) : dmx[v];
+            const float dz = bn_dz_row(z, d, relu);
+            o[v] = bn_dy(rs[v], dz, c1[v], xh, c2[v]);
             if (round_dy) o[v] = round_bf16_rne(o[v]);
             acc[v] += o[v];
           }
@@ -583,7 +553,7 @@ __device__ __forceinline__ void edge_bwd_apply_wgrad_body(
     Vec<V>::ld(mx_in + r * ldmx + f, st.mx);
     Vec<V>::ld(cnt_in + r * F + f, st.cnt);
 #pragma unroll
-    for (int v = 0; v < V; ++v) st.cnt[v] -= (float)CNT_POS * floorf(st.cnt[v] * (1.0f / CNT_POS));
+    for (int v = 0; v < V; ++v) st.cnt[v] = cnt_ties(st.cnt[v]);
     float xi[CC];
 #pragma unroll
     for (int c = 0; c < CC; ++c) xi[c] = (EXACT || c < C) ? x[r * ldx + c] : 0.f;
@@ -634,9 +604,10 @@ __device__ __forceinline__ void edge_bwd_apply_wgrad_body(
             for (int v = 0; v < V; ++v) {
               float xh;
               const float z = bn_z(yv[b][v], mu[v], rs[v], be[v], 1, xh);
+              // bn_common.h:bn_dz_edge with relu = 1, spelled out: the call moves this kernel's registers (profiles/bn_common/isa_compare.txt)
               float dz = ((z == st.mx[v]) ? q1[v] : 0.f) + q2[v];
               if (!(z > 0.f)) dz = 0.f;
-              const float o = rs[v] * (dz - c1[v] - xh * c2[v]);
+              const float o = bn_dy(rs[v], dz, c1[v], xh, c2[v]);
               acc[v] += o;
 #pragma unroll
               for (int c = 0; c < CC; ++c) wd[c][v] = fmaf(dx[b][c], o, wd[c][v]);
@@ -661,9 +632,7 @@ __device__ __forceinline__ void edge_bwd_apply_wgrad_body(
             for (int v = 0; v < V; ++v) {
               float xh;
               const float z = bn_z(yv[b][v], mu[v], rs[v], be[v], 1, xh);
-              float dz = ((z == st.mx[v]) ? dmx[v] / st.cnt[v] : 0.f) + dmn[v] * invk;
-              if (!(z > 0.f)) dz = 0.f;
-              const float o = rs[v] * (dz - c1[v] - xh * c2[v]);
+              const float o = bn_dy(rs[v], bn_dz_edge(z, st.mx[v], dmx[v] / st.cnt[v], dmn[v] * invk, 1), c1[v], xh, c2[v]);
               acc[v] += o;
 #pragma unroll
               for (int c = 0; c < CC; ++c) wd[c][v] = fmaf(dx[c], o, wd[c][v]);
@@ -798,7 +767,7 @@ __global__ __launch_bounds__(256) void bn1_act_kernel(const float* __restrict__ 
       if (rr < R) {
         float z[4];
 #pragma unroll
-        for (int v = 0; v < 4; ++v) { float xh; z[v] = bn_z(y[b][v], mu[v], rs[v], be[v], relu, xh); }
+        for (int v = 0; v < 4; ++v) z[v] = bn_z(y[b][v], mu[v], rs[v], be[v], relu);
         if (drop_seed) {
 #pragma unroll
           for (int v = 0; v < 4; ++v) z[v] = dropout_keeps(dseed, (uint64_t)(rr * F + m.f + v), dthr) ? z[v] * dscale : 0.f;
@@ -864,8 +833,8 @@ __global__ __launch_bounds__(256) void bn1_bwd_kernel(const float* T, int64_t R,
             const float z = bn_z(y[b][v], mu[v], rs[v], be[v], relu, xh);
             float dz = d[b][v];
             if (drop_seed) dz = dropout_keeps(dseed, (uint64_t)(rr * F + m.f + v), dthr) ? dz * dscale : 0.f;
-            if (relu && !(z > 0.f)) dz = 0.f;
-            if (APPLY) o[v] = rs[v] * (dz - c1[v] - xh * c2[v]);
+            dz = bn_dz_row(z, dz, relu);
+            if (APPLY) o[v] = bn_dy(rs[v], dz, c1[v], xh, c2[v]);
             else { s0[v] += dz; s1[v] += dz * xh; }
           }
           if (APPLY) {
@@ -927,7 +896,7 @@ __global__ __launch_bounds__(256) void bn1_act_class_kernel(const float* __restr
       if (rr < R) {
         float z[4];
 #pragma unroll
-        for (int v = 0; v < 4; ++v) { float xh; z[v] = bn_z(y[b][v], mu[v], rs[v], be[v], relu, xh); }
+        for (int v = 0; v < 4; ++v) z[v] = bn_z(y[b][v], mu[v], rs[v], be[v], relu);
 #pragma unroll
         for (int v = 0; v < 4; ++v) z[v] = dropout_keeps(dseed, (uint64_t)(rr * F + f + v), dthr) ? z[v] * dscale : 0.f;
         Vec<4>::st(out + rr * ldo + f, z);
@@ -989,7 +958,7 @@ __global__ __launch_bounds__(256) void bn_softmax_xent_kernel(const float* __res
   const float inv_rows = 1.0f / (float)rows;
   for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += (int64_t)gridDim.x * blockDim.x) {
     float* z = fin + r * ncls;
-    for (int c = 0; c < ncls; ++c) { float xh; z[c] = bn_z(Y[r * ncls + c], smu[c], srs[c], beta[c], relu, xh); }
+    for (int c = 0; c < ncls; ++c) z[c] = bn_z(Y[r * ncls + c], smu[c], srs[c], beta[c], relu);
     const int lab = labels ? labels[r] : -1;
     const float w = weight ? weight[r] : 1.f;
     softmax_xent_row(z, ncls, lab, w, inv_rows, softmax ? softmax + r * ncls : nullptr,
@@ -1084,9 +1053,7 @@ __global__ __launch_bounds__(256) void bn1_bwd_class_kernel(const float* T, int6
           for (int k = 0; k < NC; ++k) {
             float xh;
             const float z = bn_z(a[b][k], muf[k], rsf[k], bef[k], relu_f, xh);
-            float dz = g[b][k];
-            if (relu_f && !(z > 0.f)) dz = 0.f;
-            a[b][k] = rsf[k] * (dz - c1f[k] - xh * c2f[k]);
+            a[b][k] = bn_dy(rsf[k], bn_dz_row(z, g[b][k], relu_f), c1f[k], xh, c2f[k]);
           }
           if ((threadIdx.x & 63) == 0) {
 #pragma unroll
@@ -1101,8 +1068,8 @@ __global__ __launch_bounds__(256) void bn1_bwd_class_kernel(const float* T, int6
           const float z = bn_z(y[b][v], mu[v], rs[v], be[v], relu, xh);
           float dz = d[v];
           dz = dropout_keeps(dseed, (uint64_t)(rr * F + m.f + v), dthr) ? dz * dscale : 0.f;
-          if (relu && !(z > 0.f)) dz = 0.f;
-          if (APPLY) o[v] = rs[v] * (dz - c1[v] - xh * c2[v]);
+          if (relu && !(z > 0.f)) dz = 0.f;        // bn_common.h:bn_dz_row, spelled out (profiles/bn_common/isa_compare.txt)
+          if (APPLY) o[v] = bn_dy(rs[v], dz, c1[v], xh, c2[v]);
           else { s0[v] += dz; s1[v] += dz * xh; }
         }
         if (APPLY) Vec<4>::st(dT + rr * F + m.f, o);
@@ -1136,7 +1103,7 @@ __global__ __launch_bounds__(256) void edge_bwd_reduce_points_kernel(
       Vec<4>::ld(dmax + r * lddmax + m.f, d); Vec<4>::ld(dmean + r * lddmean + m.f, e);
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
-        const float npos = floorf(c[v] * (1.0f / CNT_POS));
+        const float npos = cnt_npos(c[v]);
         const float g1 = (a[v] > 0.f) ? d[v] : 0.f;
         const float g2 = e[v] * invk;
         s0[v] += g1 + g2 * npos;
@@ -1207,7 +1174,7 @@ int check_edge(const char* what, const float* V, int64_t ldv, const float* U, in
   DG_REQUIRE(F % 4 == 0, DGCNN_EUNSUP, "%s: F must be a multiple of 4 (got %d)", what, F);
   DG_REQUIRE((int64_t)B * N * k < (1ll << 31), DGCNN_EUNSUP, "%s: B*N*k >= 2^31", what);
   DG_REQUIRE(k < CNT_POS, DGCNN_EUNSUP, "%s: k must be < %d", what, CNT_POS);
-  DG_REQUIRE(N < (1 << 24) && ldv < (1 << 24) && (int64_t)N * ldv < (1ll << 32), DGCNN_EUNSUP,
+  DG_REQUIRE(row_offset24_ok(N, ldv), DGCNN_EUNSUP,
              "%s: N * ldv must be < 2^32 elements (32-bit row offsets inside a cloud)", what);
   DG_REQUIRE(a16(V) && a16(U) && ldv % 4 == 0 && ldu % 4 == 0 && ldv >= F && ldu >= F, DGCNN_EINVAL,
              "%s: V, U must be 16-byte aligned with leading dimensions %% 4 == 0", what);
@@ -1579,9 +1546,9 @@ extern "C" int dgcnn_edge_bn_bwd_apply_wgrad_f32(const float* V, int64_t ldv, co
   const size_t need = (size_t)grid * 2 * C * F * sizeof(float);
   DG_REQUIRE(ws_bytes >= need, DGCNN_ENOSPC, "dgcnn_edge_bn_bwd_apply_wgrad_f32: workspace too small (%zu < %zu)", ws_bytes, need);
   const size_t shb = (size_t)(256 / FV) * 2 * 4 * F * sizeof(float);
-  // the exact-width form takes row offsets inside a cloud as unsigned 32-bit element counts from one 24-bit multiply: index < N < 2^24,
-  // ldx < 2^24 and N * ldx < 2^32 (N * ldv < 2^32: check_edge); anything else keeps the run-time-C kernel and its 64-bit x offsets
-  const bool exact = edge_valu_on() && (C == 3 || C == 4) && ldx >= C && ldx < (1 << 24) && (int64_t)N * ldx < (1ll << 32);
+  // the exact-width form takes row offsets inside a cloud as unsigned 32-bit element counts from one 24-bit multiply: x must keep
+  // row_offset24's contract as V does (check_edge); anything else keeps the run-time-C kernel and its 64-bit x offsets
+  const bool exact = edge_valu_on() && (C == 3 || C == 4) && ldx >= C && row_offset24_ok(N, ldx);
   const Src src = edge_src(V, ldv, U, ldu, idx, N);
   float* part = reinterpret_cast<float*>(ws);
   if (exact && C == 3)

@@ -82,6 +82,32 @@ void launch_gemm_x3(int asrc, int bsrc, void* pv, hipStream_t st, int bn, int np
 
 }  // namespace dg
 
+// ---- the small row helpers of the streaming kernels ---------------------------------------------------------------------
+// grid of a grid-stride kernel over n items: blocks of bs threads, at most 65536 of them
+static inline unsigned grid1d(int64_t n, int bs = 256) {
+  int64_t g = dg::cdiv(n, bs);
+  if (g > 65536) g = 65536;
+  if (g < 1) g = 1;
+  return (unsigned)g;
+}
+
+#define GRID_STRIDE(i, n) \
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
+
+__device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+
+// packed towers (cloud b = rows [seg_off[b], seg_off[b + 1])): the cloud that holds row r, the largest b in [0, nseg) with
+// seg_off[b] <= r
+__device__ __forceinline__ int cloud_of_row(const int32_t* __restrict__ seg_off, int nseg, int r) {
+  int lo = 0, hi = nseg - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (seg_off[mid] <= r) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
 // ---- dropout (tf.nn.dropout(net, 0.7), model.py:91): counter-based mask, element i of the flattened tensor is kept iff
 // mix32(seed * K + i) < keep * 2^32; the backward regenerates the mask from the same seed (misc.hip, bn.hip)
 __device__ __forceinline__ uint32_t mix32(uint64_t z) {   // splitmix64 finaliser
@@ -100,11 +126,12 @@ __device__ __forceinline__ uint32_t dropout_threshold(float keep) {
 }
 
 // ---- element offset of a gathered row: j * ld in ONE full-rate multiply (v_mul_u32_u24) -- the only caller of __umul24.
-// Contract (the host checks of the gathering entries: check_edge, check_seg_edge, dgcnn_edge_gather_add_f32): j < 2^24, ld < 2^24,
-// j * ld < 2^32.  The product may be 2^31 or more, and HIP declares __umul24 as returning int: the UNSIGNED result must enter the
+// Contract (row_offset24_ok, which every entry that launches a gathering kernel asks on the host): j < rows < 2^24, ld < 2^24,
+// rows * ld < 2^32.  The product may be 2^31 or more, and HIP declares __umul24 as returning int: the UNSIGNED result must enter the
 // address zero-extended (`p + row_offset24(j, ld)`, or through an `unsigned` variable).  Never cast it to int or add it to a signed
 // offset first -- a sign-extended product addresses 2^32 elements before the intended row.
 __device__ __forceinline__ unsigned row_offset24(unsigned j, unsigned ld) { return (unsigned)__umul24(j, ld); }
+static inline bool row_offset24_ok(int64_t rows, int64_t ld) { return rows < (1 << 24) && ld < (1 << 24) && rows * ld < (1ll << 32); }
 
 // fp32 -> the nearest bf16 value (ties to even), kept as fp32 bits.  The carry of the rounding add would run a NaN whose upper
 // mantissa bits are all ones into the exponent and sign (0x7fffffff -> -0.0): a NaN stays a (quiet) NaN of the same sign instead,

@@ -17,15 +17,15 @@
 //
 // Backward (edge_mlp_bf16_bwd_kernel), same tiles of whole points, y recomputed once more by the same instruction sequence:
 //     dz   = [z == max_i] dmax_i / ties_i + dmean_i / k, zero where z <= 0;  dY = rstd (dz - c1 - xhat c2), rounded to bf16 (RNE)
-//            -- the expressions of bn.hip:bn_bwd_apply_kernel, c1 / c2 from the reduce pass over the POINT outputs
-//            (bn.hip:edge_bwd_reduce_points_kernel: PASS 1 packs #ties + 256 #positives exactly as the fp32 edge kernels do);
+//            -- bn_common.h's bn_z / bn_dz_edge / bn_dy, shared with bn.hip:bn_bwd_apply_kernel; c1 / c2 from the reduce pass over
+//            the POINT outputs (bn.hip:edge_bwd_reduce_points_kernel reads the count PASS 1 packs with cnt_pack);
 //     dW0 += E^T dY   on the matrix pipe: both operands are read from their row-major LDS tiles with ds_read_b64_tr_b16 (the
 //            reduction runs over the 128 edge rows of the tile), accumulated in registers over all tiles of the workgroup,
 //            one partial (2C, F) per workgroup, added up in fixed order by reduce_partials_kernel;
 //     dYsum_i = sum_m dY (fp32 sum of the rounded values, m ascending) -> (B N, F);  dY itself leaves as bf16 (B N k, F) -- half
 //            the bytes, the same values -- for the transposed-adjacency sum (dgcnn_edge_gather_sum_bf16).
 // Neither E (2.7 GB per layer at configs[2]) nor y nor an fp32 dY is written; the separate 5.2-M-row weight-gradient GEMM is gone.
-#include "common.h"
+#include "bn_common.h"
 #include <math.h>
 
 namespace {
@@ -45,17 +45,12 @@ struct EdgeP {
   float* mx; int64_t ldmx; float* mn; int64_t ldmn; float* cnt;
   int pack;                              // PASS 1: cnt = #ties + CNT_POS * #(z > 0) (what the fused backward reads) instead of #ties
 };
-constexpr int CNT_POS = 256;             // (bn.hip)
 
 __device__ __forceinline__ unsigned pk_bf16(float lo, float hi) {
   unsigned r;
   asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
   return r;
 }
-
-// same expressions as bn.hip:bn_z (the library is built with -ffp-contract=off): the backward recomputes z from the materialised
-// y and compares it with the maximum taken here
-__device__ __forceinline__ float bn_z1(float y, float mu, float rs, float be) { return fmaxf((y - mu) * rs + be, 0.f); }
 
 // Gather + round one tile of E into LDS (row stride S = 2 K + 16 bytes): wave w stages rows 32 w .. 32 w + 31.  POINTS: the tile
 // holds P = floor(128 / k) whole points (rows past P k and points past the end are zero rows), else 128 consecutive edge rows.
@@ -218,7 +213,7 @@ __global__ __launch_bounds__(256) void edge_mlp_bf16_kernel(EdgeP p) {
           const float mu = p.mean[c], rs = p.rstd[c], be = p.beta[c];
           float mx = -INFINITY, sm = 0.f, cn = 0.f, np = 0.f;
           for (int m = 0; m < k; ++m) {
-            const float z = bn_z1(Yt[(pi * k + m) * FP + c], mu, rs, be);
+            const float z = bn_z(Yt[(pi * k + m) * FP + c], mu, rs, be, 1);
             const bool gt = z > mx;
             cn = gt ? 1.f : ((z == mx) ? cn + 1.f : cn);                // ties share the max gradient
             mx = gt ? z : mx;
@@ -227,7 +222,8 @@ __global__ __launch_bounds__(256) void edge_mlp_bf16_kernel(EdgeP p) {
           }
           p.mx[gp * p.ldmx + c] = mx;
           p.mn[gp * p.ldmn + c] = sm * invk;
-          if (p.cnt) p.cnt[gp * F + c] = p.pack ? cn + (float)CNT_POS * np : cn;
+          const float packed = cnt_pack(cn, np);
+          if (p.cnt) p.cnt[gp * F + c] = p.pack ? packed : cn;
         }
       }
       __syncthreads();
@@ -387,8 +383,7 @@ __global__ __launch_bounds__(512) void edge_mlp_bf16_bwd_kernel(EdgeBwdP bp) {
         if (it < P * F) {
           const int pi = it / F;
           const bool ok = tile * P + pi < R;
-          float cn = vc[i];
-          cn -= (float)CNT_POS * floorf(cn * (1.0f / CNT_POS));               // #ties of the max
+          const float cn = cnt_ties(vc[i]);
           v[it] = ok ? make_float4(vm[i], vdx[i] / cn, vdn[i] * invk, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
       }
@@ -518,12 +513,10 @@ __global__ __launch_bounds__(512) void edge_mlp_bf16_bwd_kernel(EdgeBwdP bp) {
         o[j] = 0.f;
         if (valid) {
           const float y = acc[j][q];
-          const float xh = (y - mu[j]) * rs[j];
-          const float z = fmaxf(xh + be[j], 0.f);
-          const float4 v4 = pv[pi * F + c];
-          float dz = ((z == v4.x) ? v4.y : 0.f) + v4.z;
-          if (!(z > 0.f)) dz = 0.f;
-          o[j] = rs[j] * (dz - c1[j] - xh * c2[j]);
+          float xh;
+          const float z = bn_z(y, mu[j], rs[j], be[j], 1, xh);
+          const float4 v4 = pv[pi * F + c];                 // (max, dmax / ties, dmean / k) of the point: commit_vec
+          o[j] = bn_dy(rs[j], bn_dz_edge(z, v4.x, v4.y, v4.z, 1), c1[j], xh, c2[j]);
         }
       }
 #pragma unroll

@@ -84,11 +84,9 @@ __device__ __forceinline__ bool block_tile(const GemmP& p, int& mt, int& nt, int
   return mt < p.mtiles;
 }
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 #define LD4(ptr) ld4(ptr)
 
 __device__ __forceinline__ float4 sub4(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
-__device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
 
 // ---- shared epilogue.  C/D layout of 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
 // WR = wave rows of the block (each wave owns BM/WR rows as TM 32-row tiles), NTH = threads taking part.

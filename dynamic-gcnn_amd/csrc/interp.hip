@@ -14,18 +14,6 @@ constexpr int IT = 256;          // threads of every block here
 constexpr int FWD_E = 2048;      // (row, neighbour) entries a forward block keeps in LDS: rows per block <= FWD_E / k
 constexpr int BWD_U = 8;         // dy rows the backward gather keeps in flight per thread
 
-inline unsigned grid1d(int64_t n, int bs = IT) {
-  int64_t g = dg::cdiv(n, bs);
-  if (g > 65536) g = 65536;
-  if (g < 1) g = 1;
-  return (unsigned)g;
-}
-
-#define GRID_STRIDE(i, n) \
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-
 // candidate row of entry e = i * k + m: dense towers (M > 0) add the cloud's first row to the cloud-local index
 __device__ __forceinline__ int32_t cand_row(const int32_t* __restrict__ idx, unsigned e, unsigned k, unsigned M, unsigned N) {
   const int32_t j = idx[e];
@@ -278,12 +266,12 @@ extern "C" int dgcnn_interp_bwd_f32(const float* dy, int64_t lddy, const int32_t
   int32_t* rev = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(cnt) + pad256(4 * (int64_t)p_rows));
   int32_t* srt = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(rev) + pad256(4 * (int64_t)total));
   if (int rc = dg::memset_async(cnt, 0, sizeof(int32_t) * (size_t)p_rows, ST)) return rc;
-  dg::launch(interp_count_kernel, dim3(grid1d(total)), dim3(IT), 0, ST, idx, total, (unsigned)k, (unsigned)M, (unsigned)N, cnt, srt);
+  dg::launch(interp_count_kernel, dim3(grid1d(total, IT)), dim3(IT), 0, ST, idx, total, (unsigned)k, (unsigned)M, (unsigned)N, cnt, srt);
   dg::launch(interp_scan_kernel, dim3(1), dim3(1024), 0, ST, cnt, p_rows, off);
-  dg::launch(interp_fill_kernel, dim3(grid1d(total)), dim3(IT), 0, ST, idx, total, (unsigned)k, (unsigned)M, (unsigned)N, off, srt, rev);
-  dg::launch(interp_rank_kernel, dim3(grid1d(total)), dim3(IT), 0, ST, idx, total, (unsigned)k, (unsigned)M, (unsigned)N, off, rev, srt);
+  dg::launch(interp_fill_kernel, dim3(grid1d(total, IT)), dim3(IT), 0, ST, idx, total, (unsigned)k, (unsigned)M, (unsigned)N, off, srt, rev);
+  dg::launch(interp_rank_kernel, dim3(grid1d(total, IT)), dim3(IT), 0, ST, idx, total, (unsigned)k, (unsigned)M, (unsigned)N, off, rev, srt);
   const int FV = F / 4;
-  dg::launch(interp_bwd_gather_kernel, dim3(grid1d((int64_t)p_rows * FV)), dim3(IT), 0, ST, dy, lddy, a, off, srt, (int64_t)p_rows,
+  dg::launch(interp_bwd_gather_kernel, dim3(grid1d((int64_t)p_rows * FV, IT)), dim3(IT), 0, ST, dy, lddy, a, off, srt, (int64_t)p_rows,
              (unsigned)k, FV, dfeat, lddf, beta);
   return dg::check_launch(who);
 }

@@ -9,16 +9,6 @@
 
 namespace {
 
-inline unsigned grid1d(int64_t n, int bs = 256) {
-  int64_t g = dg::cdiv(n, bs);
-  if (g > 65536) g = 65536;
-  if (g < 1) g = 1;
-  return (unsigned)g;
-}
-
-#define GRID_STRIDE(i, n) \
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
-
 __global__ void edge_gather_kernel(const float* __restrict__ x, int64_t ldx, const int32_t* __restrict__ idx,
                                    int N, int C, int k, int64_t total, float* __restrict__ E) {
   GRID_STRIDE(i, total) {
@@ -396,7 +386,7 @@ __global__ __launch_bounds__(64 * RG) void group_colsum_kernel(const float* __re
 
 __global__ void dropout_kernel(const float* x, float* y, int64_t n, float keep, uint64_t seed) {
   const float scale = 1.0f / keep;
-  const uint32_t thr = (keep >= 1.f) ? 0xffffffffu : (uint32_t)((double)keep * 4294967296.0);
+  const uint32_t thr = dropout_threshold(keep);
   GRID_STRIDE(i, n) {
     const uint32_t r = mix32(seed * 0xD1342543DE82EF95ull + (uint64_t)i);
     y[i] = (r < thr) ? x[i] * scale : 0.f;
@@ -406,7 +396,7 @@ __global__ void dropout_kernel(const float* x, float* y, int64_t n, float keep, 
 // the same with the seed read from device memory: a captured HIP graph replays with a new mask every step
 __global__ void dropout_dev_kernel(const float* x, float* y, int64_t n, float keep, const uint64_t* __restrict__ seed_dev) {
   const float scale = 1.0f / keep;
-  const uint32_t thr = (keep >= 1.f) ? 0xffffffffu : (uint32_t)((double)keep * 4294967296.0);
+  const uint32_t thr = dropout_threshold(keep);
   const uint64_t seed = *seed_dev;
   GRID_STRIDE(i, n) {
     const uint32_t r = mix32(seed * 0xD1342543DE82EF95ull + (uint64_t)i);
@@ -577,7 +567,7 @@ extern "C" int dgcnn_edge_gather_add_f32(const float* V, int64_t ldv, const floa
   DG_REQUIRE(F % 4 == 0 && F <= 1024, DGCNN_EUNSUP, "dgcnn_edge_gather_add_f32: F must be a multiple of 4, <= 1024 (got %d)", F);
   const int64_t rows = (int64_t)B * N * k;
   DG_REQUIRE(rows < (1ll << 31), DGCNN_EUNSUP, "dgcnn_edge_gather_add_f32: B*N*k >= 2^31");
-  DG_REQUIRE(N < (1 << 24) && ldv < (1 << 24) && (int64_t)N * ldv < (1ll << 32), DGCNN_EUNSUP,
+  DG_REQUIRE(row_offset24_ok(N, ldv), DGCNN_EUNSUP,
              "dgcnn_edge_gather_add_f32: N * ldv must be < 2^32 elements (32-bit row offsets inside a cloud)");
   auto a16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   DG_REQUIRE(a16(V) && a16(U) && (!Y || a16(Y)) && ldv % 4 == 0 && ldu % 4 == 0 && ldv >= F && ldu >= F, DGCNN_EINVAL,

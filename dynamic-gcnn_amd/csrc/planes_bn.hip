@@ -10,20 +10,14 @@
 //   scales    dgcnn_param_scales_f32         one pass over the parameter bucket: scale of every activation plane set
 //                                            (|z| <= sqrt(rows - 1) + max |beta| for ANY batch-normalised tensor) and of the weights
 // Tiles: 64 rows x 16 channel octets per 256-thread block, slots transposed through LDS (planes_common.h) so that every wave
-// store is 1 KiB contiguous.
+// store is 1 KiB contiguous.  The element arithmetic (xhat, z, dz, dY) is bn_common.h's, shared with bn.hip.
 #include "planes_common.h"
+#include "bn_common.h"
 #include <stdlib.h>
 
 namespace {
 
 constexpr int SLOTS = DGCNN_STAT_SLOTS;
-
-__device__ __forceinline__ float bn_z(float y, float mu, float rs, float be, int relu, float& xh) {   // == bn.hip:bn_z
-  xh = (y - mu) * rs;
-  float z = xh + be;
-  if (relu) z = fmaxf(z, 0.f);
-  return z;
-}
 
 __device__ __forceinline__ void ld8(const float* p, float (&v)[8]) {
   const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
@@ -101,7 +95,7 @@ __global__ __launch_bounds__(256) void bn_act_planes_kernel(const float* __restr
         float mu[8], rs[8], be[8];
         ld8(mean + c, mu); ld8(rstd + c, rs); ld8(beta + c, be);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) { float xh; z[e] = bn_z(y[u][e], mu[e], rs[e], be[e], relu, xh); }
+        for (int e = 0; e < 8; ++e) z[e] = bn_z(y[u][e], mu[e], rs[e], be[e], relu);
         if (out) st8(out + r * ldo + c, z);
         if (out2) st8(out2 + r * ldo2 + c, z);
       }
@@ -152,8 +146,7 @@ __global__ __launch_bounds__(256) void bn1_bwd_reduce_max_kernel(const float* __
           for (int v = 0; v < 4; ++v) {
             float xh;
             const float z = bn_z(yy[v], mu[v], rs[v], be[v], relu, xh);
-            float dz = dd[v];
-            if (relu && !(z > 0.f)) dz = 0.f;
+            const float dz = bn_dz_row(z, dd[v], relu);
             s0[v] += dz; s1[v] += dz * xh;
             a0[v] = fmaxf(a0[v], fabsf(dz)); a1[v] = fmaxf(a1[v], fabsf(xh));
           }
@@ -251,9 +244,7 @@ __global__ __launch_bounds__(256) void bn1_bwd_apply_planes_kernel(const float* 
         for (int e = 0; e < 8; ++e) {
           float xh;
           const float z = bn_z(y[u][e], mu[e], rs[e], be[e], relu, xh);
-          float dz = d[u][e];
-          if (relu && !(z > 0.f)) dz = 0.f;
-          o8[e] = rs[e] * (dz - c1[e] - xh * c2[e]);
+          o8[e] = bn_dy(rs[e], bn_dz_row(z, d[u][e], relu), c1[e], xh, c2[e]);
           gacc[u][e] += o8[e];
         }
         if (dT) st8(dT + r * F + c, o8);

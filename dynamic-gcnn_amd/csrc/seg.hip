@@ -5,43 +5,13 @@
 // chip as evenly as a dense tower does.  A chunk is cut at the cloud boundaries inside it; every piece is reduced by the
 // workgroup (registers per wave, then LDS across the waves) before ONE result per (piece, column) leaves it.
 #include "gemm_common.h"
+#include "bn_common.h"   // Vec
 
 namespace {
 
 constexpr int SEG_CHUNK = 64;   // rows of the tower per workgroup
 constexpr int SEG_WAVES = 4;    // waves per workgroup; wave w owns rows w, w + 4, ... of a piece (ascending: first arg-max / fixed order)
 constexpr int SEG_UNROLL = 4;   // independent row loads in flight per lane
-
-inline unsigned grid1d(int64_t n, int bs = 256) {
-  int64_t g = dg::cdiv(n, bs);
-  if (g > 65536) g = 65536;
-  if (g < 1) g = 1;
-  return (unsigned)g;
-}
-
-#define GRID_STRIDE(i, n) \
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
-
-// the cloud that holds row r: the largest b in [0, nseg) with seg_off[b] <= r
-__device__ __forceinline__ int cloud_of_row(const int32_t* __restrict__ seg_off, int nseg, int r) {
-  int lo = 0, hi = nseg - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (seg_off[mid] <= r) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-template <int VW> struct RowVec;
-template <> struct RowVec<4> {
-  static __device__ __forceinline__ void load(const float* p, float (&v)[4]) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  }
-};
-template <> struct RowVec<1> {
-  static __device__ __forceinline__ void load(const float* p, float (&v)[1]) { v[0] = *p; }
-};
 
 // Per-cloud column maximum as keys (gemm_common.h: f32_ordered(value) << 32 | ~row-in-cloud): grid = (row chunks, column blocks of
 // 64 * VW), lane = VW adjacent columns (one float4 per row when VW = 4: a wave reads 1 KiB of a row per load).
@@ -71,7 +41,7 @@ __global__ __launch_bounds__(64 * SEG_WAVES) void colmax_seg_kernel(const float*
       for (; i + (SEG_UNROLL - 1) * SEG_WAVES < pe; i += SEG_UNROLL * SEG_WAVES) {
         float v[SEG_UNROLL][VW];
 #pragma unroll
-        for (int u = 0; u < SEG_UNROLL; ++u) RowVec<VW>::load(p + (int64_t)(i + u * SEG_WAVES) * ldx, v[u]);
+        for (int u = 0; u < SEG_UNROLL; ++u) Vec<VW>::ld(p + (int64_t)(i + u * SEG_WAVES) * ldx, v[u]);
 #pragma unroll
         for (int u = 0; u < SEG_UNROLL; ++u)
 #pragma unroll
@@ -80,7 +50,7 @@ __global__ __launch_bounds__(64 * SEG_WAVES) void colmax_seg_kernel(const float*
       }
       for (; i < pe; i += SEG_WAVES) {
         float v[VW];
-        RowVec<VW>::load(p + (int64_t)i * ldx, v);
+        Vec<VW>::ld(p + (int64_t)i * ldx, v);
 #pragma unroll
         for (int q = 0; q < VW; ++q)
           if (v[q] > best[q] || (v[q] == best[q] && bi[q] == 0x7fffffff)) { best[q] = v[q]; bi[q] = i; }
@@ -154,7 +124,7 @@ __global__ __launch_bounds__(64 * SEG_WAVES) void seg_colsum_partial_kernel(cons
       for (; i + (SEG_UNROLL - 1) * SEG_WAVES < pe; i += SEG_UNROLL * SEG_WAVES) {
         float v[SEG_UNROLL][VW];
 #pragma unroll
-        for (int u = 0; u < SEG_UNROLL; ++u) RowVec<VW>::load(p + (int64_t)(i + u * SEG_WAVES) * ldx, v[u]);
+        for (int u = 0; u < SEG_UNROLL; ++u) Vec<VW>::ld(p + (int64_t)(i + u * SEG_WAVES) * ldx, v[u]);
 #pragma unroll
         for (int u = 0; u < SEG_UNROLL; ++u)
 #pragma unroll
@@ -162,7 +132,7 @@ __global__ __launch_bounds__(64 * SEG_WAVES) void seg_colsum_partial_kernel(cons
       }
       for (; i < pe; i += SEG_WAVES) {
         float v[VW];
-        RowVec<VW>::load(p + (int64_t)i * ldx, v);
+        Vec<VW>::ld(p + (int64_t)i * ldx, v);
 #pragma unroll
         for (int q = 0; q < VW; ++q) s[q] += v[q];
       }

@@ -10,62 +10,18 @@
 //
 // The backward (second half of the file) takes its per-cloud sums red = double[nseg][2][F] (sum dz, sum dz * xhat) by the same two
 // stages, turns them into the float tables c1 / c2 = red / (n_b k) and applies dY = rstd_g ((dz - c1_g) - xhat c2_g) through the
-// row -> cloud map; the arithmetic of bn.hip's backward kernels, operation for operation.
+// row -> cloud map.
+//
+// The element arithmetic (xhat, z, the packed count, dz, dY) is bn_common.h's, shared with bn.hip's dense kernels: a one-cloud tower
+// gives their outputs bit for bit.
 #include "gemm_common.h"
+#include "bn_common.h"
 
 namespace {
 
 constexpr int SEG_CHUNK = 64;   // rows of the tower per workgroup (stage 1 of both statistics kernels)
 constexpr int SEG_WAVES = 4;    // k = 1 statistics: wave w owns rows w, w + 4, ... of a piece
 constexpr int SEG_UNROLL = 4;   // independent row loads in flight per lane
-
-inline unsigned grid1d(int64_t n, int bs = 256) {
-  int64_t g = dg::cdiv(n, bs);
-  if (g > 65536) g = 65536;
-  if (g < 1) g = 1;
-  return (unsigned)g;
-}
-
-#define GRID_STRIDE(i, n) \
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
-
-// the cloud that holds row r: the largest b in [0, nseg) with seg_off[b] <= r
-__device__ __forceinline__ int cloud_of_row(const int32_t* __restrict__ seg_off, int nseg, int r) {
-  int lo = 0, hi = nseg - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (seg_off[mid] <= r) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-// bn.hip's definition of xhat and z, operation for operation (the library is built with -ffp-contract=off): a one-cloud tower
-// gives the dense kernels' outputs bit for bit
-__device__ __forceinline__ float bn_z(float y, float mu, float rs, float be, int relu) {
-  const float xh = (y - mu) * rs;
-  float z = xh + be;
-  if (relu) z = fmaxf(z, 0.f);
-  return z;
-}
-
-__device__ __forceinline__ float bn_z(float y, float mu, float rs, float be, int relu, float& xh) {
-  xh = (y - mu) * rs;
-  float z = xh + be;
-  if (relu) z = fmaxf(z, 0.f);
-  return z;
-}
-
-template <int V> struct Vec;
-template <> struct Vec<4> {
-  static __device__ __forceinline__ void ld(const float* p, float (&o)[4]) {
-    const float4 v = *reinterpret_cast<const float4*>(p); o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
-  static __device__ __forceinline__ void st(float* p, const float (&o)[4]) {
-    *reinterpret_cast<float4*>(p) = make_float4(o[0], o[1], o[2], o[3]); }
-};
-template <> struct Vec<1> {
-  static __device__ __forceinline__ void ld(const float* p, float (&o)[1]) { o[0] = *p; }
-  static __device__ __forceinline__ void st(float* p, const float (&o)[1]) { *p = o[0]; }
-};
 
 // ---- statistics of a materialised (rows, F) tensor (the k = 1 layers), stage 1 -------------------------------------------------
 // grid = (row chunks, column blocks of 64 * VW), lane = VW adjacent columns.  A wave sums its <= 16 rows of the piece in fp32
@@ -249,9 +205,8 @@ __global__ __launch_bounds__(256) void seg_bn_act_kernel(const float* __restrict
 // ---- conv0: BN + ReLU + max / mean over the k recomputed edge rows of each point, with the table row of the point's cloud ---------
 // item = (point, channel quad); XCD x (blockIdx % 8) owns the x-th eighth of the points and its blocks sweep it side by side (the
 // item map of bn.hip's edge kernels).  The k terms of the mean are added in ascending m and scaled by 1.0f / k, as there.
-// CNT: also cnt_out (rows, F) = #ties of the max + CNT_POS * #(z > 0), the packing of bn.hip's edge forward (exact small integers,
-// k < CNT_POS), which the backward reads; max_out / mean_out are formed by the same instructions in both instantiations.
-constexpr int CNT_POS = 256;
+// CNT: also cnt_out (rows, F) = the packed count of bn_common.h (k < CNT_POS), which the backward reads; max_out / mean_out are
+// formed by the same instructions in both instantiations.
 template <bool CNT>
 __global__ __launch_bounds__(256) void seg_edge_bn_act_kreduce_kernel(const float* __restrict__ V, int64_t ldv, const float* __restrict__ U,
                                                                       int64_t ldu, const int32_t* __restrict__ idx, int64_t rows, int k,
@@ -295,7 +250,7 @@ __global__ __launch_bounds__(256) void seg_edge_bn_act_kreduce_kernel(const floa
             const float z = bn_z(y[j][c] + u[c], mu[c], rs[c], be[c], relu);
             if (CNT) {
               cn[c] = (z > mx[c]) ? 1.f : ((z == mx[c]) ? cn[c] + 1.f : cn[c]);
-              np[c] += (z > 0.f) ? (float)CNT_POS : 0.f;
+              np[c] += cnt_pos_term(z);
             }
             mx[c] = (z > mx[c]) ? z : mx[c];
             sm[c] += z;
@@ -333,7 +288,7 @@ int check_seg_edge(const char* what, const float* V, int64_t ldv, const float* U
   DG_REQUIRE(rows > 0 && k > 0 && F > 0, DGCNN_EINVAL, "%s: bad shape", what);
   DG_REQUIRE(F % 4 == 0 && F <= 1024, DGCNN_EUNSUP, "%s: F must be a multiple of 4, <= 1024 (got %d)", what, F);
   DG_REQUIRE((int64_t)rows * k < (1ll << 31), DGCNN_EUNSUP, "%s: rows * k >= 2^31", what);
-  DG_REQUIRE(rows < (1 << 24) && ldv < (1 << 24) && (int64_t)rows * ldv < (1ll << 32), DGCNN_EUNSUP,
+  DG_REQUIRE(row_offset24_ok(rows, ldv), DGCNN_EUNSUP,
              "%s: rows * ldv must be < 2^32 elements (32-bit row offsets inside the tower)", what);
   DG_REQUIRE(a16(V) && a16(U) && ldv % 4 == 0 && ldu % 4 == 0 && ldv >= F && ldu >= F, DGCNN_EINVAL,
              "%s: V, U must be 16-byte aligned with leading dimensions %% 4 == 0", what);
@@ -482,9 +437,7 @@ struct K1Terms {
     for (int j = 0; j < VW; ++j) {
       float xh;
       const float z = bn_z(v.y[j], p.mu[j], p.rs[j], p.be[j], relu, xh);
-      float dz = v.d[j];
-      if (d2) dz += v.e[j];                                   // the output had two consumers: one fp32 add
-      if (relu && !(z > 0.f)) dz = 0.f;
+      const float dz = bn_dz_row(z, d2 ? v.d[j] + v.e[j] : v.d[j], relu);     // (two consumers of the output: one fp32 add)
       s0[j] += dz;
       s1[j] += dz * xh;
     }
@@ -513,7 +466,7 @@ struct PointTerms {
     const float invk = 1.0f / (float)k, kf = (float)k;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float npos = floorf(v.c[j] * (1.0f / CNT_POS));
+      const float npos = cnt_npos(v.c[j]);
       const float g1 = (v.a[j] > 0.f) ? v.d[j] : 0.f;
       const float g2 = v.e[j] * invk;
       s0[j] += g1 + g2 * npos;
@@ -622,17 +575,15 @@ __global__ __launch_bounds__(256) void seg_bn_bwd_apply_kernel(const float* T, i
     for (int j = 0; j < VW; ++j) {
       float xh;
       const float z = bn_z(y[j], mu[j], rs[j], be[j], relu, xh);
-      float dz = d[j];
-      if (relu && !(z > 0.f)) dz = 0.f;
-      o[j] = rs[j] * (dz - k1[j] - xh * k2[j]);
+      o[j] = bn_dy(rs[j], bn_dz_row(z, d[j], relu), k1[j], xh, k2[j]);
     }
     Vec<VW>::st(dT + r * lddt + f, o);
   }
 }
 
 // ---- conv0: y = V[idx] + U and z recomputed by the forward's instruction sequence (z == mx compares equal to the maximum it took);
-// dz = ((z == mx) ? dmax / ties : 0) + dmean * (1.0f / k), zero where relu and !(z > 0); dY (rows * k, F) and dYsum (rows, F) = the k
-// rows added in ascending m.  The item map of seg_edge_bn_act_kreduce_kernel.
+// dz = bn_dz_edge with dmax / ties and dmean * (1.0f / k); dY (rows * k, F) and dYsum (rows, F) = the k rows added in ascending m.
+// The item map of seg_edge_bn_act_kreduce_kernel.
 __global__ __launch_bounds__(256) void seg_edge_bn_bwd_apply_kernel(const float* __restrict__ V, int64_t ldv, const float* __restrict__ U,
                                                                     int64_t ldu, const int32_t* __restrict__ idx, int64_t rows, int k, int F,
                                                                     const int32_t* __restrict__ row_group, const float* __restrict__ mean,
@@ -664,7 +615,7 @@ __global__ __launch_bounds__(256) void seg_edge_bn_bwd_apply_kernel(const float*
     Vec<4>::ld(mx_in + r * ldmx + f, mx); Vec<4>::ld(cnt_in + r * F + f, ties);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      ties[c] -= (float)CNT_POS * floorf(ties[c] * (1.0f / CNT_POS));
+      ties[c] = cnt_ties(ties[c]);
       acc[c] = 0.f;
     }
     const int32_t* ip = idx + r * k;
@@ -685,9 +636,9 @@ __global__ __launch_bounds__(256) void seg_edge_bn_bwd_apply_kernel(const float*
           for (int c = 0; c < 4; ++c) {
             float xh;
             const float z = bn_z(y[j][c] + u[c], mu[c], rs[c], be[c], relu, xh);
-            float dz = ((z == mx[c]) ? dmx[c] / ties[c] : 0.f) + dmn[c] * invk;
-            if (relu && !(z > 0.f)) dz = 0.f;
-            o[c] = rs[c] * (dz - k1[c] - xh * k2[c]);
+            // bn_common.h:bn_edge_dout spelled out: as an argument the division leaves the tie's arm (profiles/bn_common/isa_compare.txt)
+            const float dz = bn_dz_row(z, ((z == mx[c]) ? dmx[c] / ties[c] : 0.f) + dmn[c] * invk, relu);
+            o[c] = bn_dy(rs[c], dz, k1[c], xh, k2[c]);
             acc[c] += o[c];
           }
           Vec<4>::st(dy + (int64_t)(m + j) * F, o);

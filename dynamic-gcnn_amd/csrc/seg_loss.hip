@@ -22,18 +22,6 @@ constexpr int SEG_LANES = SEG_CHUNK / SEG_WAVES;    // ... one per lane: a piece
 constexpr int FIN_THREADS = 256;
 constexpr int FIN_BATCH = 8;                        // independent slot loads in flight per thread (stage 2)
 
-__device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
-
-// the cloud that holds row r: the largest b in [0, nseg) with seg_off[b] <= r
-__device__ __forceinline__ int cloud_of_row(const int32_t* __restrict__ seg_off, int nseg, int r) {
-  int lo = 0, hi = nseg - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (seg_off[mid] <= r) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
 // ---- stage 1: the rows (softmax, dlogits) and, with labels, part[chunk + b][2] = (sum of w * xent, #correct) of every piece ------
 // SUMS = false (labels == nullptr): the softmax only, no shared memory, `part` untouched.
 template <bool SUMS>

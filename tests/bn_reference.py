@@ -23,7 +23,7 @@ def f32(a):
 
 # ---------------------------------------------------------------------------------------------------------------- decisions
 def bn_z32(y, mu, rs, be, relu):
-    """-> (z, xh) in float32, one rounding per operation (bn.hip:bn_z).  `relu` is tested for truth of bit 0."""
+    """-> (z, xh) in float32, one rounding per operation (bn_common.h:bn_z).  `relu` is tested for truth of bit 0."""
     y, mu, rs, be = f32(y), f32(mu), f32(rs), f32(be)
     xh = (y - mu) * rs
     z = xh + be
