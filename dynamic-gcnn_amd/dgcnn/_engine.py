@@ -867,6 +867,88 @@ def interpolate(f2d, idx, dist, B, M, N, k, packed, eps, out=None):
     return y
 
 
+FPS_MAX_C = 64                               # fps.hip: sampling runs on coordinates or narrow feature rows
+
+
+def fps(x2d, B, N, m, seg=None, sseg=None, start=None, want_dist=False):
+    """Farthest point sampling (dgcnn_fps_f32, include/dgcnn_hip.h K7).  Dense: x2d (B*N, C), m samples per cloud -> idx (B, m) int32,
+    cloud-local.  Packed (seg and sseg, both Segments of the same number of clouds; B = 1, N = the tower's rows): cloud b is sampled
+    sseg's b-th size times -> idx (sseg.rows,) int32, rows of the tower.  start: None or a host sequence of one cloud-local row per
+    cloud.  Returns idx or (idx, dist).  A selection: nothing is recorded."""
+    C = x2d.shape[1]
+    if C > FPS_MAX_C or C < 1:
+        raise ValueError("farthest_point_sample: C=%d channels, the sampling takes 1 ... %d" % (C, FPS_MAX_C))
+    if (seg is None) != (sseg is None):
+        raise ValueError("farthest_point_sample: both offsets (rows and samples) or neither")
+    if seg is not None:
+        sizes, counts = np.diff(seg.host), np.diff(sseg.host)
+        if seg.nseg != sseg.nseg or x2d.shape[0] != seg.rows:
+            raise ValueError("farthest_point_sample: %d clouds of rows (%d rows, the tower has %d), %d clouds of samples"
+                             % (seg.nseg, seg.rows, x2d.shape[0], sseg.nseg))
+        if (counts > sizes).any():
+            b = int(np.flatnonzero(counts > sizes)[0])
+            raise ValueError("farthest_point_sample: m=%d exceeds the %d rows of cloud %d" % (counts[b], sizes[b], b))
+        nseg, rows, samples, max_n, max_m = seg.nseg, seg.rows, sseg.rows, seg.max_n, sseg.max_n
+        steps = float((sizes * counts).sum())
+    else:
+        if x2d.shape[0] != B * N:
+            raise ValueError("farthest_point_sample: %d rows, expected B * N = %d" % (x2d.shape[0], B * N))
+        if m < 1 or m > N:
+            raise ValueError("farthest_point_sample: m=%d must be in [1, N=%d]" % (m, N))
+        nseg, rows, samples, max_n, max_m = B, B * N, B * m, N, m
+        sizes = np.full(B, N)
+        steps = float(B) * N * m
+    if start is not None:
+        start = np.asarray(start, np.int64).reshape(-1)
+        if start.size != nseg or (start < 0).any() or (start >= sizes).any():
+            raise ValueError("farthest_point_sample: start must hold one row inside each of the %d clouds, got %s" % (nseg, start.tolist()))
+    H.require_gpu(x2d)
+    dev = x2d.device
+    idx = torch.empty((samples,) if seg is not None else (B, m), dtype=torch.int32, device=dev)
+    dist = torch.empty(tuple(idx.shape), dtype=torch.float32, device=dev) if want_dist else None
+    st = None if start is None else torch.from_numpy(start.astype(np.int32)).to(dev)
+    ws, nws = _knn_workspace(x2d, "dgcnn_fps_workspace_bytes", rows, C, max_n)
+    res = int(H.load().dgcnn_fps_resident_max_n(C))
+    tag = "fps[%s]" % "+".join((["fps_resident_kernel<C%d>" % C] if res and (seg is not None or max_n <= res) else []) + (["fps_stream_kernel"] if max_n > res else []))
+    H.call("dgcnn_fps_f32", x2d.data_ptr(), H.ld2(x2d), C, nseg, H._p(None if seg is None else seg.device(dev)),
+           H._p(None if sseg is None else sseg.device(dev)), rows, samples, max_n, max_m, H._p(st), idx.data_ptr(), H._p(dist),
+           ws.data_ptr() if nws else 0, nws, tag=tag, work=3.0 * C * steps)
+    return (idx, dist) if want_dist else idx
+
+
+def take_rows(x2d, idx, B, M, N, packed):
+    """y (s_rows, F) = the rows of x2d that idx names (dgcnn_rows_gather_f32): dense -- x2d (B*N, F), idx (B, M) int32 cloud-local;
+    packed -- x2d (N, F) with B = 1, idx (M,) int32 tower rows.  idx must hold DISTINCT rows per cloud (farthest point sampling
+    guarantees it).  Recorded: d(x2d) receives the scatter of d(y) (dgcnn_rows_scatter_f32; beta = 0 on a gradient buffer nobody has
+    touched, which the scatter then fills whole, else beta = 1)."""
+    c = ctx()
+    x_rows, F = x2d.shape
+    s_rows = B * M
+    if x_rows != B * N:
+        raise ValueError("take_rows: x has %d rows, expected %d" % (x_rows, B * N))
+    if idx.dtype != torch.int32:
+        raise TypeError("take_rows: idx must be int32 (what farthest_point_sample returns), got %s" % idx.dtype)
+    if idx.numel() != s_rows:
+        raise ValueError("take_rows: idx holds %d rows, expected %d" % (idx.numel(), s_rows))
+    H.require_gpu(x2d, idx)
+    idx = idx.contiguous()
+    Md, Nd = (0, 0) if packed else (M, N)
+    y = c.new_buffer(s_rows, F)
+    moved = 8.0 * s_rows * F
+    H.call("dgcnn_rows_gather_f32", x2d.data_ptr(), H.ld2(x2d), idx.data_ptr(), s_rows, x_rows, Md, Nd, F, y.data_ptr(), H.ld2(y),
+           tag="rows_gather_kernel", work=moved, nbytes=moved)
+    if c.recording:
+        def bwd():
+            dy = c.grad(y)
+            if dy is None or not c.tracked(x2d):
+                return
+            dx, beta = c.grad_w(x2d)
+            H.call("dgcnn_rows_scatter_f32", dy.data_ptr(), H.ld2(dy), idx.data_ptr(), s_rows, x_rows, Md, Nd, F, dx.data_ptr(),
+                   H.ld2(dx), int(beta), tag="rows_scatter_kernel", work=moved, nbytes=moved)
+        c.tape.append(bwd)
+    return y
+
+
 def _tile_m(M, N):
     """Mirror of gemm.hip:tile_m (only used to name the kernel instance in bench.py's roofline tags)."""
     return 128

@@ -49,6 +49,11 @@ PROTOTYPES = {
     "dgcnn_interp_f32": [c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_f32, c_vp, c_vp, c_i64, c_vp],
     "dgcnn_interp_bwd_workspace_bytes": [c_int, c_int, c_int],
     "dgcnn_interp_bwd_f32": [c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_int, c_vp, c_sz, c_vp],
+    "dgcnn_fps_resident_max_n": [c_int],
+    "dgcnn_fps_workspace_bytes": [c_int, c_int, c_int],
+    "dgcnn_fps_f32": [c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp],
+    "dgcnn_rows_gather_f32": [c_vp, c_i64, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp],
+    "dgcnn_rows_scatter_f32": [c_vp, c_i64, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_int, c_vp],
     "dgcnn_edge_gather_f32": [c_vp, c_i64, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp],
     "dgcnn_edge_gather_bwd_f32": [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp],
     "dgcnn_edge_mlp_f32": [c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp],
@@ -193,7 +198,8 @@ PROTOTYPES = {
 }
 
 INT64_RESULTS = ("dgcnn_knn_workspace_bytes", "dgcnn_knn_seg_workspace_bytes", "dgcnn_knn_seg_grid_workspace_bytes",
-                 "dgcnn_knn_seg_mix_workspace_bytes", "dgcnn_knn_cross_workspace_bytes", "dgcnn_interp_bwd_workspace_bytes", "dgcnn_edge_mlp_bf16_bwd_workspace_bytes", "dgcnn_seg_colsum_workspace_bytes",
+                 "dgcnn_knn_seg_mix_workspace_bytes", "dgcnn_knn_cross_workspace_bytes", "dgcnn_interp_bwd_workspace_bytes", "dgcnn_fps_workspace_bytes",
+                 "dgcnn_edge_mlp_bf16_bwd_workspace_bytes", "dgcnn_seg_colsum_workspace_bytes",
                  "dgcnn_seg_stats_workspace_bytes", "dgcnn_seg_softmax_xent_workspace_bytes")      # byte counts; every other entry point returns an int status
 
 _lib = None

@@ -7,6 +7,8 @@ aliases BASELINE.json's north_star uses for `k_nn` / `edge_conv`.
 """
 from __future__ import annotations
 
+import math
+
 import torch
 
 from . import _engine as E
@@ -49,7 +51,7 @@ def _segments(points, offsets, ks, bn_per_cloud=False, bn_per_cloud_train=False)
     return seg
 
 
-def _rows_channels(t, what, packed):
+def _rows_channels(t, what, packed, who="k_nn"):
     """(B, rows per cloud, C) of a dense (B,N,C) set, or (1, R, C) of a packed (R,C) / (1,R,C) tower -- from the shape alone"""
     shp = tuple(t.shape)
     if packed:
@@ -57,9 +59,9 @@ def _rows_channels(t, what, packed):
             return 1, shp[0], shp[1]
         if len(shp) == 3 and shp[0] == 1:
             return 1, shp[1], shp[2]
-        raise ValueError("k_nn: a packed %s tower is (R,C) or (1,R,C), got %s" % (what, shp))
+        raise ValueError("%s: a packed %s tower is (R,C) or (1,R,C), got %s" % (who, what, shp))
     if len(shp) != 3:
-        raise ValueError("k_nn: %s must be (B,N,C), got %s" % (what, shp))
+        raise ValueError("%s: %s must be (B,N,C), got %s" % (who, what, shp))
     return shp
 
 
@@ -122,22 +124,22 @@ def k_nn(points, k, offsets=None, queries=None, query_offsets=None, return_dist=
 knn = k_nn
 
 
-def _interp_rows(t, what, packed, rank4=False):
+def _interp_rows(t, what, packed, rank4=False, who="interpolate"):
     """(clouds, rows per cloud, channels) of an argument of `interpolate`, from its shape alone: dense (B,N,C) [(B,N,1,C) with rank4],
     packed (R,C) or (1,R,C) [(1,R,1,C) with rank4]"""
     shp = tuple(t.shape)
     if rank4 and len(shp) == 4:
         if shp[2] != 1:
-            raise ValueError("interpolate: a rank-4 %s has a singleton axis -2, got %s" % (what, shp))
+            raise ValueError("%s: a rank-4 %s has a singleton axis -2, got %s" % (who, what, shp))
         shp = (shp[0], shp[1], shp[3])
     if packed:
         if len(shp) == 2:
             return 1, shp[0], shp[1]
         if len(shp) == 3 and shp[0] == 1:
             return 1, shp[1], shp[2]
-        raise ValueError("interpolate: a packed %s tower is (R,C) or (1,R,C), got %s" % (what, tuple(t.shape)))
+        raise ValueError("%s: a packed %s tower is (R,C) or (1,R,C), got %s" % (who, what, tuple(t.shape)))
     if len(shp) != 3:
-        raise ValueError("interpolate: %s must be (B,N,C), got %s" % (what, tuple(t.shape)))
+        raise ValueError("%s: %s must be (B,N,C), got %s" % (who, what, tuple(t.shape)))
     return shp
 
 
@@ -222,6 +224,104 @@ def interpolate(features, points, queries, k=3, offsets=None, query_offsets=None
     H.call("dgcnn_copy2d_f32", s2d.data_ptr(), H.ld2(s2d), tail.data_ptr(), H.ld2(tail), B * M, Cs, 0)
     E_copy_grad(s2d, tail)
     return E.rank4(buf, B, M)
+
+
+def _fps_counts(m, ratio, sizes, dense):
+    """The sample count of every cloud, from m (an int for every cloud, or -- packed only -- one int per cloud) or ratio in (0, 1]"""
+    if (m is None) == (ratio is None):
+        raise ValueError("farthest_point_sample: exactly one of m and ratio is given (got %s)" % ("both" if m is not None else "neither"))
+    if ratio is not None:
+        ratio = float(ratio)
+        if not (0.0 < ratio <= 1.0):
+            raise ValueError("farthest_point_sample: ratio=%r must be in (0, 1]" % ratio)
+        return [int(math.ceil(ratio * n)) for n in sizes]
+    if isinstance(m, (list, tuple)) or (hasattr(m, "ndim") and getattr(m, "ndim") == 1):
+        if dense:
+            raise ValueError("farthest_point_sample: a dense call takes one m for every cloud, got a sequence")
+        counts = [int(v) for v in m]
+        if len(counts) != len(sizes):
+            raise ValueError("farthest_point_sample: m holds %d counts, the tower has %d clouds" % (len(counts), len(sizes)))
+    else:
+        counts = [int(m)] * len(sizes)
+    for b, (v, n) in enumerate(zip(counts, sizes)):
+        if v < 1:
+            raise ValueError("farthest_point_sample: m=%d must be at least 1" % v)
+        if v > n:
+            raise ValueError("farthest_point_sample: m=%d exceeds the %d rows of cloud %d" % (v, n, b))
+    return counts
+
+
+def farthest_point_sample(points, m=None, ratio=None, offsets=None, start=None, return_dist=False):
+    """Farthest point sampling (PointNet++ set abstraction, PyG's fps): from every cloud the start row, then again and again the row
+    farthest (squared L2) from the rows selected so far, ties -> the lower row (include/dgcnn_hip.h K7 states the arithmetic bit for
+    bit).  One persistent workgroup per cloud walks the whole chain in one launch.
+    Exactly one of m (samples per cloud) and ratio in (0, 1] (ceil(ratio * n) samples of a cloud of n rows, as PyG counts).
+    Dense: points (B,N,C) -> idx (B,m) int32, cloud-local rows.
+    Packed: points (R,C) or (1,R,C) with offsets (a sequence or a Segments); m an int for every cloud or one int per cloud ->
+    (idx (S,) int32 rows of the tower, sample_offsets): sample_offsets is a Segments over the S samples, ready to be the
+    query_offsets= of k_nn / interpolate for the sampled set.
+    start: None (row 0 of every cloud), an int, or a host sequence of one cloud-local row per cloud.
+    return_dist: appends dist, float32 in idx's shape: +inf for the start row, then the squared distance of every sample to the ones
+    before it.  The result is m distinct rows whatever the input holds; rows with a non-finite coordinate are taken last.
+    C <= 64.  No gradient: a selection, like k_nn."""
+    packed = offsets is not None
+    _, N, C = _rows_channels(points, "points", packed, who="farthest_point_sample")
+    B = 1 if packed else points.shape[0]
+    if C > E.FPS_MAX_C or C < 1:
+        raise ValueError("farthest_point_sample: C=%d channels, the sampling takes 1 ... %d" % (C, E.FPS_MAX_C))
+    seg = _segments(points, offsets, []) if packed else None
+    sizes = [int(v) for v in (seg.host[1:] - seg.host[:-1])] if packed else [N] * B
+    if not packed and (B < 1 or N < 1):
+        raise ValueError("farthest_point_sample: points must hold at least one cloud of at least one row, got %s" % (tuple(points.shape),))
+    counts = _fps_counts(m, ratio, sizes, not packed)
+    if start is not None:
+        st = [int(v) for v in start] if hasattr(start, "__len__") else [int(start)] * len(sizes)
+        if len(st) != len(sizes):
+            raise ValueError("farthest_point_sample: start holds %d rows, there are %d clouds" % (len(st), len(sizes)))
+        for b, (v, n) in enumerate(zip(st, sizes)):
+            if v < 0 or v >= n:
+                raise ValueError("farthest_point_sample: start=%d is outside the %d rows of cloud %d" % (v, n, b))
+        start = st
+    # ---- device work from here on
+    x2d = E.as2d(points)[0]
+    if packed:
+        soff = [0]
+        for v in counts:
+            soff.append(soff[-1] + v)
+        sseg = E.Segments(soff)
+        res = E.fps(x2d, 1, N, 0, seg=seg, sseg=sseg, start=start, want_dist=bool(return_dist))
+        return (res[0], sseg, res[1]) if return_dist else (res, sseg)
+    return E.fps(x2d, B, N, counts[0], start=start, want_dist=bool(return_dist))
+
+
+def take_rows(x, idx, offsets=None):
+    """The rows of x that idx names -- the sampled coordinates or features after farthest_point_sample.
+    Dense: x (B,N,F) or (B,N,1,F), idx (B,m) int32 cloud-local -> (B,m,F) / (B,m,1,F).
+    Packed: x (R,F), (1,R,F) or (1,R,1,F) with offsets (the tower's), idx (S,) int32 tower rows -> (S,F), (1,S,F) / (1,S,1,F).
+    idx must hold DISTINCT rows per cloud (farthest_point_sample guarantees it): the backward writes every gradient row from one
+    sample, without atomics.  Recorded, x receives the scatter of the result's gradient; idx carries none."""
+    packed = offsets is not None
+    shp = tuple(x.shape)
+    B, N, F = _interp_rows(x, "x", packed, rank4=True, who="take_rows")
+    ishp = tuple(idx.shape)
+    if packed:
+        seg = offsets if isinstance(offsets, E.Segments) else E.Segments(offsets)
+        if seg.rows != N:
+            raise ValueError("take_rows: offsets end at %d, x has %d rows" % (seg.rows, N))
+        if len(ishp) != 1 or ishp[0] < 1:
+            raise ValueError("take_rows: a packed idx is (S,), got %s" % (ishp,))
+        M = ishp[0]
+    else:
+        if len(ishp) != 2 or ishp[0] != B or ishp[1] < 1 or ishp[1] > N:
+            raise ValueError("take_rows: idx must be (B=%d, m <= N=%d), got %s" % (B, N, ishp))
+        M = ishp[1]
+    if idx.dtype != torch.int32:
+        raise ValueError("take_rows: idx must be int32 (what farthest_point_sample returns), got %s" % idx.dtype)
+    # ---- device work from here on
+    y = E.take_rows(E.as2d(x)[0], idx, B, M, N, packed)
+    if len(shp) == 4:
+        return E.rank4(y, B, M)
+    return y if len(shp) == 2 else y.view(B, M, F)
 
 
 def edges(points, k=20, offsets=None):

@@ -267,6 +267,66 @@ int64_t dgcnn_interp_bwd_workspace_bytes(int q_rows, int p_rows, int k);
 int dgcnn_interp_bwd_f32(const float* dy, int64_t lddy, const int32_t* idx, const float* a, int q_rows, int p_rows, int M, int N,
                          int k, int F, float* dfeat, int64_t lddf, int beta, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- K7: farthest point sampling, the row take and its backward (csrc/fps.hip) -- the downsampling half of a hierarchical point
+ * network (PointNet++ set abstraction, PyG's fps): the producer of the second point set of dgcnn_knn_cross_f32 / dgcnn_interp_f32.
+ * NORMATIVE arithmetic, for one cloud of n rows and C channels sampled m times (1 <= m <= n); every operation is rounded to fp32 once,
+ * nothing is fused or reassociated:
+ *     bad_i   = row i holds a coordinate that is not finite (NaN, +inf or -inf)
+ *     mind_i  = bad_i ? 0.0f : +inf                                  for every row i
+ *     D(i, s) : t = x_i[0] - x_s[0]; D = t * t;  then t = x_i[c] - x_s[c]; D = D + t * t     for c = 1 ... C-1, ascending
+ *     s_0     = start (cloud-local; 0 when no start is given; a start outside [0, n) counts as 0)
+ *     step j = 0 ... m-1:
+ *         idx[j]  = s_j;   dist[j] = mind_{s_j} as it stands at this moment (+inf for an ordinary start row)
+ *         mind_i  = (D(i, s_j) < mind_i) ? D(i, s_j) : mind_i        for every row i (a NaN or +inf D lowers nothing)
+ *         mind_{s_j} = -1.0f                                          a selected row is never selected again
+ *         s_{j+1} = the row with the largest mind; ties -> the LOWER row index
+ *   What follows from these rules:
+ *   - the result is m DISTINCT rows of the cloud, whatever the input holds;
+ *   - bad rows are chosen only after every finite row that is not a duplicate of a selected one; such duplicates tie with the bad rows
+ *     at mind = 0, lower index first.  A bad row does not disturb the others: its D is NaN or +inf towards every row, in both roles;
+ *   - the first m' entries of an m-sample are the m'-sample (prefix property);
+ *   - duplicates of a selected point sit at mind = 0;
+ *   - mind is never -0.0 (t * t is +0.0 or larger, or NaN) and never NaN, so the non-negative floats and +inf order as their bit
+ *     patterns: a kernel may reduce on an integer key, provided the selected-row sentinel maps below every real value.
+ *   dist[j] for j >= 1 is the squared distance of sample j to the samples before it (the coverage radius after j samples, squared).
+ * x: rows of C floats, row stride ldx >= C, no alignment beyond 4 bytes (raw coordinates have C = 3).
+ * Dense call: x_off == s_off == NULL, nseg clouds of max_n rows and max_m samples each, rows = nseg max_n, samples = nseg max_m; idx
+ *   (samples int32) holds cloud-local rows.
+ * Packed call: x_off and s_off (device, nseg + 1 int32 each) strictly increasing from 0 to rows / samples: cloud b = rows
+ *   [x_off[b], x_off[b + 1]) sampled s_off[b + 1] - s_off[b] times; idx holds rows of the TOWER.  max_n / max_m = the host-known largest
+ *   cloud and largest sample count.  A cloud asked for more samples than it has rows cannot be seen on the host by this entry (the
+ *   Python layer refuses it from its host offsets): the kernel clamps it to n samples and writes -1 into the rest of idx (and dist).
+ * start: NULL, or nseg device int32 of cloud-local rows.  dist: NULL, or samples floats.
+ * 1 <= C <= 64, nseg in [1, 65535].  One workgroup of 1024 threads per cloud, in one of two forms chosen per cloud from its own n:
+ *   resident  (C <= 4 and n <= dgcnn_fps_resident_max_n(C) = 16384): coordinates and mind in registers, one barrier per step;
+ *   streaming (everything else): coordinates re-read every step, mind in the workspace.
+ *   No workgroup waits for another one.  No host synchronisation, no read-back; one launch for a dense call, at most two (one per form) for a
+ *   packed one.
+ * dgcnn_fps_resident_max_n(C): the largest cloud the resident form takes for that C, 0 where it takes none.
+ * dgcnn_fps_workspace_bytes(rows, C, max_n): rows floats rounded up to 256 bytes when some cloud of the call can need the streaming
+ *   form (max_n > dgcnn_fps_resident_max_n(C)), else 0 (ws may then be NULL); 0 also for sizes the entry refuses.
+ * DGCNN_EINVAL for a null x / idx, exactly one of x_off / s_off null, non-positive sizes, dense sizes that do not multiply out,
+ *   max_m > max_n, ldx < C, a missing or misaligned (16 bytes) workspace where one is needed; DGCNN_EUNSUP for C > 64 or nseg > 65535;
+ *   DGCNN_ENOSPC for a workspace that is too small.  Every refusal happens before any launch, with the reason in dgcnn_last_error. */
+int dgcnn_fps_resident_max_n(int C);
+int64_t dgcnn_fps_workspace_bytes(int rows, int C, int max_n);
+int dgcnn_fps_f32(const float* x, int64_t ldx, int C, int nseg, const int32_t* x_off, const int32_t* s_off, int rows, int samples,
+                  int max_n, int max_m, const int32_t* start, int32_t* idx, float* dist, void* ws, size_t ws_bytes, void* stream);
+/* The row take and its backward.  row(s) = (s / M) * N + idx[s] for M > 0 (dense: idx cloud-local, s_rows = B M, x_rows = B N), and
+ * idx[s] for M == N == 0 (idx holds tower rows) -- what dgcnn_fps_f32 returns in its two call forms.
+ * gather:  y[s][0..F) = x[row(s)][0..F).
+ * scatter: beta = 0: dx = 0 everywhere (x_rows rows of F), then dx[row(s)] = dy[s];  beta = 1: dx[row(s)] = dx[row(s)] + dy[s].
+ *   The rows of idx are TRUSTED TO BE DISTINCT (per cloud), as farthest point sampling guarantees: every dx row has at most one
+ *   writer, so there are no atomics and one result run to run.  With repeated rows the scatter keeps one of the writers.
+ * Any F >= 1; leading dimensions >= F.  A float4 path when F % 4 == 0, both leading dimensions % 4 == 0 and both bases are 16-byte
+ *   aligned; a scalar path otherwise (coordinates have F = 3).  The contents of idx are trusted to lie inside the cloud.
+ * DGCNN_EINVAL for a null pointer, F < 1, rows < 1, negative M / N, M > 0 with s_rows % M != 0 or x_rows != (s_rows / M) N, M == 0
+ *   with N != 0, a leading dimension below F, beta outside {0, 1}.  Every refusal happens before any launch. */
+int dgcnn_rows_gather_f32(const float* x, int64_t ldx, const int32_t* idx, int s_rows, int x_rows, int M, int N, int F, float* y,
+                          int64_t ldy, void* stream);
+int dgcnn_rows_scatter_f32(const float* dy, int64_t lddy, const int32_t* idx, int s_rows, int x_rows, int M, int N, int F, float* dx,
+                           int64_t lddx, int beta, void* stream);
+
 /* ---- K3 in its bf16-operand form (BASELINE configs[2] "bf16 edge-MLP MFMA"): conv0 of an EdgeConv layer, ops.py:21-52 ------
  * E[e] = [x_i, x_j - x_i] formed in fp32 and rounded to bf16 once (RNE), W0 (2C x F, row-major) rounded to bf16 once,
  * y = E W0 on v_mfma_f32_32x32x16_bf16 with fp32 accumulation; neither E nor y is written by the two forward passes:
